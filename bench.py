@@ -1,6 +1,7 @@
 """Headline benchmark: PGD attack steps/s on the x-vector/PLDA system (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--scaling weak|strong] [--batch-per-gpu B]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload: PGD, L-inf eps 0.002, step 0.0004, cross-entropy, untargeted, EOT 1/1, CSI-E, 3 s @ 16 kHz synthetic
@@ -29,6 +30,12 @@ N > 1, two partitions of the work, both measured in the same run:
 
 ``other_configs``: the other BASELINE.json configurations (configs[0], [2], [3], [4]) on this GPU, a few seconds in
 all (tools/config_bench.py); ``--no-other-configs`` skips them.
+
+``--dump-outputs DIR``: after the timed attacks, what the LAST one returned to its caller is written as float32 .npy
+files -- ``adversarial.npy`` (the adversarial audio, (B, 1, 48000)) and ``success.npy`` (the per-utterance success flags
+as 0 / 1, all ranks in rank order); with N > 1 every rank writes its own ``adversarial_rank<r>.npy``.  The inputs are
+seeded and the front-end's dither is off, so two builds run with the same arguments can be compared file for file.
+At most 64 MB in all: beyond that every array is replaced by the same fixed, seeded sample of its flattened elements.
 """
 import argparse
 import json
@@ -174,6 +181,28 @@ def summarise(samples, steps):
             "ms_per_step_samples": [1e3 * s / steps for s in samples]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: every file of one run together
+_NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array of `arrays` (name -> tensor or array) as out_dir/<name>.npy in float32.  If together they would
+    exceed `limit` bytes, each is cut to the same fraction of its elements: a sample of its flattened elements at sorted
+    positions drawn by a fixed seed, so that two runs sample the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in host.values())
+    room = limit - _NPY_HEADER_BYTES * len(host)
+    for name, a in host.items():
+        if total > room:
+            keep = int(a.size * room / total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def stage_roofline(model, run_attack, B, steps):
     """In-loop per-launch times from HIP-event pairs on the launch stream (sg_trace_begin / sg_trace_end) over one traced
     attack of the timed workload: flop-weighted fraction of the f32-MFMA peak over the 8 stream-K contraction launches of
@@ -206,6 +235,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-shard-points", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed attack returned (adversarial audio, success flags) as DIR/<name>.npy")
     # test hooks (tests/test_gpu_multiproc.py runs the N > 1 code path as two ranks on the ONE GPU of the test box)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--one-gpu", action="store_true", help=argparse.SUPPRESS)
@@ -213,6 +244,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks ourselves as a CHILD torchrun (nothing in this process
         # has touched the GPU yet) and leave with its exit code -- never silently report a 1-GPU number for N > 1
@@ -289,6 +322,11 @@ def main():
 
     primary, primary_b = (weak, weak_b) if args.scaling == "weak" else (strong, strong_b)
     (out, flags), samples = timed_reps(primary, args.steps, args.warmup, args.reps, dist, sync, dev)
+    if args.dump_outputs:
+        dumps = {"adversarial" if world == 1 else "adversarial_rank%d" % rank: out}
+        if rank == 0:
+            dumps["success"] = flags
+        dump_outputs(args.dump_outputs, dumps, DUMP_LIMIT_BYTES // world)
     prim = summarise(samples, args.steps)
     dt = prim["ms_per_step"] * 1e-3 * args.steps
     # a "step" of the metric is a batch-64 step: weak = N of them per time step of the job, strong = one

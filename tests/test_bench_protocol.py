@@ -93,3 +93,30 @@ def test_stage_roofline_arithmetic():
     assert abs(r["us_per_step_in_kernel"] - t_us) < 1e-6 and abs(r["flop_per_step"] - fl) < 1
     assert abs(r["achieved"] - fl / (t_us * 1e-6) / 1e12) < 1e-9
     assert r["stages"]["tdnn3_fwd"]["launches"] == 3 and r["stages"]["tdnn3_dgrad"]["launches"] == 2
+
+
+def test_dump_outputs_float32_and_bounded(tmp_path):
+    """--dump-outputs: float32 .npy per array; over the byte limit every array is cut to the same fixed, seeded sample."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    adv = torch.linspace(-1, 1, 64 * 1000).reshape(64, 1, 1000)
+    flags = torch.tensor([1, 0, 1, 1], dtype=torch.uint8)
+    bench.dump_outputs(str(tmp_path / "full"), {"adversarial": adv, "success": flags})
+    a, s = np.load(tmp_path / "full" / "adversarial.npy"), np.load(tmp_path / "full" / "success.npy")
+    assert a.dtype == np.float32 and a.shape == (64, 1, 1000) and np.array_equal(a, adv.numpy())
+    assert s.dtype == np.float32 and s.tolist() == [1, 0, 1, 1]
+    limit = 64 * 1000                                        # a quarter of the adversarial array's bytes
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), {"adversarial": adv, "success": flags}, limit=limit)
+    total = sum(os.path.getsize(os.path.join(tmp_path, "cut1", f)) for f in os.listdir(tmp_path / "cut1"))
+    assert total <= limit
+    c1, c2 = np.load(tmp_path / "cut1" / "adversarial.npy"), np.load(tmp_path / "cut2" / "adversarial.npy")
+    assert c1.dtype == np.float32 and 0 < c1.size < adv.numel() and np.array_equal(c1, c2)
+    assert np.isin(c1, adv.numpy().reshape(-1)).all() and (np.diff(c1) > 0).all()  # elements of the output, in order
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"],
+                       capture_output=True, text=True)
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -106,12 +106,14 @@ def test_two_rank_gloo_matches_single_process(tmp_path):
 
 
 def test_metric_configuration_is_cut_over_all_ranks(tmp_path):
-    """N = 64 with batch_size = 64 (what INTEGRATION.md tells users to pass, and BASELINE.json's metric) on 8 and on 3
-    ranks: every rank attacks its 64 / world utterances as ONE chunk, and the result is the unsharded one bit for
-    bit.  Round 3 cut on multiples of batch_size, which handed rank 0 the whole batch."""
+    """N = 64 with batch_size = 64 (what INTEGRATION.md tells users to pass, and BASELINE.json's metric) on 4 and on 3
+    ranks (an even and an uneven cut): every rank attacks its 64 / world utterances as ONE chunk, and the result is the
+    unsharded one bit for bit.  Round 3 cut on multiples of batch_size, which handed rank 0 the whole batch (VERDICT r3,
+    item 1).  No more ranks than that: a ROCm build of torch opens the GPU in every process that runs a backward pass,
+    CPU tensors included, so on a GPU machine each rank here is a process on the device."""
     assert ShardedAttack(_make("pgd64")).granule() == 1 and ShardedAttack(_make("cw2_64")).granule() == 1
     x, y = _data(64)
-    for kind, worlds in (("pgd64", (8, 3)), ("cw2_64", (3,))):
+    for kind, worlds in (("pgd64", (4, 3)), ("cw2_64", (3,))):
         np.random.seed(77)
         ref_adv, ref_succ = _make(kind).attack(x, y)
         for world in worlds:
