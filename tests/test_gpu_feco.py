@@ -293,7 +293,7 @@ def test_gradient_through_feco_matches_oracle_autograd(hip_model, oracle_model, 
     # within round-off of 0 flips between the two implementations and changes the gradient of its receptive
     # field (seen at flag 2: 0.1 % of the samples, 6e-3 of max).  Hence a bulk tolerance plus a bound on outliers.
     bad = float((np.abs(got - want) > 3e-3 * gs).mean())
-    assert bad < 5e-3 and err < 2e-2, (bad, err)
+    assert bad < 5e-3 and err < 3.5e-4, (bad, err)  # err: 10x the measured 3.4e-5 at flag 2 (was 2e-2)
     assert same > 0.97
 
 
@@ -390,7 +390,7 @@ def test_audionet_feco_gradient_and_pgd_eot():
         same, (scores.cpu() - sc.detach()).abs().max().item(), err))
     assert dec.cpu().tolist() == sc.argmax(1).tolist()
     bad = float((np.abs(got - want) > 3e-3 * gs).mean())
-    assert bad < 5e-3 and err < 2e-2, (bad, err)
+    assert bad < 5e-3 and err < 1.8e-5, (bad, err)  # err: 10x the measured 1.8e-6 (was 2e-2)
     atk = PGD(dm, epsilon=0.002, step_size=0.0004, max_iter=10, batch_size=3, EOT_size=2, EOT_batch_size=1, verbose=0)
     adv, success = atk.attack(x.to(DEV), y)
     l0 = dm.loss_grad(x.to(DEV), y, SEC4SR_CrossEntropy(), want_grad=False)[2]
@@ -536,7 +536,7 @@ def test_score_vjp_and_average_order_gradient(hip_model, oracle_model):
     xin = x.clone().requires_grad_(True)
     (coef_a * oan.make_decision(xin)[1]).sum().backward()
     e_an = rel(ga.cpu().numpy(), xin.grad.numpy())
-    assert rms_hip <= 2 * rms_ora and rms_hip < 2e-2 and e_xv < 5e-2 and e_an < 2e-3, (rms_hip, rms_ora, e_xv, e_an)
+    assert rms_hip <= 2 * rms_ora and rms_hip < 2e-2 and e_xv < 5e-2 and e_an < 2.2e-5, (rms_hip, rms_ora, e_xv, e_an)  # e_an: 10x the measured 2.15e-6 (was 2e-3)
     with pytest.raises(ValueError, match="ScoreVJP"):  # a (B, S) table of the wrong shape is refused before the pass reads it
         hip_model.loss_grad(x.to(DEV), y0, ScoreVJP(coef[:2].to(DEV)))
     # the loss stage alone on given scores == the tail kernel's own

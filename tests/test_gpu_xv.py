@@ -411,7 +411,7 @@ def test_waveform_gradient_matches_oracle_autograd(hip_model, oracle_model, dev)
             nm, np.abs(arr - g64).max() / np.abs(g64).max(), np.sqrt(((arr - g64) ** 2).mean() / (g64 ** 2).mean()),
             float((np.sign(arr) != np.sign(g64)).mean())))
     np.testing.assert_allclose(got, want, rtol=0, atol=3e-3 * gs)
-    assert sign_mismatch < 5e-3
+    assert sign_mismatch < 1.5e-3  # 10x the measured 1.5e-4 (was 5e-3); the fp64 judgement: tests/test_gpu_truth.py
 
 
 def test_short_and_ragged_lengths(hip_model, oracle_model, dev):
@@ -455,7 +455,7 @@ def test_long_utterance_sliding_cmvn_and_gradient(hip_model, oracle_model, dev):
     # fp32 implementations somewhere and moves the gradient of its receptive field (same effect and policy as in
     # tests/test_gpu_feco.py): bulk tolerance + a bound on the outliers
     bad = float((np.abs(got - want) > 3e-3 * gs).mean())
-    assert bad < 5e-3 and err < 2e-2 and sm < 5e-3, (bad, err, sm)
+    assert bad < 5e-3 and err < 2e-2 and sm < 1.6e-3, (bad, err, sm)  # sm: 10x the measured 1.6e-4 (was 5e-3)
 
 
 # ------------------------------------------------------------------------------ PGD update + loops
