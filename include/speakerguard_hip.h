@@ -464,6 +464,22 @@ int sg_feco_compress_backward_reps(sg_ctx* ctx, const float* dout_dev, const int
 int sg_feco_compress_backward(sg_ctx* ctx, const float* dout_dev, const int32_t* assign_dev, const int32_t* counts_dev,
                               int32_t B, int32_t F, int32_t D, int32_t k, int32_t force, float* dfeats_dev, void* stream);
 
+/* FeCo with warped k-means (defense/feature_level.py:53-165 warped_kmeans / wk_compute): the F frames of each row cut into
+ * k contiguous segments, the boundaries moved frame by frame while the squared error falls, out (B,k,D) = the final
+ * segment means.  Determinism contract: k_feco_warped.hip header.  F <= 1200, D <= 64, 1 <= k <= F, 0 <= delta <= 1.
+ * init_mode 0: TS init (:53-77); 1: random init (:80-85) -- the k - 1 frames of lowest Philox4x32-10 rank among frames
+ *   1 .. F-1, keyed by (key + r * 0xC2B2AE3D27D4EB4F, index_base + u) for row r * rep_rows + u (rep_rows 0: r = 0, u = row),
+ *   like sg_feco_kmeans_seeded; 2: the initial boundaries are read from `boundaries` (B,k).
+ * boundaries (B,k): in for mode 2, out always (the final boundaries); init_ids (B,F) / init_counts (B,k): the INITIAL
+ *   segmentation -- the reference updates its means through `.data`, so its gradient is that of the initial segment means:
+ *   sg_feco_compress_backward(dout, init_ids, init_counts, force = 1); sweeps (B): sweeps made, the last one moving nothing.
+ * Synchronises the stream.  SG_ERR_ARG naming the row if its initial boundaries do not rise strictly from 0 (TS of a
+ * pathological input; the reference then averages empty segments: NaN) -- that row's out is zero, never NaN;
+ * SG_ERR_STATE naming the row if it still moves after 4 F sweeps (the reference's loop has no cap). */
+int sg_feco_warped(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t init_mode,
+                   double delta, uint64_t key, int64_t index_base, int32_t rep_rows, int32_t* boundaries_dev,
+                   int32_t* init_ids_dev, int32_t* init_counts_dev, float* out_dev, int32_t* sweeps_dev, void* stream);
+
 /* BASELINE.json configs[3]: PGD + EOT against the FeCo-defended AudioNet as ONE device-resident loop --
  * attack/FGSM.py:38-70 attack_batch with the model of model/defended_model.py:46-65 (FeCo at feature level 1:
  * waveform -> log-mel -> FeCo -> AudioNet CNN) and the gradient chained back through the defense by hand.
