@@ -34,6 +34,8 @@ def margin_loss(scores, label, targeted=False, confidence=0.0, task="CSI", thres
     n, num_class = scores.shape
     rows = []
     conf = torch.tensor(confidence, dtype=torch.float)
+    # CSI imposter rows: ONE 0 * sum over all of them (:97), so the sign of that zero is the batch's, as in the reference
+    imp_zero = 0.0 * torch.sum(scores[label == -1])
     for i in range(n):
         s = scores[i]
         y = int(label[i])
@@ -48,22 +50,25 @@ def margin_loss(scores, label, targeted=False, confidence=0.0, task="CSI", thres
                 onehot = torch.zeros(num_class)
                 onehot[y] = 1
                 real = torch.sum(onehot * s)
-                other = torch.max((1 - onehot) * s - onehot * 10000)
+                # torch.max(t, dim) as the reference (:77, :85, :93): a tie sends the whole gradient to the FIRST maximal
+                # index; the full reduction torch.max(t) would split it evenly between the tied entries
+                other = torch.max((1 - onehot) * s - onehot * 10000, 0)[0]
                 if targeted:
                     l = other + conf - real if task == "CSI" else torch.clamp(other, min=threshold) + conf - real
                 elif task == "CSI":
                     l = real + conf - other
                 else:
-                    f_reject = torch.max(s) + conf - threshold
+                    f_reject = torch.max(s, 0)[0] + conf - threshold
                     f_mis = torch.clamp(real, min=threshold) + conf - other
                     l = torch.minimum(f_reject, f_mis)
             elif task == "OSI":
-                l = torch.max(s) + conf - threshold if targeted else threshold + conf - torch.max(s)
+                top = torch.max(s, 0)[0]
+                l = top + conf - threshold if targeted else threshold + conf - top
             else:
-                l = 0.0 * torch.sum(s)
+                l = imp_zero
         rows.append(l)
     loss = torch.stack(rows).float()
-    if clip_max:
+    if clip_max:  # the binary max of :100: 0.5 to each side at loss == 0
         loss = torch.max(torch.tensor(0, dtype=torch.float), loss)
     return loss
 

@@ -28,9 +28,9 @@ class EOT:
         decisions = [[] for _ in range(n_audios)]
         base = getattr(self.model, 'base_model', self.model)
         keyed = hasattr(base, 'row_keys')  # the engine keys its noise by (utterance, repeat), not by the row of the call
+        y_rep = self._labels(y_batch, EOT_batch_size)
         for EOT_index in range(EOT_num_batches):
             x_rep = x_batch.repeat(EOT_batch_size, 1, 1)
-            y_rep = y_batch.repeat(EOT_batch_size)
             if keyed:
                 base._rep_rows = n_audios if EOT_batch_size > 1 else 0
             try:
@@ -52,5 +52,15 @@ class EOT:
             for ii in range(n_audios):
                 decisions[ii] += list(dec[:, ii])
         return scores, loss, grad, decisions
+
+    _y_rep = None  # (labels, their version, repeats, the repeated tensor)
+
+    def _labels(self, y_batch, reps):
+        """y_batch.repeat(reps), the SAME tensor while y_batch is unchanged: the model checks the labels it is given
+        once per tensor (EngineOps.check_labels), not at every step."""
+        c = self._y_rep
+        if c is None or c[0] is not y_batch or c[1] != y_batch._version or c[2] != reps:
+            c = self._y_rep = (y_batch, y_batch._version, reps, y_batch.repeat(reps))
+        return c[3]
 
     __call__ = forward

@@ -121,12 +121,38 @@ class ScoreVJP(_Loss):
         return (self.coef.to(scores.device) * scores).sum(1)
 
 
+def check_labels(label, S, loss_spec):
+    """Refuse, on the host, labels the loss stage cannot take, naming the first offending row: ValueError.  The device
+    code indexes the scores with the label unchecked (loss_device.h), so a label >= S would read and write another
+    utterance's row, or past the end of the buffer.  The reference raises too (an index error in the one-hot or in
+    F.cross_entropy; attack/utils.py:51 asserts SV labels).  CSI / OSI: -1 (imposter) or 0 .. S-1; SV: 0 or -1, and
+    exactly one enrolled speaker.  ScoreVJP ignores labels.  One copy to the host when `label` lives on the device."""
+    if loss_spec.loss_id == N.SG_LOSS_LINEAR:
+        return
+    y = np.asarray(label.detach().to('cpu', torch.int64) if torch.is_tensor(label) else label, np.int64).reshape(-1)
+    if loss_spec.task == 'SV':
+        if S != 1:
+            raise ValueError('the SV task scores exactly one enrolled speaker; the model has %d' % S)
+        bad = (y != 0) & (y != -1)
+        allowed = '0 or -1 (SV)'
+    else:
+        bad = (y < -1) | (y >= S)
+        allowed = '-1 .. %d (%s, %d classes)' % (S - 1, loss_spec.task, S)
+    if bad.any():
+        r = int(np.argmax(bad))
+        raise ValueError('label %d of row %d is outside %s' % (int(y[r]), r, allowed))
+
+
 def loss_dscores(model, scores, label, loss_spec):
     """(decisions, loss, d loss / d scores) of `loss_spec` on given scores (B, S): the loss stage of the tail kernels
     alone (sg_loss_eval), for scores that no single model pass produced."""
     base = getattr(model, 'base_model', model)
-    scores = scores.to(torch.float32).contiguous()
     B, S = scores.shape
+    if hasattr(base, 'check_labels'):
+        base.check_labels(label, loss_spec, S)
+    else:
+        check_labels(label, S, loss_spec)
+    scores = scores.to(torch.float32).contiguous()
     label = label.to(scores.device, torch.int64).contiguous()
     dec = torch.empty(B, device=scores.device, dtype=torch.int64)
     loss = torch.empty(B, device=scores.device, dtype=torch.float32)

@@ -90,10 +90,15 @@ __device__ __forceinline__ float loss_and_dscores_given(const float* sc, float* 
             else { loss = sc[0] + ls.confidence - ls.threshold; dsc[0] = 1.f; }
         } else if (yy >= 0) {
             const float real = sc[yy];
+            // attack/utils.py:72: the max of the row with the label's own entry replaced by -10000, in index order (the
+            // first maximum wins); the label's entry carries no gradient, so jo = -1 when it wins.  A score equal to the
+            // sentinel BEFORE the label therefore takes the gradient, one after it does not.
             int jo = -1;
-            float other = -10000.f;  // attack/utils.py:72
-            for (int s = 0; s < S; ++s)
-                if (s != yy && sc[s] > other) { other = sc[s]; jo = s; }
+            float other = -INFINITY;
+            for (int s = 0; s < S; ++s) {
+                const float v = s == yy ? -10000.f : sc[s];
+                if (v > other) { other = v; jo = s == yy ? -1 : s; }
+            }
             if (ls.targeted) {
                 if (ls.task == SG_TASK_CSI) {
                     loss = other + ls.confidence - real;

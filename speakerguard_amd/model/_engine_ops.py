@@ -66,6 +66,24 @@ class EngineOps:
         self._def_draw += 1
         return key
 
+    _labels_ok = None  # (label tensor, its version, S, task, loss id) of the last labels check_labels accepted
+
+    def check_labels(self, y, loss_spec, S=None):
+        """attack.utils.check_labels before a native call that takes labels, against this model's class count.  The
+        tensor last accepted is remembered (a reference to it, and its in-place version counter), so that a loop calling
+        the model with the same labels at every step -- CW2, the EOT wrapper -- pays one check, not one device round trip
+        per step."""
+        from ..attack.utils import check_labels
+        if loss_spec.loss_id == N.SG_LOSS_LINEAR:
+            return  # (no labels read; leaves the memo to the loss calls around it, defended_model's 'average' order)
+        S = self.num_spks if S is None else int(S)
+        key = (S, loss_spec.task, loss_spec.loss_id)
+        ok = self._labels_ok
+        if torch.is_tensor(y) and ok is not None and ok[0] is y and ok[1] == y._version and ok[2:] == key:
+            return
+        check_labels(y, S, loss_spec)
+        self._labels_ok = (y, y._version) + key if torch.is_tensor(y) else None
+
     def _stream(self):
         return N.current_stream_ptr(self.device)
 

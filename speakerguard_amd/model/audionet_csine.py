@@ -160,6 +160,7 @@ class audionet_csine(EngineOps):
     # ---- engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True):
         x, B, TF = self._prep(x, flag)
+        self.check_labels(y, loss_spec)
         y = y.to(self.device, torch.int64).contiguous()
         dec = torch.empty(B, device=self.device, dtype=torch.int64)
         scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
@@ -183,6 +184,7 @@ class audionet_csine(EngineOps):
         device-resident loop: log-mel -> FeCo -> CNN forward, hand-chained backward, EOT repeats over the defense's
         random initial frames (``feco.init == 'random'``) summed on the device.  `feco`: a FeCoDefense."""
         x, B, T = self._prep(x, 0)
+        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
         x_adv = x.clone()
         y = y.to(self.device, torch.int64).contiguous()
         lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()
@@ -217,6 +219,7 @@ class audionet_csine(EngineOps):
     def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
                 trace=False):
         x, B, T = self._prep(x, 0)
+        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
         x_adv = x.clone()
         y = y.to(self.device, torch.int64).contiguous()
         lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()

@@ -339,6 +339,7 @@ class xv_plda(EngineOps):
         Returns (decisions, scores, loss, grad) with grad shaped like x (None if want_grad=False).
         """
         x, B, TF = self._prep(x, flag)
+        self.check_labels(y, loss_spec)
         y = y.to(self.device, torch.int64).contiguous()
         dec = torch.empty(B, device=self.device, dtype=torch.int64)
         scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
@@ -358,6 +359,7 @@ class xv_plda(EngineOps):
         dither (eot_size fresh-noise passes per gradient step, gradients summed on the device; the traces record each
         step's loss averaged and decision voted over its repeats, like the reference's verbose print)."""
         x, B, T = self._prep(x, 0)
+        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
         x_adv = x.clone()
         y = y.to(self.device, torch.int64).contiguous()
         lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()

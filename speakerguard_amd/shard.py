@@ -306,13 +306,25 @@ class QueryShardedModel:
             return 1, 0
         return dist.get_world_size(self.group), dist.get_rank(self.group)
 
+    _y_slice = None  # (labels, their version, lo, hi, labels[lo:hi])
+
+    def _labels_slice(self, y, lo, hi):
+        """y[lo:hi], the SAME tensor while y is unchanged: the model checks the labels it is given once per tensor
+        (EngineOps.check_labels), not at every step (a view shares y's in-place version counter)."""
+        if not torch.is_tensor(y):
+            return y[lo:hi]
+        c = self._y_slice
+        if c is None or c[0] is not y or c[1] != y._version or c[2:4] != (lo, hi):
+            c = self._y_slice = (y, y._version, lo, hi, y[lo:hi])
+        return c[4]
+
     def _call_rows(self, x, y, loss_spec, lo, hi, want_grad, kw):
         base = self.base_model
         had = hasattr(base, '_row_base')
         if had:
             base._row_base = lo
         try:
-            return self.model.loss_grad(x[lo:hi], y[lo:hi], loss_spec, want_grad=want_grad, **kw)
+            return self.model.loss_grad(x[lo:hi], self._labels_slice(y, lo, hi), loss_spec, want_grad=want_grad, **kw)
         finally:
             if had:
                 base._row_base = 0

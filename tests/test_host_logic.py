@@ -135,3 +135,43 @@ def test_model_file_parsers_roundtrip(tmp_path, xv_weights):
     ids, zm, zs, enroll = m.parse_enroll_model_file(paths["model_file"])
     assert ids[0] == "spk00" and len(ids) == 10
     np.testing.assert_allclose(enroll, xv_weights["enroll"])
+
+
+def test_label_check_runs_once_per_label_tensor(monkeypatch):
+    """EngineOps.check_labels remembers the label tensor it accepted: a loop that passes the same tensor (CW2, the EOT
+    wrapper's cached repeat, the sharded proxy's cached slice) pays one check and one copy to the host, an in-place change
+    is checked again, and a ScoreVJP call in between (no labels) leaves the memo alone."""
+    import types
+    from speakerguard_amd import _native as N
+    from speakerguard_amd.adaptive_attack.EOT import EOT
+    from speakerguard_amd.attack import utils as U
+    from speakerguard_amd.model._engine_ops import EngineOps
+    from speakerguard_amd.shard import QueryShardedModel
+    calls = []
+    real = U.check_labels
+    monkeypatch.setattr(U, "check_labels", lambda y, S, spec: (calls.append(1), real(y, S, spec)))
+
+    class Model(EngineOps):
+        num_spks = 10
+
+    m, ce = Model(), U.SEC4SR_CrossEntropy()
+    vjp = types.SimpleNamespace(loss_id=N.SG_LOSS_LINEAR, task="CSI")
+    y = torch.tensor([0, 9, -1, 3])
+    for _ in range(3):
+        m.check_labels(y, ce)
+        m.check_labels(y, vjp)
+    assert len(calls) == 1
+    y[1] = 10
+    with pytest.raises(ValueError, match="label 10 of row 1 "):
+        m.check_labels(y, ce)
+    y[1] = 9
+    m.check_labels(y, ce)
+    m.check_labels(y.clone(), ce)  # another tensor: checked
+    assert len(calls) == 4
+    eot = EOT(m, ce, 2, 2)
+    assert eot._labels(y, 2) is eot._labels(y, 2) and eot._labels(y, 2).tolist() == y.repeat(2).tolist()
+    ns = types.SimpleNamespace(_y_slice=None)
+    a = QueryShardedModel._labels_slice(ns, y, 1, 3)
+    assert QueryShardedModel._labels_slice(ns, y, 1, 3) is a and a.tolist() == [9, -1]
+    y[2] = 4  # in place: a view shares the version counter, so the model sees the change
+    assert QueryShardedModel._labels_slice(ns, y, 1, 3) is not a

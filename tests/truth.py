@@ -75,32 +75,40 @@ class Loss:
     def unclipped(self, s, y):
         if self.kind == "ce":
             return F.cross_entropy(s, y, reduction="none")
-        conf, thr = self.confidence, self.threshold
+        # the reference's rules at ties (attack/utils.py:41-102, tests/test_oracle_losses.py): the confidence is a tensor of
+        # the scores' dtype (the threshold, a Python float, rounds to it in the additions); torch.max(t, dim) sends the
+        # gradient to the first maximal index; `other` is the max over the row with the label's entry at the -10000 sentinel
+        conf, thr = torch.tensor(self.confidence, dtype=s.dtype), self.threshold
+        imp_zero = 0.0 * s[y == -1].sum()  # CSI imposters: one 0 * sum over all of them, the batch's sign of zero
         rows = []
         for i in range(s.shape[0]):
             si, yi = s[i], int(y[i])
             if self.task == "SV":
                 rows.append(thr + conf - si[0] if (yi == 0) == self.targeted else si[0] + conf - thr)
                 continue
+            top = si.max(0)[0]
             if yi == -1:
                 if self.task == "OSI":
-                    rows.append(si.max() + conf - thr if self.targeted else thr + conf - si.max())
+                    rows.append(top + conf - thr if self.targeted else thr + conf - top)
                 else:
-                    rows.append(0.0 * si.sum())
+                    rows.append(imp_zero)
                 continue
+            onehot = torch.zeros_like(si)
+            onehot[yi] = 1
             real = si[yi]
-            other = torch.cat((si[:yi], si[yi + 1:])).max()
+            other = ((1 - onehot) * si - onehot * 10000).max(0)[0]
             if self.targeted:
                 rows.append(other + conf - real if self.task == "CSI" else torch.clamp(other, min=thr) + conf - real)
             elif self.task == "CSI":
                 rows.append(real + conf - other)
             else:
-                rows.append(torch.minimum(si.max() + conf - thr, torch.clamp(real, min=thr) + conf - other))
+                rows.append(torch.minimum(top + conf - thr, torch.clamp(real, min=thr) + conf - other))
         return torch.stack(rows)
 
     def __call__(self, s, y):
         l = self.unclipped(s, y)
-        return torch.clamp(l, min=0) if self.clip_max else l
+        # binary max as the reference's clip (:100): 0.5 to each side at l == 0, where clamp(min=0) passes all of it
+        return torch.max(torch.zeros((), dtype=l.dtype), l) if self.clip_max else l
 
 
 # ---------------------------------------------------------------------------------------------------------------- evaluation
