@@ -1,7 +1,7 @@
 """Headline benchmark: PGD attack steps/s on the x-vector/PLDA system (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--scaling weak|strong] [--batch-per-gpu B]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-shard-points] [--no-other-configs]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload: PGD, L-inf eps 0.002, step 0.0004, cross-entropy, untargeted, EOT 1/1, CSI-E, 3 s @ 16 kHz synthetic
@@ -19,7 +19,13 @@ Every timed attack is the PRODUCT's call: ``speakerguard_amd.attack.PGD(model, .
 (reference attack/PGD.py:40-79: input checks, epsilon box, one chunk -> the fused device loop, flags to the host), and
 for N > 1 ``speakerguard_amd.shard.ShardedAttack`` around it -- not a bench-private partition.
 
-N > 1, two partitions of the work, both measured in the same run:
+A plain run does only what the headline needs: it sets up, warms up, times the R attacks, writes the outputs if
+``--dump-outputs`` is given and prints the line (``value``, ``ms_per_step``, the timed samples).  Everything else the
+benchmark measures takes runs of its own and comes with ``--full``: the other partition (N > 1), the shard points
+(N = 1), the in-loop ``roofline``, ``other_configs`` and ``cpu_baseline``.  A ``--full`` run times the headline first,
+exactly as a plain run does.
+
+N > 1, two partitions of the work, both measured in the same ``--full`` run:
   * ``--scaling weak`` (default, the line's `value`): every rank attacks its own batch of 64; no data-path collective,
     one RCCL all-gather of the per-utterance success flags at the end of the attack, inside the timed region;
   * ``strong`` (the line's ``value_metric_partition`` / ``strong_scaling``; `value` with ``--scaling strong``): the
@@ -28,8 +34,9 @@ N > 1, two partitions of the work, both measured in the same run:
     sharded B/G per GPU"), flags all-gathered by the wrapper.  On one GPU the shard sizes 32 / 16 / 8 are timed as well
     (``shard_points``): what a rank of a 2 / 4 / 8-GPU strong-scaling run does.
 
-``other_configs``: the other BASELINE.json configurations (configs[0], [2], [3], [4]) on this GPU, a few seconds in
-all (tools/config_bench.py); ``--no-other-configs`` skips them.
+``other_configs`` (``--full``): the other BASELINE.json configurations (configs[0], [2], [3], [4]) on this GPU, a few
+seconds in all (tools/config_bench.py); ``--no-other-configs`` skips them, as ``--no-cpu-baseline`` and
+``--no-shard-points`` skip the other two one-GPU extras.
 
 ``--dump-outputs DIR``: after the timed attacks, what the LAST one returned to its caller is written as float32 .npy
 files -- ``adversarial.npy`` (the adversarial audio, (B, 1, 48000)) and ``success.npy`` (the per-utterance success flags
@@ -224,6 +231,38 @@ def stage_roofline(model, run_attack, B, steps):
             "stages": stages, "traced_records": len(recs)}
 
 
+def roofline_entry(model, roof, B, ms_per_step):
+    """The line's `roofline` (--full): stage_roofline's in-loop figures, the isolated tdnn3 forward launch (a run of its own)
+    and the committed PMC traffic of that launch."""
+    ms_iso, flops_iso, _ = model.time_layer(3, B, T_SAMPLES, iters=20)
+    traffic, traffic_src = None, None
+    for name in ("r06_pmc_tdnn3.json", "r05_pmc_tdnn3.json", "r04_pmc_tdnn3.json", "r03_pmc_tdnn3.json", "r02_pmc_tdnn3.json", "r01_pmc_tdnn3.json"):  # latest committed passes of this kernel
+        pmc = os.path.join(ROOT, "profiles", name)
+        if os.path.exists(pmc):
+            with open(pmc) as f:
+                traffic = json.load(f).get("traffic_bytes_per_launch")
+            traffic_src = "profiles/%s: one tdnn3 forward launch at batch 64 (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; fabric " \
+                          "bytes incl. Infinity-Cache hits; cannot be collected from inside this process)" % name
+            break
+    return {
+        "bound": "mfma", "achieved": roof["achieved"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+        "frac": roof["achieved"] / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+        "kernel": "conv_gemm_streamk_kernel (tdnn2-5 forward, tdnn5-2 data gradient: 8 launches per step, 98 % of a step's FLOPs)",
+        "how": "algorithmic FLOPs of the 8 launches / sum of their average in-loop durations; HIP-event pairs on the launch stream "
+               "around every launch of one traced attack of the timed workload (sg_trace_begin / sg_trace_end); compare "
+               "avg_us_*_instantiation with the rocprofv3 --kernel-trace --stats averages of the same command (profiles/)",
+        "us_per_step_in_kernel": roof["us_per_step_in_kernel"], "flop_per_step": roof["flop_per_step"],
+        "avg_us_forward_instantiation": roof["avg_us_forward_instantiation"],
+        "avg_us_dgrad_instantiation": roof["avg_us_dgrad_instantiation"],
+        "stages": roof["stages"],
+        "isolated_tdnn3_forward": {"ms_per_launch": ms_iso, "frac": flops_iso / (ms_iso * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                                   "note": "the best layer launched back to back with a warm L2 (sg_xv_time_layer): an upper bound, not `frac`"},
+        # whole step against the same peak: algorithmic TDNN FLOPs of the job / wall time (front-end, pooling, tail and the
+        # final forward-only pass of the attack included in the time, not in the FLOPs)
+        "end_to_end_frac": B * FLOP_PER_UTT_STEP / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,9 +271,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="timed attacks of --steps steps; the line reports the median")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="utterances per GPU (default: 64 weak, 64 / N strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shard-points", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the other partition (N > 1) or the shard sizes (N = 1), the "
+                         "in-loop roofline, other_configs and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-shard-points", action="store_true", help="--full without shard_points")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without other_configs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed attack returned (adversarial audio, success flags) as DIR/<name>.npy")
     # test hooks (tests/test_gpu_multiproc.py runs the N > 1 code path as two ranks on the ONE GPU of the test box)
@@ -306,21 +348,27 @@ def main():
         return attack
 
     labels = np.arange(GLOBAL_BATCH) % 10
-    # weak: every rank its own 64 utterances; strong: ONE batch of 64 (seed 1234), resident on every rank, cut by ShardedAttack
+    # weak: every rank its own 64 utterances; strong: ONE batch of 64 (seed 1234), resident on every rank, cut by ShardedAttack.
+    # A partition is made resident only when something times it: the headline's always, the other one with --full and N > 1.
     weak_b = args.batch_per_gpu if (args.batch_per_gpu > 0 and args.scaling == "weak") else GLOBAL_BATCH
-    weak = make_attack(synth.make_waveforms(weak_b, T_SAMPLES, seed=1234 + rank), np.arange(weak_b) % 10)
-    global_x = synth.make_waveforms(GLOBAL_BATCH, T_SAMPLES, seed=1234)
     if args.batch_per_gpu > 0 and args.scaling == "strong":
         strong_b = args.batch_per_gpu  # one GPU standing in for a rank of a 64 / B-GPU run (no exchange)
-        strong = make_attack(global_x[:strong_b], labels[:strong_b])
     else:
         lo, hi = ShardedAttack(pgd(1)).bounds(GLOBAL_BATCH)[rank] if world > 1 else (0, GLOBAL_BATCH)
         strong_b = hi - lo
         if strong_b < 1:
             sys.exit("bench.py: more ranks (%d) than utterances in the metric's batch" % world)
-        strong = make_attack(global_x, labels, sharded=world > 1)
+    global_x = synth.make_waveforms(GLOBAL_BATCH, T_SAMPLES, seed=1234) if (args.scaling == "strong" or args.full) else None
 
-    primary, primary_b = (weak, weak_b) if args.scaling == "weak" else (strong, strong_b)
+    def make_weak():
+        return make_attack(synth.make_waveforms(weak_b, T_SAMPLES, seed=1234 + rank), np.arange(weak_b) % 10)
+
+    def make_strong():
+        if args.batch_per_gpu > 0 and args.scaling == "strong":
+            return make_attack(global_x[:strong_b], labels[:strong_b])
+        return make_attack(global_x, labels, sharded=world > 1)
+
+    primary, primary_b = (make_weak(), weak_b) if args.scaling == "weak" else (make_strong(), strong_b)
     (out, flags), samples = timed_reps(primary, args.steps, args.warmup, args.reps, dist, sync, dev)
     if args.dump_outputs:
         dumps = {"adversarial" if world == 1 else "adversarial_rank%d" % rank: out}
@@ -334,10 +382,10 @@ def main():
     jobs_per_step = world * primary_b / GLOBAL_BATCH if args.scaling == "weak" else strong_jobs
     steps_per_s = jobs_per_step * args.steps / dt
 
-    # ---- the other partition, same run (N > 1), or the per-rank shard sizes of 2 / 4 / 8 GPUs (N = 1)
+    # ---- --full: the other partition, same run (N > 1), or the per-rank shard sizes of 2 / 4 / 8 GPUs (N = 1)
     other = None
-    if world > 1:
-        sec, sec_b = (strong, strong_b) if args.scaling == "weak" else (weak, weak_b)
+    if args.full and world > 1:
+        sec, sec_b = (make_strong(), strong_b) if args.scaling == "weak" else (make_weak(), weak_b)
         (_, sflags), ssamples = timed_reps(sec, args.steps, min(args.warmup, 2), 3, dist, sync, dev)
         s = summarise(ssamples, args.steps)
         mult = strong_jobs if args.scaling == "weak" else world * sec_b / GLOBAL_BATCH
@@ -347,7 +395,7 @@ def main():
                           "utterances (attack/PGD.py:62-73), flags all-gathered inside the timed region" if args.scaling == "weak"
                           else "every rank its own batch")
     shard_points = None
-    if world == 1 and not args.no_shard_points:
+    if args.full and world == 1 and not args.no_shard_points:
         shard_points = []
         for b in (32, 16, 8):
             atk = make_attack(global_x[:b], labels[:b])
@@ -361,38 +409,11 @@ def main():
                                      end_to_end_frac=b * FLOP_PER_UTT_STEP / (s["ms_per_step"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS))
 
     # ---- roofline of the dominant kernel (conv_gemm_streamk_kernel: 8 of the 10 contractions of a step), in the loop
-    roof = stage_roofline(model, lambda k: primary(k, gather=False), primary_b, args.steps) if rank == 0 else None
+    roof = stage_roofline(model, lambda k: primary(k, gather=False), primary_b, args.steps) if (args.full and rank == 0) else None
     if dist is not None:
         dist.barrier()
     line = None
     if rank == 0:
-        ms_iso, flops_iso, _ = model.time_layer(3, primary_b, T_SAMPLES, iters=20)
-        traffic, traffic_src = None, None
-        for name in ("r06_pmc_tdnn3.json", "r05_pmc_tdnn3.json", "r04_pmc_tdnn3.json", "r03_pmc_tdnn3.json", "r02_pmc_tdnn3.json", "r01_pmc_tdnn3.json"):  # latest committed passes of this kernel
-            pmc = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(pmc):
-                with open(pmc) as f:
-                    traffic = json.load(f).get("traffic_bytes_per_launch")
-                traffic_src = "profiles/%s: one tdnn3 forward launch at batch 64 (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; fabric " \
-                              "bytes incl. Infinity-Cache hits; cannot be collected from inside this process)" % name
-                break
-        roofline = {
-            "bound": "mfma", "achieved": roof["achieved"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-            "frac": roof["achieved"] / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-            "kernel": "conv_gemm_streamk_kernel (tdnn2-5 forward, tdnn5-2 data gradient: 8 launches per step, 98 % of a step's FLOPs)",
-            "how": "algorithmic FLOPs of the 8 launches / sum of their average in-loop durations; HIP-event pairs on the launch stream "
-                   "around every launch of one traced attack of the timed workload (sg_trace_begin / sg_trace_end); compare "
-                   "avg_us_*_instantiation with the rocprofv3 --kernel-trace --stats averages of the same command (profiles/)",
-            "us_per_step_in_kernel": roof["us_per_step_in_kernel"], "flop_per_step": roof["flop_per_step"],
-            "avg_us_forward_instantiation": roof["avg_us_forward_instantiation"],
-            "avg_us_dgrad_instantiation": roof["avg_us_dgrad_instantiation"],
-            "stages": roof["stages"],
-            "isolated_tdnn3_forward": {"ms_per_launch": ms_iso, "frac": flops_iso / (ms_iso * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                                       "note": "the best layer launched back to back with a warm L2 (sg_xv_time_layer): an upper bound, not `frac`"},
-            # whole step against the same peak: algorithmic TDNN FLOPs of the job / wall time (front-end, pooling, tail and the
-            # final forward-only pass of the attack included in the time, not in the FLOPs)
-            "end_to_end_frac": primary_b * FLOP_PER_UTT_STEP / (prim["ms_per_step"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
-        }
         line = {
             "metric": "PGD attack steps/sec (xv_plda, 3s@16kHz, batch 64)",
             "value": steps_per_s,
@@ -418,21 +439,23 @@ def main():
             "utt_steps_per_s": world * primary_b * args.steps / dt,
             "model_tflops_per_gpu": primary_b * args.steps / dt * FLOP_PER_UTT_STEP / 1e12,
             "success_count": int(flags.sum().item()),
-            "roofline": roofline,
         }
+        if roof is not None:
+            line["roofline"] = roofline_entry(model, roof, primary_b, prim["ms_per_step"])
         # the metric's own partition (GPU-N = the batch of 64 cut B/N per GPU), next to `value`
         if args.scaling == "strong" or world == 1:
             line["value_metric_partition"] = steps_per_s
         elif other is not None:
             line["value_metric_partition"] = other["value"]
-        line["value_metric_partition_note"] = ("steps/s of ONE batch of 64 cut over the %d GPUs by the product's ShardedAttack (strong "
-                                               "scaling); `value` is %s" % (world, "the same number" if (args.scaling == "strong" or world == 1)
-                                                                            else "weak scaling: every rank its own batch of 64"))
+        if "value_metric_partition" in line:  # (N > 1 weak: the strong partition is timed by --full only)
+            line["value_metric_partition_note"] = ("steps/s of ONE batch of 64 cut over the %d GPUs by the product's ShardedAttack "
+                                                   "(strong scaling); `value` is %s" % (world, "the same number" if (args.scaling == "strong" or world == 1)
+                                                                                        else "weak scaling: every rank its own batch of 64"))
         if other is not None:
             line["strong_scaling" if args.scaling == "weak" else "weak_scaling"] = other
         if shard_points is not None:
             line["shard_points"] = shard_points
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             import contextlib
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import config_bench
@@ -440,7 +463,7 @@ def main():
                 t0 = time.perf_counter()
                 line["other_configs"] = config_bench.measure(dev, reps=3, xv_weights=weights)
                 line["other_configs"]["seconds_spent"] = time.perf_counter() - t0
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(weights, gpu_model=model)
             line["gpu_vs_cpu"] = steps_per_s / line["cpu_baseline"]["value"]
         order = ["metric", "value", "value_metric_partition"]

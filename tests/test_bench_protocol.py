@@ -1,12 +1,13 @@
 """bench.py's N > 1 protocol (warm-up, barrier + synchronise on both sides of exactly K steps, MAX over ranks, rank-ordered
 all-gather of the success flags) on a world-size-2 gloo group on the CPU; the GPU ranks run the same two functions over
-RCCL.  Also: the launcher contract (--gpus must match the world size)."""
+RCCL.  Also: the launcher contract (--gpus must match the world size), and what a plain run (no --full) prints."""
 import os
 import socket
 import subprocess
 import sys
 import time
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -120,3 +121,40 @@ def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_full_is_an_option():
+    """What a plain run leaves out comes with --full (and the --no-* switches that trim a --full run)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0
+    for opt in ("--full", "--no-cpu-baseline", "--no-shard-points", "--no-other-configs"):
+        assert opt in r.stdout, opt
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY_KEYS = ("roofline", "shard_points", "other_configs", "cpu_baseline", "gpu_vs_cpu", "strong_scaling")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1` without --full: the timed attacks, their outputs, one line with the headline and none of the figures
+    that take runs of their own.  Run as the benchmark is run: no SG_* variable set."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SG_")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--reps", "2", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert all(k in line for k in HEADLINE_KEYS), sorted(line)
+    assert not set(FULL_ONLY_KEYS) & set(line), sorted(line)
+    assert line["unit"] == "steps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["timed_attacks"] == 2
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]   # one batch-64 step per time step
+    assert line["value_metric_partition"] == line["value"]
+    adv, succ = np.load(out / "adversarial.npy"), np.load(out / "success.npy")
+    assert adv.shape == (64, 1, 48000) and adv.dtype == np.float32
+    assert succ.shape == (64,) and int(succ.sum()) == line["success_count"]

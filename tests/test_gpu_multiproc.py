@@ -126,7 +126,7 @@ def test_rccl_backend_runs_the_exchange_on_device_tensors(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_bench_n2_code_path_on_one_gpu(tmp_path):
-    """bench.py's N > 1 path end to end -- the launcher contract, ShardedAttack(PGD(batch_size=64)) as the strong partition,
+    """bench.py --full's N > 1 path end to end -- the launcher contract, ShardedAttack(PGD(batch_size=64)) as the strong partition,
     the weak partition, MAX-over-ranks timing, the one JSON line from rank 0 -- as two ranks over gloo that share the test
     box's one GPU (hidden --backend / --one-gpu hooks; RCCL needs a GPU per rank: the driver's SCALE run).  Two steps, and
     SG_STREAMK=0: two processes must not both run chip-wide persistent kernels with intra-launch hand-offs on one GPU."""
@@ -142,7 +142,7 @@ def test_bench_n2_code_path_on_one_gpu(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reps", "2",
-           "--backend", "gloo", "--one-gpu"]
+           "--full", "--backend", "gloo", "--one-gpu"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -153,3 +153,31 @@ def test_bench_n2_code_path_on_one_gpu(tmp_path):
     assert ss["scaling"] == "strong" and ss["batch_per_gpu"] == 32 and "ShardedAttack" in ss["note"]
     assert line["value_metric_partition"] == ss["value"] and 0 <= ss["success_count"] <= 64
     assert line["success_count"] <= 128 and line["roofline"]["frac"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_n2_plain_run_on_one_gpu():
+    """A plain `bench.py --gpus 2` (no --full) on the same two-rank setup: the weak partition alone, timed MAX over ranks,
+    one JSON line from rank 0 without the figures that take runs of their own."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, SG_TUNE="1", SG_STREAMK="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reps", "2",
+           "--backend", "gloo", "--one-gpu"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["global_batch"] == 128
+    assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]  # two batches of 64 per time step
+    assert line["timed_attacks"] == 2 and line["success_count"] <= 128
+    assert not {"strong_scaling", "value_metric_partition", "roofline"} & set(line)

@@ -6,7 +6,7 @@
                 batch of 512: ms per step; the undefended AudioNet loop at 64 and 512 next to it
     configs[4]  FAKEBOB / NES on xv_plda OSI, samples_per_draw 50: queries/s
 
-``measure()`` is what ``bench.py`` puts into its JSON line as ``other_configs`` (every entry: workload string, median of
+``measure()`` is what ``bench.py --full`` puts into its JSON line as ``other_configs`` (every entry: workload string, median of
 ``reps`` timed runs after one warm-up, and the fraction of the f32-MFMA peak its algorithmic FLOPs amount to);
 ``python tools/config_bench.py`` prints the same plus the host-chained / deterministic-defense variants of configs[3].
 """

@@ -3,7 +3,7 @@
 out=gpurun_out/r05b
 rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/bench_line.json 2> $out/bench_err.log
+python bench.py --full > $out/bench_line.json 2> $out/bench_err.log
 for B in 64 512; do
     rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_an$B -o an -- python3 tools/audionet_profile.py $B > $out/an_profile_b$B.log 2>&1
 done

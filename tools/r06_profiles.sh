@@ -3,8 +3,8 @@
 out=gpurun_out/r06
 rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/bench_line.json 2> $out/bench_err.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -o bench -- python3 bench.py --no-cpu-baseline --no-shard-points --no-other-configs > $out/bench_line_profiled.json 2> $out/prof_bench.log
+python bench.py --full > $out/bench_line.json 2> $out/bench_err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -o bench -- python3 bench.py --full --no-cpu-baseline --no-shard-points --no-other-configs > $out/bench_line_profiled.json 2> $out/prof_bench.log
 for B in 32 16 8; do
     rocprofv3 --kernel-trace --output-format csv -d $out/prof_b$B -o step -- python3 tools/step_profile.py $B 20 > $out/step_b$B.log 2>&1
 done

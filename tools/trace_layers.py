@@ -1,4 +1,4 @@
-"""Per-LAYER kernel times from a rocprofv3 kernel trace of ``bench.py``.
+"""Per-LAYER kernel times from a rocprofv3 kernel trace of ``bench.py --full``.
 
 ``rocprofv3 --kernel-trace --stats`` averages ``conv_gemm_streamk_kernel<1, 2>`` over the four forward layers that
 share that instantiation (and ``<2, 2>`` over the four data-gradient layers), so its per-kernel average cannot be
