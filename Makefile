@@ -46,9 +46,9 @@ $(ASAN_DIR)/hip_host_double.o: tests/native/hip_host_double.cpp
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
-$(ASAN_DIR)/abi_asan_driver.o: tests/native/abi_asan_driver.cpp include/speakerguard_hip.h
+$(ASAN_DIR)/abi_asan_driver.o: tests/native/abi_asan_driver.cpp $(CSRC)/sg_internal.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
-	$(HIPCC) $(ASAN_FLAGS) -x c++ -c $< -o $@
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
 # (the host objects reference their embedded-code-object symbols even when none is embedded: define them empty)
 $(ASAN_EXE): $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/abi_asan_driver.o

@@ -23,11 +23,13 @@
 //   * conv_gemm_streamk_kernel: persistent blocks with equal (tile, K-chunk) ranges and a bit-exact hand-off of
 //     split tiles.
 // v_mfma_f32_32x32x2_f32 is exact fp32 (an fmaf chain), 64 cycles per instruction per SIMD.
+#include <array>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <type_traits>
+#include <utility>
 
 #include "sg_internal.h"
 
@@ -1070,9 +1072,8 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_q_kernel(ConvGemmArgs p, int
 // the full batch (the all-in-one 16-wave kind 2 keeps the K = 512 layers, whose 16-chunk tiles feel the split's longer prologue).
 // 9: 128x128 as four computing waves of 64 x 64 + four staging waves (two waves per SIMD).
 constexpr bool sk_deep(int kind) { return kind >= 5; }
-constexpr int sk_wm(int kind) { return (kind == 2 || kind == 8) ? 4 : (kind == 3 || kind == 4 || kind == 6 || kind == 7) ? 1 : 2; }  // waves along M (9: 2)
+// (sk_wm, waves along M, and sk_bm, the tile height, are in sg_internal.h: the launch plan needs them)
 constexpr int sk_wn(int kind) { return (kind == 8 || kind == 9) ? 2 : 4; }                                                                   // waves along N
-constexpr int sk_bm(int kind) { return (kind == 4 || kind == 7) ? 32 : 64 * sk_wm(kind); }
 constexpr int sk_threads(int kind) { return 64 * sk_wm(kind) * sk_wn(kind) + (sk_deep(kind) ? 256 : 0); }  // deep: + 4 staging waves
 constexpr int sk_min_waves(int kind) { return (kind == 5 || kind == 8) ? 3 : sk_deep(kind) ? 2 : sk_wm(kind) == 1 ? 1 : 4; }  // per SIMD: sets the VGPR budget
 // kinds whose computing waves take their W operands straight from the L2 (ws_compute_segment, BG): the 32- and 64-row tiles
@@ -1276,24 +1277,24 @@ __global__ __launch_bounds__(sk_threads(KIND), sk_min_waves(KIND)) void conv_gem
 #undef SG_STAMP
 }
 
+// runs f(std::integral_constant<int, EPI>) for the runtime epilogue (launch_conv_gemm has refused any other value)
+template <class F>
+static void with_epilogue(int epi, F&& f) {
+    switch (epi) {
+        case EPI_NONE: f(std::integral_constant<int, EPI_NONE>{}); break;
+        case EPI_BIAS_RELU: f(std::integral_constant<int, EPI_BIAS_RELU>{}); break;
+        case EPI_RELU_MASK: f(std::integral_constant<int, EPI_RELU_MASK>{}); break;
+    }
+}
+
 template <int BM, int BN, int WM, int WN>
 static hipError_t launch_tile(const ConvGemmArgs& a, int epi, int splits, hipStream_t s) {
     const int mtiles = (a.M + BM - 1) / BM;
     const int ntiles = a.N / BN;
     dim3 grid(mtiles * ntiles, 1, splits);
-    switch (epi) {
-        case EPI_NONE:
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, EPI_NONE>), grid, dim3(256), 0, s, a, mtiles, ntiles);
-            break;
-        case EPI_BIAS_RELU:
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, EPI_BIAS_RELU>), grid, dim3(256), 0, s, a, mtiles, ntiles);
-            break;
-        case EPI_RELU_MASK:
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, EPI_RELU_MASK>), grid, dim3(256), 0, s, a, mtiles, ntiles);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
+    with_epilogue(epi, [&](auto e) {
+        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, decltype(e)::value>), grid, dim3(256), 0, s, a, mtiles, ntiles);
+    });
     return hipGetLastError();
 }
 
@@ -1474,16 +1475,11 @@ static hipError_t launch_s16(const ConvGemmArgs& a_in, int epi, hipStream_t s) {
     a.trace = tr_dev;
     const int ntile32 = a.N / 32;
     dim3 grid(((a.M + 31) / 32) * ntile32);
-#define SG_S16(EPI) \
-    if (tr_on) hipLaunchKernelGGL((conv_gemm_s16_kernel<EPI, R, true>), grid, dim3(256), 0, s, a, ntile32); \
-    else hipLaunchKernelGGL((conv_gemm_s16_kernel<EPI, R, false>), grid, dim3(256), 0, s, a, ntile32);
-    switch (epi) {
-        case EPI_NONE: SG_S16(EPI_NONE) break;
-        case EPI_BIAS_RELU: SG_S16(EPI_BIAS_RELU) break;
-        case EPI_RELU_MASK: SG_S16(EPI_RELU_MASK) break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SG_S16
+    with_epilogue(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        if (tr_on) hipLaunchKernelGGL((conv_gemm_s16_kernel<EPI, R, true>), grid, dim3(256), 0, s, a, ntile32);
+        else hipLaunchKernelGGL((conv_gemm_s16_kernel<EPI, R, false>), grid, dim3(256), 0, s, a, ntile32);
+    });
     if (tr_on && tr_dev && hipStreamSynchronize(s) == hipSuccess) {
         unsigned long long h[4];
         if (hipMemcpy(h, tr_dev, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[3])
@@ -1494,29 +1490,15 @@ static hipError_t launch_s16(const ConvGemmArgs& a_in, int epi, hipStream_t s) {
     return hipGetLastError();
 }
 
+// quad-fed, one block per 32 MI x 128 tile (which height: conv_plan)
 template <int MI>
-static hipError_t launch_tile_q_mi(const ConvGemmArgs& a, int epi, hipStream_t s) {
+static hipError_t launch_tile_q(const ConvGemmArgs& a, int epi, hipStream_t s) {
     const int mtiles = (a.M + 32 * MI - 1) / (32 * MI), ntiles = a.N / 128;
     dim3 grid(mtiles * ntiles);
-    switch (epi) {
-        case EPI_NONE: hipLaunchKernelGGL((conv_gemm_q_kernel<EPI_NONE, MI>), grid, dim3(256), 0, s, a, mtiles, ntiles); break;
-        case EPI_BIAS_RELU: hipLaunchKernelGGL((conv_gemm_q_kernel<EPI_BIAS_RELU, MI>), grid, dim3(256), 0, s, a, mtiles, ntiles); break;
-        case EPI_RELU_MASK: hipLaunchKernelGGL((conv_gemm_q_kernel<EPI_RELU_MASK, MI>), grid, dim3(256), 0, s, a, mtiles, ntiles); break;
-        default: return hipErrorInvalidValue;
-    }
+    with_epilogue(epi, [&](auto e) {
+        hipLaunchKernelGGL((conv_gemm_q_kernel<decltype(e)::value, MI>), grid, dim3(256), 0, s, a, mtiles, ntiles);
+    });
     return hipGetLastError();
-}
-
-static hipError_t launch_tile_q(const ConvGemmArgs& a, int epi, hipStream_t s) {
-    // A nearly empty chip (batch <= 8: fewer 64-row tiles than CUs) waits for the sequential k chain of one tile;
-    // 32-row tiles halve the MFMAs per wave and chunk, so the chain -- and the launch -- takes half as long.
-    static const int small_rows = [] {
-        const char* e = sg_tune_env("SG_TILE32");  // 0 = always 64-row tiles (tuning aid)
-        return e ? atoi(e) : 1;
-    }();
-    const int cus = a.num_cus > 0 ? a.num_cus : 256;
-    if (small_rows && a.force == 0 && a.total_chunks >= 8 && ((a.M + 63) / 64) * (a.N / 128) < cus) return launch_tile_q_mi<1>(a, epi, s);
-    return launch_tile_q_mi<2>(a, epi, s);
 }
 
 // Persistent workers = resident blocks: 512 8-wave blocks (64 KB LDS, two per CU) or 256 16-wave blocks (96 KB, one
@@ -1526,8 +1508,7 @@ static hipError_t launch_tile_q(const ConvGemmArgs& a, int epi, hipStream_t s) {
 // bytes per MAC.
 
 template <int EPI, int KIND>
-static void launch_streamk_kind(const ConvGemmArgs& a, int workers, int ntiles, int tiles, int ipw, float* slabs,
-                                unsigned* flags, unsigned epoch, hipStream_t s) {
+static void launch_streamk_kind(const ConvGemmArgs& a, const ConvPlan& p, unsigned epoch, hipStream_t s) {
     constexpr int threads = sk_threads(KIND);
     constexpr size_t lds = sk_lds_bytes(KIND);
     // per device: remember for which devices the > 64 KB dynamic-LDS opt-in has been made (a process may hold one
@@ -1541,8 +1522,8 @@ static void launch_streamk_kind(const ConvGemmArgs& a, int workers, int ntiles, 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         done_mask.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((conv_gemm_streamk_kernel<EPI, KIND>), dim3(workers), dim3(threads), lds, s, a, ntiles,
-                       tiles, ipw, slabs, flags, epoch);
+    hipLaunchKernelGGL((conv_gemm_streamk_kernel<EPI, KIND>), dim3(p.workers), dim3(threads), lds, s, a, p.ntiles, p.tiles, p.ipw,
+                       a.sk_slabs, a.sk_flags, epoch);
 }
 
 // resident blocks per CU the runtime admits for a stream-K kernel (all workers must be co-resident: a waiter spins on
@@ -1562,175 +1543,71 @@ static int streamk_blocks_per_cu() {
     return n;
 }
 
-// returns hipErrorNotSupported when the shape does not qualify (caller falls back to the tile launch)
-static hipError_t launch_streamk(const ConvGemmArgs& a, int epi, float* slabs, unsigned* flags, hipStream_t s) {
-    static const int w16 = [] {
-        const char* e = sg_tune_env("SG_STREAMK_W16");  // 0 = two 8-wave 128x128 blocks per CU
-        return e ? atoi(e) : 1;
-    }();
-    int kind = !a.Wq ? 0 : ((w16 && a.force != 3) ? 2 : 1);
-    // one worker per resident slot of this device (slabs / flags are sized for 256 CUs)
-    const int cus = a.num_cus > 0 && a.num_cus < 256 ? a.num_cus : 256;
-    int bm = kind == 2 ? 256 : 128, workers = kind == 2 ? cus : 2 * cus;
-    // Medium batches (B = 32 at 3 s: 136 tiles of 256 rows for 256 CUs): fewer 256-row tiles than CUs would leave the
-    // persistent launch to the 4-wave tile kernel at ~100 TFLOP/s.  128-row tiles still give every CU one: run the
-    // 8-wave 128x128 kernel with ONE block per CU (2 waves per SIMD; the CU's MFMA rate is what a lone block needs).
-    static const int mid = [] {
-        const char* e = sg_tune_env("SG_STREAMK_MID");  // 0 = off (tuning aid)
-        return e ? atoi(e) : 1;
-    }();
-    static const int mid9 = [] {
-        const char* e = sg_tune_env("SG_STREAMK_MID9");  // 1 = 128-row tiles as four 64 x 64 computing waves (kind 9) instead of kind 5
-        return e ? atoi(e) : 0;
-    }();
-    if (mid && kind == 2 && a.force == 0 && ((a.M + 255) / 256) * (a.N / 128) < cus) {
-        // deep = 1 (default): the wave-specialised kinds 5 / 6 / 7 (ws_stage_segment / ws_compute_segment); 0: the all-in-one kinds 1 / 3 / 4
-        static const int deep = [] {
-            const char* e = sg_tune_env("SG_STREAMK_DEEP");
-            return e ? atoi(e) : 1;
-        }();
-        if (((a.M + 127) / 128) * (a.N / 128) >= cus) {
-            kind = deep ? (mid9 ? 9 : 5) : 1;
-            bm = 128;
-            workers = cus;
-        } else if (((a.M + 63) / 64) * (a.N / 128) >= cus) {
-            // small batches (B = 16): 4-wave 64x128 blocks, one per CU -- balances the 272 tiles a one-block-per-tile
-            // launch would spread as 240 x 1 + 16 x 2
-            kind = deep ? 6 : 3;
-            bm = 64;
-            workers = cus;
-        } else if (((a.M + 31) / 32) * (a.N / 128) >= cus) {
-            kind = deep ? 7 : 4;  // batch 8: 32-row tiles, half the k chain per tile, balanced over the CUs
-            bm = 32;
-            workers = cus;
-        }
-    }
-    // the full batch (>= 256 tiles of 256 rows): kind 8, the 256-row tile with the roles split between waves (round 3)
-    static const int ws256 = [] {
-        const char* e = sg_tune_env("SG_STREAMK_WS");  // 0 = the all-in-one 16-wave kernel (kind 2)
-        return e ? atoi(e) : 1;
-    }();
-    // measured per layer at 64 utterances (profiles/r03_layers.txt): tdnn2 / tdnn3 (80 / 112 chunks per tile) gain 1-3 % from
-    // the split, tdnn4 / tdnn5 (16 / 48 chunks) lose 4-8 %
-    static const int ws256_min_chunks = [] {
-        const char* e = sg_tune_env("SG_STREAMK_WS_MINCHUNKS");
-        return e ? atoi(e) : 64;
-    }();
+// The stream-K kinds, generated from the templates: per kind the launch per epilogue and the residency query.  A kind
+// outside the table is an error of the plan, never kind 0.
+struct StreamKKind {
+    void (*launch[3])(const ConvGemmArgs&, const ConvPlan&, unsigned epoch, hipStream_t);
+    int (*blocks_per_cu)();
+};
+template <int... KIND>
+static constexpr std::array<StreamKKind, sizeof...(KIND)> streamk_kinds(std::integer_sequence<int, KIND...>) {
+    return {{{{launch_streamk_kind<EPI_NONE, KIND>, launch_streamk_kind<EPI_BIAS_RELU, KIND>, launch_streamk_kind<EPI_RELU_MASK, KIND>},
+              streamk_blocks_per_cu<KIND>}...}};
+}
+static const StreamKKind* streamk_kind(int kind) {
+    static constexpr auto kinds = streamk_kinds(std::make_integer_sequence<int, 10>{});
+    return kind >= 0 && kind < (int)kinds.size() ? &kinds[kind] : nullptr;
+}
 
-    if (ws256 && kind == 2 && a.force == 0) {
-        if (a.total_chunks >= ws256_min_chunks) {
-            kind = 8;
-        } else {
-            // the K = 512 / 1536 layers of the full batch: 128-row tiles on the wave-specialised kind 5 (eight 64x32 computing
-            // waves + four staging waves, one block per CU) -- 3-4 % faster than the 16-wave all-in-one 256-row kernel on each
-            // of tdnn4 / tdnn5 both ways (profiles/r03_layers.txt)
-            kind = 5;
-            bm = 128;
-            workers = cus;
-        }
-    }
-    static const int env_kind = [] {
-        const char* e = sg_tune_env("SG_STREAMK_KIND");  // tuning aid: 5 .. 9 = this wave-specialised kind wherever the shape qualifies
-        return e ? atoi(e) : 0;
-    }();
-    if (env_kind >= 5 && env_kind <= 9 && a.force == 0 && a.Wq) {
-        const int kind0 = kind, bm0 = bm, workers0 = workers;
-        kind = env_kind;
-        bm = kind == 5 || kind == 9 ? 128 : kind == 6 ? 64 : kind == 7 ? 32 : 256;
-        workers = cus;
-        const long tl = (long)((a.M + bm - 1) / bm) * (a.N / 128);
-        if (tl < workers || (tl * a.total_chunks + workers - 1) / workers < a.total_chunks) {  // does not qualify: leave the choice alone
-            kind = kind0;
-            bm = bm0;
-            workers = workers0;
-        }
-    }
-    if (a.force >= 6 && a.force <= 10 && a.Wq) {  // parity tests: the wave-specialised kinds on any shape that qualifies
-        kind = a.force - 1;
-        bm = kind == 5 || kind == 9 ? 128 : kind == 6 ? 64 : kind == 7 ? 32 : 256;
-        workers = cus;
-    }
-    const int mtiles = (a.M + bm - 1) / bm, ntiles = a.N / 128;
-    const int tiles = mtiles * ntiles;
-    const long total = (long)tiles * a.total_chunks;
-    const int ipw = (int)((total + workers - 1) / workers);
-    // every range must span at least one full tile's worth of chunks, so a tile is shared by at most
-    // two workers and never lies strictly inside one range.
-    // Very short K (tdnn1 forward: 5 chunks) is faster one block per tile (measured).
-    static const int min_chunks = [] {
-        const char* e = sg_tune_env("SG_STREAMK_MINCHUNKS");
-        return e ? atoi(e) : 16;  // >= 16 chunks (K >= 512): tdnn4 / tdnn5 gain 4-12 %, tdnn1 (5 chunks) loses
-    }();
-    if (!slabs || !flags || tiles < workers || ipw < a.total_chunks || a.total_chunks < min_chunks) return hipErrorNotSupported;
-    // every worker has to be resident at once; if the runtime would admit fewer blocks than that, use the tile launch
-    const int per_cu = kind == 2 ? streamk_blocks_per_cu<2>() : kind == 1 ? streamk_blocks_per_cu<1>()
-                     : kind == 3 ? streamk_blocks_per_cu<3>() : kind == 4 ? streamk_blocks_per_cu<4>()
-                     : kind == 5 ? streamk_blocks_per_cu<5>() : kind == 6 ? streamk_blocks_per_cu<6>()
-                     : kind == 7 ? streamk_blocks_per_cu<7>() : kind == 8 ? streamk_blocks_per_cu<8>() : kind == 9 ? streamk_blocks_per_cu<9>() : streamk_blocks_per_cu<0>();
-    if ((long)per_cu * cus < workers) return hipErrorNotSupported;
-    if ((size_t)workers * bm * 128 > (size_t)512 * 128 * 128) return hipErrorNotSupported;  // slab capacity (sg_api.hip)
-    static std::atomic<unsigned> launch_counter{0};
-    unsigned epoch = ++launch_counter;
-    if (epoch == 0) epoch = ++launch_counter;  // 0 is the value of never-written flags
-    static const char* trace_file = sg_tune_env("SG_SK_TRACE");  // tuning aid: dump per-worker phase timestamps
-    // ... of the launches [SG_SK_TRACE_SKIP, SG_SK_TRACE_SKIP + SG_SK_TRACE_COUNT) only (default: all of them): a traced launch
-    // is followed by a synchronisation, so tracing every launch never sees the chip at the clock of a long loop
-    static const long trace_skip = [] {
+// tuning aid SG_SK_TRACE=file: per-worker phase timestamps of the stream-K launches [SG_SK_TRACE_SKIP, SG_SK_TRACE_SKIP +
+// SG_SK_TRACE_COUNT) of the process (default: all of them).  A traced launch is followed by a synchronisation, so tracing
+// every launch never sees the chip at the clock of a long loop.
+static const char* sk_trace_file() {
+    static const char* file = sg_tune_env("SG_SK_TRACE");
+    return file;
+}
+static unsigned long long* sk_trace_buffer(int workers) {
+    if (!sk_trace_file()) return nullptr;
+    static const long skip = [] {
         const char* e = sg_tune_env("SG_SK_TRACE_SKIP");
         return e ? atol(e) : 0L;
     }();
-    static const long trace_count = [] {
+    static const long count = [] {
         const char* e = sg_tune_env("SG_SK_TRACE_COUNT");
         return e ? atol(e) : (1L << 60);
     }();
-    static std::atomic<long> trace_seen{0};
-    static PerDeviceScratch trace_buf;
-    bool trace_this = trace_file != nullptr;
-    if (trace_this) {
-        const long idx = trace_seen.fetch_add(1, std::memory_order_relaxed);
-        trace_this = idx >= trace_skip && idx - trace_skip < trace_count;
+    static std::atomic<long> seen{0};
+    static PerDeviceScratch buf;
+    const long idx = seen.fetch_add(1, std::memory_order_relaxed);
+    if (idx < skip || idx - skip >= count) return nullptr;
+    return static_cast<unsigned long long*>(buf.get((size_t)workers * 16 * 8));
+}
+static void sk_trace_dump(const ConvGemmArgs& a, const ConvPlan& p, int epi, hipStream_t s) {
+    std::vector<unsigned long long> h((size_t)p.workers * 16);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    if (FILE* f = fopen(sk_trace_file(), "ab")) {
+        const int hdr[8] = {p.workers, a.M, a.N, a.total_chunks, p.ipw, p.tiles, epi, 0};
+        fwrite(hdr, sizeof(hdr), 1, f);
+        fwrite(h.data(), 8, h.size(), f);
+        fclose(f);
     }
-    unsigned long long* trace_dev = trace_this ? static_cast<unsigned long long*>(trace_buf.get((size_t)workers * 16 * 8)) : nullptr;
-    ConvGemmArgs at = a;
-    at.trace = trace_dev;
-    if (at.lose_counter && *at.lose_counter > 0) {  // fault injection: THIS stream-K launch publishes no hand-off flags
-        at.ablate |= 8;
-        --*at.lose_counter;
+}
+
+// the plan chose stream-K: the launch itself.  Everything that counts launches -- the epoch, the trace window, the
+// fault-injection budget -- moves only here, when a stream-K kernel is actually launched.
+static hipError_t launch_streamk(const ConvGemmArgs& a, const StreamKKind& kind, const ConvPlan& p, int epi, hipStream_t s) {
+    static std::atomic<unsigned> launch_counter{0};
+    unsigned epoch = ++launch_counter;
+    if (epoch == 0) epoch = ++launch_counter;  // 0 is the value of never-written flags
+    ConvGemmArgs ka = a;  // the kernel's copy
+    ka.trace = sk_trace_buffer(p.workers);
+    if (ka.lose_counter && *ka.lose_counter > 0) {  // fault injection: THIS stream-K launch publishes no hand-off flags
+        ka.ablate |= 8;
+        --*ka.lose_counter;
     }
-    at.lose_counter = nullptr;
-    dim3 grid(workers);
-#define a at
-#define SG_SK(EPI)                                                                                          \
-    if (kind == 9) launch_streamk_kind<EPI, 9>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);       \
-    else if (kind == 8) launch_streamk_kind<EPI, 8>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 7) launch_streamk_kind<EPI, 7>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 6) launch_streamk_kind<EPI, 6>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 5) launch_streamk_kind<EPI, 5>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 4) launch_streamk_kind<EPI, 4>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 3) launch_streamk_kind<EPI, 3>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 2) launch_streamk_kind<EPI, 2>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else if (kind == 1) launch_streamk_kind<EPI, 1>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);  \
-    else launch_streamk_kind<EPI, 0>(a, workers, ntiles, tiles, ipw, slabs, flags, epoch, s);
-    switch (epi) {
-        case EPI_NONE: SG_SK(EPI_NONE) break;
-        case EPI_BIAS_RELU: SG_SK(EPI_BIAS_RELU) break;
-        case EPI_RELU_MASK: SG_SK(EPI_RELU_MASK) break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SG_SK
-#undef a
-    if (trace_this && trace_dev) {
-        std::vector<unsigned long long> h((size_t)workers * 16);
-        if (hipStreamSynchronize(s) == hipSuccess &&
-            hipMemcpy(h.data(), trace_dev, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE* f = fopen(trace_file, "ab")) {
-                const int hdr[8] = {workers, at.M, at.N, at.total_chunks, ipw, tiles, epi, 0};
-                fwrite(hdr, sizeof(hdr), 1, f);
-                fwrite(h.data(), 8, h.size(), f);
-                fclose(f);
-            }
-        }
-    }
+    ka.lose_counter = nullptr;
+    kind.launch[epi](ka, p, epoch, s);
+    if (ka.trace) sk_trace_dump(ka, p, epi, s);
     return hipGetLastError();
 }
 
@@ -1750,10 +1627,29 @@ hipError_t launch_pack_k4(const float* w, int K, int N, float* wq, hipStream_t s
     return hipGetLastError();
 }
 
-int conv_gemm_tile_rows(int M, int N) {
-    (void)M;
-    (void)N;
-    return 64;
+// the launcher knobs ("Environment"), read once per process
+static const ConvKnobs& conv_knobs() {
+    static const ConvKnobs knobs = [] {
+        ConvKnobs k;
+        const auto read = [](const char* name, auto& v) {
+            if (const char* e = sg_tune_env(name)) v = atol(e);
+        };
+        read("SG_STREAMK", k.streamk);
+        read("SG_STREAMK_KIND", k.kind);
+        read("SG_STREAMK_W16", k.w16);
+        read("SG_STREAMK_MID", k.mid);
+        read("SG_STREAMK_MID9", k.mid9);
+        read("SG_STREAMK_DEEP", k.deep);
+        read("SG_STREAMK_WS", k.ws);
+        read("SG_STREAMK_WS_MINCHUNKS", k.ws_minchunks);
+        read("SG_STREAMK_MINCHUNKS", k.minchunks);
+        read("SG_STREAMK_XCD", k.xcd);
+        read("SG_QUADFEED", k.quadfeed);
+        read("SG_TILE32", k.tile32);
+        read("SG_S16_MAX_BLOCKS", k.s16_max_blocks);
+        return k;
+    }();
+    return knobs;
 }
 
 hipError_t launch_conv_gemm(const ConvGemmArgs& a_in, int tile, int epi, int splits, hipStream_t s) {
@@ -1765,23 +1661,12 @@ hipError_t launch_conv_gemm(const ConvGemmArgs& a_in, int tile, int epi, int spl
 #else
     constexpr int ablate = 0;
 #endif
-    static const int use_streamk = [] {
-        const char* e = sg_tune_env("SG_STREAMK");  // 0 = always one block per tile
-        return e ? atoi(e) : 1;
-    }();
+    const ConvKnobs& knobs = conv_knobs();
     ConvGemmArgs a = a_in;
     a.ablate |= ablate;  // (a_in.ablate: the fault-injection bit of sg_debug_lose_handoffs)
-    static const int sk_xcd = [] {
-        const char* e = sg_tune_env("SG_STREAMK_XCD");  // tuning aid, see the kernel
-        return e ? atoi(e) : 2;
-    }();
-    a.sk_xcd = sk_xcd;
-    static const int use_quad = [] {
-        const char* e = sg_tune_env("SG_QUADFEED");  // 0 = b32-fed 8-wave kernel even when packed weights exist
-        return e ? atoi(e) : 1;
-    }();
-    if (!use_quad || a.force == 2 || (a.ldw % 4) || (a.Kc % 4)) a.Wq = nullptr;
-    if (a.Kc % BK != 0 || a.M <= 0 || a.Tc <= 0) return hipErrorInvalidValue;
+    a.sk_xcd = knobs.xcd;
+    if (!knobs.quadfeed || a.force == 2 || (a.ldw % 4) || (a.Kc % 4)) a.Wq = nullptr;
+    if (a.Kc % BK != 0 || a.M <= 0 || a.Tc <= 0 || epi < EPI_NONE || epi > EPI_RELU_MASK) return hipErrorInvalidValue;
     // The staging loads address A and W through 32-bit buffer descriptors (num_records, per-lane byte offsets), and
     // the "this tap row is outside the utterance" marker is the offset 0x80000000, which must stay out of range:
     // an operand of 2 GiB or more is refused (the API layer reports the largest batch that fits, see check_dims).
@@ -1790,34 +1675,22 @@ hipError_t launch_conv_gemm(const ConvGemmArgs& a_in, int tile, int epi, int spl
     if (a_bytes >= 0x80000000ull || w_bytes >= 0x80000000ull) return hipErrorInvalidValue;
     a.a_bytes = (unsigned)a_bytes;
     a.w_bytes = (unsigned)w_bytes;
-    // batch 1-4: so few 16 x 16 output blocks that every one can have a SIMD (almost) to itself
-    static const long s16_max = [] {
-        const char* e = sg_tune_env("SG_S16_MAX_BLOCKS");  // 0 = never (tuning aid)
-        return e ? atol(e) : 2800L;
-    }();
-    if ((tile == 0 || tile == 2) && splits == 1 && a.Wq && (a.N % 32) == 0 &&
-        (a.force == 5 || (a.force == 0 && a.total_chunks >= 4 && (long)((a.M + 15) / 16) * (a.N / 16) <= s16_max)))
-        return launch_s16(a, epi, s);
-    switch (tile) {
-        case 0: {
-            if (a.N % 128) return hipErrorInvalidValue;
-            if (splits == 1 && use_streamk && !a.no_streamk && a.force != 1 && a.force != 4) {
-                const hipError_t e = launch_streamk(a, epi, a.sk_slabs, a.sk_flags, s);
-                if (e != hipErrorNotSupported) return e;
-                if (a.force >= 6) return hipErrorInvalidValue;  // a forced wave-specialised kind never silently becomes a tile launch
-            }
-            if (a.Wq && splits == 1 && a.force != 1) return launch_tile_q(a, epi, s);
-            return launch_tile<64, 128, 2, 2>(a, epi, splits, s);
-        }
-        case 1:
-            if (a.N % 32) return hipErrorInvalidValue;
-            return launch_tile<128, 32, 4, 1>(a, epi, splits, s);
-        case 2:
-            if (a.N % 128) return hipErrorInvalidValue;
-            if (a.Wq && splits == 1 && a.force != 1) return launch_tile_q(a, epi, s);
-            return launch_tile<64, 128, 2, 2>(a, epi, splits, s);
-        default:
-            return hipErrorInvalidValue;
+    ConvPlan p = conv_plan(a.M, a.N, a.total_chunks, tile, splits, a.force, a.Wq != nullptr, a.sk_slabs && a.sk_flags, a.no_streamk != 0,
+                           a.num_cus, knobs);
+    // stream-K: every worker has to be resident at once (a waiter spins on its predecessor) and park into its own slab;
+    // the runtime is asked about the chosen kind only, once per kind
+    const StreamKKind* kind = p.path == ConvPlan::STREAMK ? streamk_kind(p.kind) : nullptr;
+    if (p.path == ConvPlan::STREAMK &&
+        (!kind || (long)kind->blocks_per_cu() * p.cus < p.workers || (size_t)p.workers * p.bm * 128 > kSkSlabFloats))
+        p.path = kind ? p.fallback : ConvPlan::INVALID;
+    switch (p.path) {
+        case ConvPlan::S16: return launch_s16(a, epi, s);
+        case ConvPlan::STREAMK: return launch_streamk(a, *kind, p, epi, s);
+        case ConvPlan::QUAD32: return launch_tile_q<1>(a, epi, s);
+        case ConvPlan::QUAD64: return launch_tile_q<2>(a, epi, s);
+        case ConvPlan::TILE_64x128: return launch_tile<64, 128, 2, 2>(a, epi, splits, s);
+        case ConvPlan::TILE_128x32: return launch_tile<128, 32, 4, 1>(a, epi, splits, s);
+        default: return hipErrorInvalidValue;
     }
 }
 

@@ -201,9 +201,9 @@ int build_tables(sg_ctx* ctx) {
     }
     rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->range_scratch, 512);
     rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->cw2_scratch, 1024 * 32);
-    rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_slabs, (size_t)512 * 128 * 128);  // >= 768 * 64 * 128
-    rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_flags, 1024);
-    if (!rc && hipMemset(ctx->sk_flags, 0, 1024 * sizeof(unsigned)) != hipSuccess) rc = SG_ERR_HIP;
+    rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_slabs, kSkSlabFloats);
+    rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_flags, kSkFlags);
+    if (!rc && hipMemset(ctx->sk_flags, 0, kSkFlags * sizeof(unsigned)) != hipSuccess) rc = SG_ERR_HIP;
     if (rc) return SG_ERR_HIP;
     ctx->tables_ready = true;
     return SG_OK;
@@ -1103,7 +1103,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
     float ms = 0.f;
     SG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     *ms_per_launch = ms / (float)iters;
-    if (tile_rows) *tile_rows = tile == 0 ? conv_gemm_tile_rows(a.M, a.N) : 128;
+    if (tile_rows) *tile_rows = tile == 0 ? 64 : 128;
     if (flops) *flops = 2.0 * (double)a.M * (double)kCout[l] * (double)kCin[l] * (double)kTaps[l];
     return SG_OK;
 }

@@ -329,16 +329,16 @@ struct ConvGemmArgs {
     int sk_xcd;         // stream-K: XCD-contiguous workers + n-tile-major tile order (see kernel)
     int num_cus;        // stream-K: persistent blocks = resident slots of THIS device (0: assume 256)
     unsigned long long* trace;  // tuning aid (SG_SK_TRACE): per-worker phase timestamps, 16 slots each, or null
-    int force;          // 0 auto, 1 one b32-fed block per tile, 2 stream-K b32-fed 8-wave, 3 stream-K quad-fed 8-wave,
-                        // 4 one quad-fed block per tile, 5 one 16 x 16 block per wave, 6 / 7 / 8 / 9 stream-K with the roles split
-                        // between waves, 128- / 64- / 32- / 256-row tiles, 10 = 128-row tiles as four 64 x 64 computing waves
-                        // (kind 9) (parity tests)
+    int force;          // parity tests (sg_conv1d_rows `kernel`): 0 auto, 1 one b32-fed block per tile, 2 the b32-fed kernels
+                        // only (Wq dropped: stream-K kind 0 where the shape qualifies), 3 stream-K quad-fed 8-wave (kind 1),
+                        // 4 one quad-fed block per tile, 5 16 x 16 blocks, 6 .. 10 stream-K kind force - 1 (roles split between
+                        // waves: 128- / 64- / 32- / 256-row tiles, 128 rows as four 64 x 64 waves) or an error, never a tile launch
     int ablate;         // 8 = fault injection (sg_debug_lose_handoffs): stream-K hand-off flags are never published;
                         // builds with -DSG_EXP_ABLATE only (never the shipped library), from SG_ABLATE: 1 no global loads,
                         // 2 no LDS stores, 4 no barrier (results become wrong), 16 = A/B agent-scope fences around the hand-off
     int no_streamk;     // one block per tile whatever the shape (sg_set_streamk(ctx, 0): same bits, no co-residency needed)
-    float* sk_slabs;    // stream-K: [768][64*128] parked partial tiles (may be null -> tile launch)
-    unsigned* sk_flags; // stream-K: [768] hand-off flags
+    float* sk_slabs;    // stream-K: kSkSlabFloats floats, one parked partial tile [bm][128] per worker (may be null -> tile launch)
+    unsigned* sk_flags; // stream-K: [kSkFlags] hand-off flags, one per worker, holding the epoch of the launch that parked
     unsigned* err_word; // stream-K: device-visible health word (bit 0 = a hand-off wait timed out), may be null
     int* lose_counter;  // HOST pointer (never dereferenced on the device): the context's fault-injection budget, may be null
 };
@@ -392,12 +392,95 @@ inline void conv_ctx_args(sg_ctx* ctx, ConvGemmArgs& a) {
     a.lose_counter = ctx->use_streamk ? &ctx->lose_handoffs : nullptr;
 }
 
-// tile: 0 = auto (stream-K 128x128 8-wave blocks when the shape qualifies, else 64x128), 1 = 128x32 (4x1 waves),
-//       2 = 64x128 (2x2 waves), one block per tile
+// stream-K scratch of a context: room for 512 parked 128 x 128 (or 256 parked 256 x 128) partial tiles, and the flags
+constexpr size_t kSkSlabFloats = (size_t)512 * 128 * 128;
+constexpr int kSkFlags = 1024;
+
+// stream-K kinds (k_conv_gemm.hip, above conv_gemm_streamk_kernel): waves along M and the tile height
+constexpr int sk_wm(int kind) { return (kind == 2 || kind == 8) ? 4 : (kind == 3 || kind == 4 || kind == 6 || kind == 7) ? 1 : 2; }  // (9: 2)
+constexpr int sk_bm(int kind) { return (kind == 4 || kind == 7) ? 32 : 64 * sk_wm(kind); }
+
+// the launcher's tuning knobs with their defaults (SG_* names: INTEGRATION.md "Environment"; read by conv_knobs())
+struct ConvKnobs {
+    int streamk = 1;         // SG_STREAMK: 0 = always one block per tile
+    int kind = 0;            // SG_STREAMK_KIND: 5 .. 9 = this wave-specialised kind wherever the shape qualifies
+    int w16 = 1;             // SG_STREAMK_W16: 0 = two 8-wave 128x128 blocks per CU instead of the 16-wave 256x128 one
+    int mid = 1;             // SG_STREAMK_MID: 0 = no one-block-per-CU launches for fewer 256-row tiles than CUs
+    int mid9 = 0;            // SG_STREAMK_MID9: 1 = 128-row tiles as four 64 x 64 computing waves (kind 9) instead of kind 5
+    int deep = 1;            // SG_STREAMK_DEEP: 0 = the all-in-one kinds 1 / 3 / 4 instead of the wave-specialised 5 / 6 / 7
+    int ws = 1;              // SG_STREAMK_WS: 0 = the all-in-one 16-wave kernel (kind 2) for the full batch
+    int ws_minchunks = 64;   // SG_STREAMK_WS_MINCHUNKS: full batch, chunks per tile from which kind 8 beats kind 5
+    int minchunks = 16;      // SG_STREAMK_MINCHUNKS: shorter K is faster one block per tile (tdnn1: 5 chunks)
+    int xcd = 2;             // SG_STREAMK_XCD: worker / tile order, see the kernel
+    int quadfeed = 1;        // SG_QUADFEED: 0 = b32-fed kernels even when packed weights exist
+    int tile32 = 1;          // SG_TILE32: 0 = always 64-row quad tiles
+    long s16_max_blocks = 2800;  // SG_S16_MAX_BLOCKS: 16 x 16 blocks up to which every one has a SIMD (almost) to itself; 0 = never
+};
+
+// What launch_conv_gemm launches for a shape: a pure function of its arguments (no HIP call, no state), so the CPU build
+// can walk it (tests/test_launch_table.py).  One thing is left to the launcher, because only the runtime knows it: a
+// STREAMK plan whose `workers` blocks of `kind` are not all resident at once takes `fallback` instead.
+struct ConvPlan {
+    enum Path { INVALID, S16, STREAMK, QUAD32, QUAD64, TILE_64x128, TILE_128x32 };
+    Path path = INVALID;      // 16 x 16 blocks, stream-K, quad-fed 32- / 64-row tiles, b32-fed 64 x 128 / 128 x 32 tiles
+    Path fallback = INVALID;  // STREAMK only: the one-block-per-tile path, INVALID for a forced kind
+    int kind = 0, bm = 0, workers = 0, cus = 0, mtiles = 0, ntiles = 0, tiles = 0, ipw = 0;  // STREAMK only; cus: resident slots / blocks per CU
+};
+// tile: 0 = auto, 1 = 128x32 (4x1 waves), 2 = 64x128, the last two always one block per tile; wq: packed weights usable
+inline ConvPlan conv_plan(int M, int N, int total_chunks, int tile, int splits, int force, bool wq, bool slabs, bool no_streamk,
+                          int num_cus, const ConvKnobs& k) {
+    ConvPlan p;
+    // batch 1-4: so few 16 x 16 output blocks that every one can have a SIMD (almost) to itself
+    if ((tile == 0 || tile == 2) && splits == 1 && wq && N % 32 == 0 &&
+        (force == 5 || (force == 0 && total_chunks >= 4 && (long)((M + 15) / 16) * (N / 16) <= k.s16_max_blocks))) {
+        p.path = ConvPlan::S16;
+        return p;
+    }
+    if (tile == 1 && N % 32 == 0) p.path = ConvPlan::TILE_128x32;
+    if ((tile != 0 && tile != 2) || N % 128) return p;
+    const int nt = N / 128;
+    const auto mt = [&](int rows) { return (M + rows - 1) / rows; };
+    // One block per tile.  A nearly empty chip (batch <= 8: fewer 64-row tiles than CUs) waits for the sequential k chain of
+    // one tile; 32-row tiles halve the MFMAs per wave and chunk, so the chain -- and the launch -- takes half as long.
+    p.path = ConvPlan::TILE_64x128;
+    if (wq && splits == 1 && force != 1)
+        p.path = k.tile32 && force == 0 && total_chunks >= 8 && mt(64) * nt < (num_cus > 0 ? num_cus : 256) ? ConvPlan::QUAD32 : ConvPlan::QUAD64;
+    if (tile != 0 || splits != 1 || !k.streamk || no_streamk || force == 1 || force == 4) return p;
+
+    // Stream-K: one worker per resident slot of this device (slabs / flags are sized for 256 CUs) -- two 8-wave blocks per
+    // CU for kinds 0 / 1 as first chosen, one block per CU for every other choice.
+    const int cus = num_cus > 0 && num_cus < 256 ? num_cus : 256;
+    int kind = !wq ? 0 : (k.w16 && force != 3) ? 2 : 1;
+    int workers = kind == 2 ? cus : 2 * cus;
+    const auto one_per_cu = [&](int kd) { kind = kd; workers = cus; };
+    // Medium batches (B = 32 at 3 s: 136 tiles of 256 rows for 256 CUs): fewer 256-row tiles than CUs would leave the launch
+    // to the 4-wave tile kernel at ~100 TFLOP/s.  The tallest tile that still gives every CU one: 128 rows (B = 32), 64 rows
+    // (B = 16: balances the 272 tiles a one-block-per-tile launch would spread as 240 x 1 + 16 x 2), 32 rows (B = 8: half
+    // the k chain per tile).
+    if (k.mid && kind == 2 && force == 0 && mt(256) * nt < cus) {
+        if (mt(128) * nt >= cus) one_per_cu(k.deep ? (k.mid9 ? 9 : 5) : 1);
+        else if (mt(64) * nt >= cus) one_per_cu(k.deep ? 6 : 3);
+        else if (mt(32) * nt >= cus) one_per_cu(k.deep ? 7 : 4);
+    }
+    // The full batch (>= 256 tiles of 256 rows), measured per layer at 64 utterances (profiles/r03_layers.txt): with the roles
+    // split between waves (kind 8) tdnn2 / tdnn3 (80 / 112 chunks per tile) gain 1-3 %, tdnn4 / tdnn5 (16 / 48 chunks)
+    // lose 4-8 %; those are 3-4 % faster as 128-row tiles on kind 5 than on the all-in-one kind 2.
+    if (k.ws && kind == 2 && force == 0) one_per_cu(total_chunks >= k.ws_minchunks ? 8 : 5);
+    // every range must span at least one full tile's worth of chunks, so a tile is shared by at most two workers and never
+    // lies strictly inside one range
+    const auto ipw = [&](int kd, int w) { return (int)(((long)mt(sk_bm(kd)) * nt * total_chunks + w - 1) / w); };
+    const auto qualifies = [&](int kd, int w) { return mt(sk_bm(kd)) * nt >= w && ipw(kd, w) >= total_chunks; };
+    if (k.kind >= 5 && k.kind <= 9 && force == 0 && wq && qualifies(k.kind, cus)) one_per_cu(k.kind);  // else: leave the choice alone
+    if (force >= 6 && force <= 10 && wq) one_per_cu(force - 1);  // parity tests: this kind or an error
+    p.fallback = force >= 6 ? ConvPlan::INVALID : p.path;
+    p.path = slabs && qualifies(kind, workers) && total_chunks >= k.minchunks ? ConvPlan::STREAMK : p.fallback;
+    p.kind = kind; p.bm = sk_bm(kind); p.workers = workers; p.cus = cus;
+    p.mtiles = mt(p.bm); p.ntiles = nt; p.tiles = p.mtiles * nt; p.ipw = ipw(kind, workers);
+    return p;
+}
 hipError_t launch_conv_gemm(const ConvGemmArgs& a, int tile, int epi, int splits, hipStream_t s);
-int conv_gemm_tile_rows(int M, int N);
-// [K][N] row-major -> k4-major [K/4][N][4] on the device (K % 4 == 0)
-hipError_t launch_pack_k4(const float* w, int K, int N, float* wq, hipStream_t s);  // tile height launch_conv_gemm(tile 0) picks
+// [K][N] row-major -> k4-major [K/4][N][4] on the device (K % 4 == 0): the packed weights (Wq) of the quad-fed kernels
+hipError_t launch_pack_k4(const float* w, int K, int N, float* wq, hipStream_t s);
 
 // mode 0: xv_plda ('origin': [-1,1] -> x32768), mode 1: AudioNet ('scale': int16 range -> /32768)
 hipError_t launch_input_scale(const float* x, int64_t n, float* scratch512, float* scale, int mode, hipStream_t s);

@@ -3,6 +3,15 @@
 // report aborts the process (-fno-sanitize-recover); a failed expectation returns 1.  "Device" buffers are host
 // buffers sized exactly as the header says, so an entry point that uploads or downloads past a documented extent is an
 // ASan error here.
+//
+// `abi_asan_driver --launch-table all|device|isolated` is the second mode: it walks the contraction launcher
+// (launch_conv_gemm, k_conv_gemm.hip) over the shapes the GPU tests pin and prints one line per conv_gemm* launch the
+// double receives -- which kernel, which grid, which arguments.  No kernel runs, so the buffers are dummies.  The output
+// of every device / knob setting is recorded in tests/native/conv_launch_table.expected and tests/test_launch_table.py
+// compares byte for byte: a changed CHOICE of kernel, which gives the same bits on the GPU, shows here.
+#include <cxxabi.h>
+
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -11,9 +20,11 @@
 #include <vector>
 
 #include "speakerguard_hip.h"
+#include "../../speakerguard_amd/csrc/sg_internal.h"  // ConvGemmArgs: the launch table reads the first kernel argument
 
 extern "C" long hipdouble_launches();
 extern "C" long hipdouble_live_allocs();
+extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                 \
@@ -74,7 +85,143 @@ struct AnModel {
     }
 };
 
-int main() {
+// ---- the launch table ------------------------------------------------------------------------------------------
+static std::string g_case;                 // label of the call being walked: every line carries it
+static int g_epi = -1;                     // its epilogue
+static std::vector<std::string> g_lines;   // the conv_gemm* launches it made
+
+static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void** args) {
+    int status = 0;
+    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+    std::string name = dm ? dm : mangled;
+    std::free(dm);
+    name = name.substr(0, name.find('('));  // "void sg::conv_gemm_q_kernel<1, 2>"
+    const size_t at = name.find("conv_gemm");
+    if (at == std::string::npos) return;
+    name = name.substr(at);
+    name.erase(std::remove(name.begin(), name.end(), ' '), name.end());  // one token: "conv_gemm_q_kernel<1,2>"
+    // the template argument that is the epilogue (the last one of conv_gemm_kernel, the first one of the others) is printed as
+    // E where it is the epilogue asked for, so that the three epilogues of a case can share a line; a wrong one stays a number
+    const size_t e = name.find("conv_gemm_kernel<") == 0 ? name.size() - 2 : name.find('<') + 1;
+    if (name[e] == '0' + g_epi) name[e] = 'E';
+    const sg::ConvGemmArgs& a = *static_cast<const sg::ConvGemmArgs*>(args[0]);
+    // the scalars after the argument block: stream-K (ntiles, tiles, iters_per_worker; not the epoch, which counts launches),
+    // 16 x 16 blocks (ntile32), one block per tile (mtiles, ntiles)
+    const int n_scalars = name.find("streamk") != std::string::npos ? 3 : name.find("s16") != std::string::npos ? 1 : 2;
+    std::string scalars;
+    for (int i = 1; i <= n_scalars; ++i) scalars += (i > 1 ? "," : "") + std::to_string(*static_cast<const int*>(args[i]));
+    char line[256];
+    std::snprintf(line, sizeof(line), "%s grid=%u,%u,%u block=%u lds=%zu Wq=%d a_bytes=%u w_bytes=%u sk_xcd=%d ablate=%d trace=%d args=%s",
+                  name.c_str(), grid.x, grid.y, grid.z, block.x, shmem, a.Wq != nullptr, a.a_bytes, a.w_bytes, a.sk_xcd, a.ablate,
+                  a.trace != nullptr, scalars.c_str());
+    g_lines.push_back(line);
+}
+
+static void begin_case(const std::string& label, int epi) {
+    g_case = label;
+    g_epi = epi;
+    g_lines.clear();
+}
+// a call that failed, or launched nothing of interest, still leaves a line
+static void end_case(sg_ctx* ctx, int rc) {
+    if (rc != SG_OK) g_lines.push_back("rc=" + std::to_string(rc) + " " + sg_last_error(ctx));
+    else if (g_lines.empty()) g_lines.push_back("no conv_gemm launch");
+}
+static void print_case(const std::string& label) {
+    for (size_t i = 0; i < g_lines.size(); ++i)
+        std::printf("%s%s | %s\n", label.c_str(), g_lines.size() > 1 ? (" #" + std::to_string(i + 1)).c_str() : "", g_lines[i].c_str());
+}
+
+struct ConvShape { const char* id; int B, Ta, Tc, Kc, N, taps, step, base; };
+
+// One shape with the given kernels, all three epilogues each.  Epilogues of a kernel that launch the same thing -- E in the
+// kernel name standing for the epilogue asked for -- share a line, labelled k<kernel> e<epilogues>.
+static void walk_conv(sg_ctx* ctx, const ConvShape& c, int kernel_lo, int kernel_hi, const char* prefix = "") {
+    static float dummy[4];  // never dereferenced: the double runs no kernel
+    for (int kernel = kernel_lo; kernel <= kernel_hi; ++kernel) {
+        std::vector<std::pair<std::vector<std::string>, std::string>> groups;  // launches -> the epilogues that made them
+        for (int epi = 0; epi <= 2; ++epi) {
+            begin_case("", epi);
+            end_case(ctx, sg_conv1d_rows(ctx, dummy, dummy, dummy, dummy, dummy, c.B, c.Ta, c.Tc, c.Kc, c.N, c.taps, c.step, c.base, epi, kernel, nullptr));
+            auto g = std::find_if(groups.begin(), groups.end(), [](const auto& x) { return x.first == g_lines; });
+            if (g == groups.end()) g = groups.insert(g, {g_lines, ""});
+            g->second += std::to_string(epi);
+        }
+        for (const auto& g : groups) {
+            g_lines = g.first;
+            print_case(std::string(prefix) + c.id + " B=" + std::to_string(c.B) + " k" + std::to_string(kernel) + " e" + g.second);
+        }
+    }
+}
+
+// mode "all": every kernel at every isolated shape, the whole models, fault injection (the default device without knobs);
+// "device" / "isolated" (device / knob variants): thinned to the launcher's own choice (kernel 0) everywhere and the forced
+// kernels at the eleven shapes where tests/test_gpu_conv.py forces them, with / without the models
+static int launch_table(const std::string& mode) {
+    setenv("SG_TUNE", "1", 1);  // the knobs of the caller's environment count
+    hipdouble_set_launch_hook(record_launch);
+    sg_ctx* ctx = nullptr;
+    if (sg_create(0, &ctx) != SG_OK) return 1;
+    const int batches[9] = {1, 2, 4, 5, 7, 8, 16, 32, 64};
+    std::vector<ConvShape> shapes = {  // tests/test_gpu_conv.py::SHAPES
+        {"fwd_streamk_dil2", 64, 270, 266, 192, 512, 3, 2, 0},        {"dgrad_streamk_edges", 64, 266, 270, 192, 512, 3, -2, 0},
+        {"fwd_streamk_mid_128row", 32, 270, 266, 192, 512, 3, 2, 0},  {"dgrad_streamk_mid_128row", 32, 266, 270, 192, 512, 3, -2, 0},
+        {"fwd_streamk_small_64row", 16, 270, 266, 192, 512, 3, 2, 0}, {"dgrad_streamk_small_64row", 16, 266, 270, 192, 512, 3, -2, 0},
+        {"fwd_streamk_tiny_32row", 8, 270, 266, 192, 512, 3, 2, 0},   {"dgrad_streamk_tiny_32row", 8, 266, 270, 192, 512, 3, -2, 0},
+        {"fwd_small_ragged_tile", 3, 50, 46, 64, 128, 5, 1, 0},       {"dgrad_small", 2, 40, 46, 96, 256, 3, -3, 0},
+        {"same_padding_tap_base", 5, 33, 33, 32, 128, 3, 1, -1}};
+    for (int b : batches) shapes.push_back({"tdnn3_fwd", b, 288, 270, 512, 512, 7, 3, 0});
+    for (int b : batches) shapes.push_back({"tdnn3_dgrad", b, 270, 288, 512, 512, 7, -3, 0});
+    const int tdnn1[5][2] = {{64, 300}, {8, 300}, {3, 125}, {1, 100}, {5, 208}};
+    for (auto& bf : tdnn1) shapes.push_back({"tdnn1_fwd", bf[0], bf[1], bf[1] - 4, 32, 512, 5, 1, 0});
+    for (int b : batches) shapes.push_back({"n1536", b, 270, 270, 512, 1536, 1, 1, 0});
+    for (size_t i = 0; i < shapes.size(); ++i) walk_conv(ctx, shapes[i], 0, mode == "all" || i < 11 ? 10 : 0);
+    if (mode != "isolated") {
+        // one forward + backward of the synthetic x-vector model at the shapes of tests/test_gpu_layers.py (tile 1, split-K fc1,
+        // the tdnn1 data gradient), one per-layer pass of AudioNet (tile 1 / 2 by N % 128)
+        const int S = 4;
+        XvModel xv(24, S);
+        if (sg_xv_load(ctx, &xv.desc) != SG_OK) return 1;
+        sg_loss_spec ce{};
+        std::vector<std::pair<int, int>> grid;
+        for (int b : batches) grid.push_back({b, 48000});
+        grid.insert(grid.end(), {{9, 52960}, {5, 16123}, {2, 192000}, {3, 16000}});
+        for (auto& bt : grid) {
+            const int B = bt.first, T = bt.second;
+            std::vector<float> x((size_t)B * T), g((size_t)B * T), sc((size_t)B * S), loss(B);
+            std::vector<int64_t> y(B, 0), dec(B);
+            const std::string label = "xv B=" + std::to_string(B) + " T=" + std::to_string(T);
+            begin_case(label, -1);
+            end_case(ctx, sg_xv_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, nullptr, dec.data(), sc.data(), loss.data(), g.data(), nullptr));
+            print_case(label);
+        }
+        const int B = 3, T = 16000, Sa = 11;
+        AnModel an(Sa);
+        if (sg_an_load(ctx, &an.desc) != SG_OK) return 1;
+        std::vector<float> x((size_t)B * T), g((size_t)B * T), sc((size_t)B * Sa), loss(B);
+        std::vector<int64_t> y(B, 0), dec(B);
+        setenv("SG_AN_FUSED", "0", 1);
+        begin_case("audionet", -1);
+        end_case(ctx, sg_an_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, dec.data(), sc.data(), loss.data(), g.data(), nullptr));
+        print_case("audionet per layer B=3 T=16000");
+    }
+    if (mode == "all") {
+        // fault injection: a budget of one lost hand-off survives a launch that ends on a tile kernel and marks exactly the
+        // next stream-K launch (ablate bit 8); then the context without stream-K
+        const ConvShape tile_shape = {"tdnn1_fwd", 64, 300, 296, 32, 512, 5, 1, 0}, sk_shape = shapes[0];  // 5 chunks: a tile launch
+        if (sg_debug_lose_handoffs(ctx, 1) != SG_OK) return 1;
+        // (three epilogues = three launches per walk: the budget is spent by the first stream-K one, epilogue 0)
+        walk_conv(ctx, tile_shape, 0, 0, "lose_handoffs=1 ");
+        walk_conv(ctx, sk_shape, 0, 0, "lose_handoffs=1 ");
+        if (sg_set_streamk(ctx, 0) != SG_OK) return 1;
+        walk_conv(ctx, sk_shape, 0, 10, "set_streamk=0 ");
+    }
+    sg_destroy(ctx);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 3 && std::string(argv[1]) == "--launch-table") return launch_table(argv[2]);
     // ---- no context ------------------------------------------------------------------------------------------
     EXPECT(sg_version() == 100);
     EXPECT(sg_xv_num_frames(48000) == 300 && sg_xv_num_frames(100) == 0 && sg_an_num_frames(48000) == 300);

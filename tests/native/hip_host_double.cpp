@@ -5,30 +5,47 @@
 // argument validation, table builders, BatchNorm folding, k4 packing, workspace sizing, launch-strategy selection,
 // error-string lifetime) and linked against THIS file instead of libamdhip64: "device" memory is host memory from
 // calloc (so AddressSanitizer sees every upload / download the host half performs with its true extent), events are
-// counters, and a kernel launch is counted and otherwise ignored -- no kernel arithmetic runs here, GPU results are
-// the business of `pytest -m gpu`.  Runs in the GPU-less build container.
+// counters, and a kernel launch is counted, shown to the launch hook (if one is set) and otherwise ignored -- no
+// kernel arithmetic runs here, GPU results are the business of `pytest -m gpu`.  Runs in the GPU-less build container.
+// The device the double plays can be resized from the environment, read at every query: HIPDOUBLE_CUS (compute units,
+// default 256) and HIPDOUBLE_OCCUPANCY (the answer to hipOccupancyMaxActiveBlocksPerMultiprocessor, default 2).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 
 static long g_launches = 0, g_allocs = 0, g_frees = 0, g_bytes = 0;
 static dim3 g_grid, g_block;
 static size_t g_shmem = 0;
 static hipStream_t g_stream = nullptr;
 
+typedef void (*hipdouble_launch_hook)(const char* mangled_name, dim3 grid, dim3 block, size_t shmem, void** args);
+static hipdouble_launch_hook g_hook = nullptr;
+// host pointer -> mangled kernel name, as __hipRegisterFunction hands them over (from static constructors: built on first use)
+static std::map<const void*, std::string>& kernel_names() {
+    static std::map<const void*, std::string> m;
+    return m;
+}
+static int env_int(const char* name, int dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
+
 extern "C" {
 
 long hipdouble_launches() { return g_launches; }
 long hipdouble_live_allocs() { return g_allocs - g_frees; }
+void hipdouble_set_launch_hook(hipdouble_launch_hook hook) { g_hook = hook; }
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t* p, int) {
     std::memset(p, 0, sizeof(*p));
-    p->multiProcessorCount = 256;
+    p->multiProcessorCount = env_int("HIPDOUBLE_CUS", 256);
     p->sharedMemPerBlock = 64 * 1024;
     p->maxSharedMemoryPerMultiProcessor = 160 * 1024;
     std::snprintf(p->name, sizeof(p->name), "host double of gfx950");
@@ -64,7 +81,11 @@ hipError_t hipMemcpyFromSymbol(void* dst, const void* sym, size_t n, size_t off,
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipGetLastError() { return hipSuccess; }
-const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "error (host double)"; }
+const char* hipGetErrorString(hipError_t e) {
+    static thread_local char buf[40];
+    std::snprintf(buf, sizeof(buf), "hip error %d (host double)", (int)e);
+    return e == hipSuccess ? "no error" : buf;
+}
 
 struct FakeEvent { long stamp; };
 hipError_t hipEventCreate(hipEvent_t* e) { *e = reinterpret_cast<hipEvent_t>(std::calloc(1, sizeof(FakeEvent))); ++g_allocs; return hipSuccess; }
@@ -77,7 +98,10 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
 }
 
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, const void*, int, size_t) { *n = 2; return hipSuccess; }
+hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, const void*, int, size_t) {
+    *n = env_int("HIPDOUBLE_OCCUPANCY", 2);
+    return hipSuccess;
+}
 
 hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t shmem, hipStream_t s) {
     g_grid = grid; g_block = block; g_shmem = shmem; g_stream = s;
@@ -87,7 +111,7 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
     *grid = g_grid; *block = g_block; *shmem = g_shmem; *s = g_stream;
     return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void*, dim3 grid, dim3 block, void**, size_t, hipStream_t) {
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t) {
     // what a launch the hardware would refuse looks like: empty or oversized grids / blocks are host-side bugs
     if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024) {
         std::fprintf(stderr, "hip double: invalid launch configuration grid (%u,%u,%u) block (%u,%u,%u)\n", grid.x, grid.y, grid.z,
@@ -95,11 +119,17 @@ hipError_t hipLaunchKernel(const void*, dim3 grid, dim3 block, void**, size_t, h
         std::abort();
     }
     ++g_launches;
+    if (g_hook) {
+        const auto it = kernel_names().find(fn);
+        g_hook(it == kernel_names().end() ? "?" : it->second.c_str(), grid, block, shmem, args);
+    }
     return hipSuccess;
 }
 void** __hipRegisterFatBinary(const void*) { static void* handle[2]; return handle; }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*) {
+    kernel_names()[host_fn] = device_name;
+}
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 
 }  // extern "C"

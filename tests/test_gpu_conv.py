@@ -1,7 +1,8 @@
 """The implicit-GEMM convolution kernels in isolation (C-ABI sg_conv1d_rows) against the numpy oracle.
 
-Every launch strategy (one block per tile, stream-K with the b32-fed 8-wave kernel, stream-K with the 8-wave and
-the 16-wave quad-fed kernel -- the last is what the TDNN layers use) must give BIT-IDENTICAL results -- that is what makes a batch shard
+Every launch strategy (one block per tile, 16 x 16 blocks, stream-K with the b32-fed 8-wave kernel, with the 8-wave and the
+16-wave quad-fed kernels and with the wave-specialised kinds -- which of them a TDNN layer gets depends on its shape and the
+batch: conv_plan, csrc/sg_internal.h) must give BIT-IDENTICAL results -- that is what makes a batch shard
 reproduce the unsharded batch exactly -- and all must agree with the float64 oracle to fp32 accumulation error.
 """
 import numpy as np
