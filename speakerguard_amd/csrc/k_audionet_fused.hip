@@ -592,7 +592,7 @@ __device__ __forceinline__ void fz_bwd_layer(const AnFusedArgs& p, const AnSlice
     __syncthreads();
 }
 
-// The head of the network for the block's utterance (AnHeadArgs): scratch in `scr` (>= 6 K floats of the idle LDS buffer), the
+// The head of the network for the block's utterance (AnHeadArgs): scratch in `scr` (kFzHeadFloats = 4096 floats of the idle LDS buffer), the
 // window of d loss / d conv8 pre-activation rows [base, base + rows) -> `win` ([rows][32], fz_off<32>, zero outside the tensor).
 // Phase by phase an_tail_kernel's arithmetic (k_audionet.hip) on the first 256 threads where that kernel's 256 matter for
 // the order of a sum: the same bits.
@@ -765,36 +765,43 @@ __global__ __launch_bounds__(kFzThreads, 1) void an_cnn_fwdbwd_kernel(AnFusedArg
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Host side: slices per utterance and LDS demand.
-static int fz_plan(const int* Tin, const int* Tout, int Fnet, int rows, int num_cus, int* S_out, int* buf_floats_out) {
-    const int T8 = Tout[kAnConv - 1];
-    if (T8 < 1) return -1;
-    const int cus = num_cus > 0 ? num_cus : 256;
-    auto demand = [&](int S) {
-        int need = 0;
-        for (int s = 0; s < S; ++s) {
-            AnSlice f, b;
-            an_slice_fwd(Tin, Tout, Fnet, S, s, f);
-            an_slice_bwd(Tin, Tout, Fnet, S, s, b);
-            need = std::max(need, (f.phi - f.plo + 4) * (kAnMel + 4) + 4);  // zero-bordered staging of the pre-filter's input
-            need = std::max(need, (b.phi - b.plo + 4) * (kAnMel + 4) + 4);  // ... and of its transpose
-            for (int l = 0; l < kAnConv; ++l) {
-                need = std::max(need, (f.ohi[l] - f.olo[l] + 2) * kAnCin[l]);   // forward input window of conv l
-                need = std::max(need, (b.whi[l] - b.wlo[l] + 2) * kAnCout[l]);  // backward: d act[l] window
-            }
+// Host side: the plan of a pass (launch form, slices per utterance, LDS demand) and the launchers that carry it out.
+
+// floats per LDS buffer that a cut into S slices needs
+static int fz_demand(const int* Tin, const int* Tout, int Fnet, int S) {
+    int need = 0;
+    for (int s = 0; s < S; ++s) {
+        AnSlice f, b;
+        an_slice_fwd(Tin, Tout, Fnet, S, s, f);
+        an_slice_bwd(Tin, Tout, Fnet, S, s, b);
+        need = std::max(need, (f.phi - f.plo + 4) * (kAnMel + 4) + 4);  // zero-bordered staging of the pre-filter's input
+        need = std::max(need, (b.phi - b.plo + 4) * (kAnMel + 4) + 4);  // ... and of its transpose
+        for (int l = 0; l < kAnConv; ++l) {
+            need = std::max(need, (f.ohi[l] - f.olo[l] + 2) * kAnCin[l]);   // forward input window of conv l
+            need = std::max(need, (b.whi[l] - b.wlo[l] + 2) * kAnCout[l]);  // backward: d act[l] window
         }
-        return (need + 3) & ~3;
-    };
+    }
+    return (need + 3) & ~3;
+}
+
+AnNetPlan an_net_plan(const AnKnobs& knobs, int rows, int Fnet, int num_cus, bool device_ok, bool want_grad) {
+    AnNetPlan p{};
+    p.Fnet = Fnet;
+    p.form = AN_PER_LAYER;
+    p.frames_ok = an_layer_frames(Fnet, p.Tin, p.Tout);
+    if (!p.frames_ok || !knobs.fused || !device_ok || rows < 1 || rows > 65535) return p;  // (gridDim.y = rows)
+    const int T8 = p.Tout[kAnConv - 1];
+    const int cus = num_cus > 0 ? num_cus : 256;
+    constexpr size_t kLdsBudget = 160 * 1024 - 512;
+    auto fits = [&](int S) { return (size_t)fz_demand(p.Tin, p.Tout, Fnet, S) * 2 * sizeof(float) <= kLdsBudget; };
     // cost model: rounds of blocks on the chip x time of a block, in conv8 rows: its share + 12 -- a block's time is not
     // proportional to its rows (tools/an_trace.py, forward: 51 us at 2.2 rows, 79 us at 8.75, 163 us at 35: ~42 us + 3.6 us
     // per row: halo, the layers' barriers and epilogues, the weight stream's start).  Until round 5 the constant was 4 and
     // 129..255 utterances were cut too finely (192 utterances: 0.77 ms per PGD step against 0.67 at 256).
     int best = 0;
     double best_cost = 0.0;
-    const int smax = std::min(T8, 16);
-    constexpr int kLdsBudget = 160 * 1024 - 512;
-    for (int S = 1; S <= smax; ++S) {
-        if ((size_t)demand(S) * 2 * sizeof(float) > (size_t)kLdsBudget) continue;
+    for (int S = 1; S <= std::min(T8, 16); ++S) {
+        if (!fits(S)) continue;
         const long blocks = (long)rows * S;
         const double cost = (double)((blocks + cus - 1) / cus) * ((double)T8 / S + 12.0);
         if (!best || cost < best_cost - 1e-9) {
@@ -802,15 +809,26 @@ static int fz_plan(const int* Tin, const int* Tout, int Fnet, int rows, int num_
             best_cost = cost;
         }
     }
-    if (!best) return -1;  // even the finest cut does not fit (very long utterances): the per-layer path takes over
-    *S_out = best;
-    *buf_floats_out = demand(best);
-    return 0;
+    if (!best) return p;  // even the finest cut does not fit (very long utterances): the per-layer path takes over
+    // the forced cut (tests: the result must not depend on it) if it fits, else the planner's
+    const int forced = knobs.slices > 0 ? std::min(knobs.slices, T8) : 0;
+    p.S = forced && fits(forced) ? forced : best;
+    p.buf_floats = fz_demand(p.Tin, p.Tout, Fnet, p.S);
+    p.buf_floats_head = std::max(p.buf_floats, kFzHeadFloats);
+    // two builds of each kernel (fz_mac): small slices -- three or more per utterance, one 32-row tile per wave -- take the
+    // deep W ring, whole / half utterances the compact multiply loop with the straight-path epilogues.  Same bits.
+    p.small = p.S >= 3;
+    // Where the head runs (round 6).  Inside the fused backward launch whenever a gradient follows: 3-5 % of a feature-level
+    // pass (tools/an_head_ab.py: 188 -> 182 us at 64 utterances, 702 -> 665 at 512), neutral inside the device loops
+    // (tools/an_head_loop_ab.py).  The one-launch form is bit-equal but measured 3.5 % SLOWER inside the PGD loop at 256 / 512
+    // utterances (profiles/r06_an_head_ab.txt): only on request.
+    p.form = !(want_grad && knobs.head) ? AN_FUSED_TAIL : knobs.one && p.S == 1 ? AN_ONE_LAUNCH : AN_FUSED_HEAD;
+    return p;
 }
 
 // The kernels ask for up to 160 KB of dynamic LDS (gfx950's per-CU LDS; the Makefile's ARCH is overridable): the opt-in is
 // made once per DEVICE, and a device that refuses it (less LDS) runs the per-layer sequence instead of failing every call.
-static bool fz_device_ok() {
+bool an_fused_device_ok() {
     static std::atomic<int> state[kMaxDevices];  // 0 unknown, 1 opted in, -1 refused
     const int d = sg_device_slot();
     int st = state[d].load(std::memory_order_relaxed);
@@ -828,41 +846,13 @@ static bool fz_device_ok() {
     return st > 0;
 }
 
-bool an_fused_supported(const int* Tin, const int* Tout, int Fnet, int rows, int num_cus) {
-    int S, bf;
-    if (rows < 1 || rows > 65535) return false;  // gridDim.y = rows
-    return fz_plan(Tin, Tout, Fnet, rows, num_cus, &S, &bf) == 0 && fz_device_ok();
-}
-
-hipError_t launch_an_cnn_fused(AnFusedArgs a, int rows, int num_cus, bool backward, int force_slices, hipStream_t s) {
-    int S = 0, bf = 0;
-    if (fz_plan(a.Tin, a.Tout, a.Fnet, rows, num_cus, &S, &bf) != 0) return hipErrorNotSupported;
-    if (force_slices > 0) {  // tests: the result must not depend on the cut
-        const int keep = S;
-        S = std::min(force_slices, a.Tout[kAnConv - 1]);
-        int need = 0;
-        for (int sl = 0; sl < S; ++sl) {
-            AnSlice f, b;
-            an_slice_fwd(a.Tin, a.Tout, a.Fnet, S, sl, f);
-            an_slice_bwd(a.Tin, a.Tout, a.Fnet, S, sl, b);
-            need = std::max(need, std::max((f.phi - f.plo + 4) * (kAnMel + 4) + 4, (b.phi - b.plo + 4) * (kAnMel + 4) + 4));
-            for (int l = 0; l < kAnConv; ++l)
-                need = std::max(need, std::max((f.ohi[l] - f.olo[l] + 2) * kAnCin[l], (b.whi[l] - b.wlo[l] + 2) * kAnCout[l]));
-        }
-        bf = (need + 3) & ~3;
-        if ((size_t)bf * 2 * sizeof(float) > 160 * 1024 - 512) {
-            S = keep;
-            if (fz_plan(a.Tin, a.Tout, a.Fnet, rows, num_cus, &S, &bf) != 0) return hipErrorNotSupported;
-        }
-    }
-    if (backward && a.head.on && bf < kFzHeadFloats) bf = kFzHeadFloats;  // the head's scratch lives in the second buffer
+hipError_t launch_an_cnn_fused(AnFusedArgs a, const AnNetPlan& plan, int rows, bool backward, hipStream_t s) {
+    if (plan.form == AN_PER_LAYER) return hipErrorNotSupported;
+    const int S = plan.S;
     a.S = S;
-    a.buf_floats = bf;
-    const size_t lds = (size_t)bf * 2 * sizeof(float);
-    if (rows > 65535 || !fz_device_ok()) return hipErrorNotSupported;
-    // two builds of each kernel (fz_mac): small slices -- three or more per utterance, one 32-row tile per wave -- take the
-    // deep W ring, whole / half utterances the compact multiply loop with the straight-path epilogues.  Same bits.
-    const bool small = S >= 3;
+    a.buf_floats = backward && a.head.on ? plan.buf_floats_head : plan.buf_floats;
+    const size_t lds = (size_t)a.buf_floats * 2 * sizeof(float);
+    const bool small = plan.small;
     static const char* trace_file = sg_tune_env("SG_AN_TRACE");  // tuning aid: dump the per-block stage timestamps of every launch
     static PerDeviceScratch trace_buf;
     const size_t nblk = (size_t)S * rows;
@@ -894,36 +884,12 @@ hipError_t launch_an_cnn_fused(AnFusedArgs a, int rows, int num_cus, bool backwa
     return hipGetLastError();
 }
 
-// LDS floats per buffer that whole utterances (S = 1) need; 0: they do not fit
-static int fz_whole_utterance_floats(const int* Tin, const int* Tout, int Fnet) {
-    AnSlice f, b;
-    an_slice_fwd(Tin, Tout, Fnet, 1, 0, f);
-    an_slice_bwd(Tin, Tout, Fnet, 1, 0, b);
-    int need = std::max((f.phi - f.plo + 4) * (kAnMel + 4) + 4, (b.phi - b.plo + 4) * (kAnMel + 4) + 4);
-    for (int l = 0; l < kAnConv; ++l)
-        need = std::max(need, std::max((f.ohi[l] - f.olo[l] + 2) * kAnCin[l], (b.whi[l] - b.wlo[l] + 2) * kAnCout[l]));
-    need = (need + 3) & ~3;
-    return (size_t)need * 2 * sizeof(float) > 160 * 1024 - 512 ? 0 : need;
-}
-
-// the cut the fused launches will use: the planner's, or `force_slices` (tests) when that fits; 0: not supported
-int an_fused_slices(const int* Tin, const int* Tout, int Fnet, int rows, int num_cus, int force_slices) {
-    int S = 0, bf = 0;
-    if (rows < 1 || rows > 65535 || Tout[kAnConv - 1] < 1 || !fz_device_ok()) return 0;
-    if (force_slices == 1 && fz_whole_utterance_floats(Tin, Tout, Fnet) > 0) return 1;
-    if (fz_plan(Tin, Tout, Fnet, rows, num_cus, &S, &bf) != 0) return 0;
-    return force_slices > 1 ? std::min(force_slices, Tout[kAnConv - 1]) : S;
-}
-
-hipError_t launch_an_cnn_fwdbwd(AnFusedArgs a, int rows, int num_cus, int force_slices, hipStream_t s) {
-    if (an_fused_slices(a.Tin, a.Tout, a.Fnet, rows, num_cus, force_slices) != 1) return hipErrorNotSupported;
-    int bf = fz_whole_utterance_floats(a.Tin, a.Tout, a.Fnet);
-    if (bf <= 0 || !a.head.on) return hipErrorNotSupported;
-    if (bf < kFzHeadFloats) bf = kFzHeadFloats;
+hipError_t launch_an_cnn_fwdbwd(AnFusedArgs a, const AnNetPlan& plan, int rows, hipStream_t s) {
+    if (plan.form != AN_ONE_LAUNCH || !a.head.on) return hipErrorNotSupported;
     a.S = 1;
-    a.buf_floats = bf;
+    a.buf_floats = plan.buf_floats_head;
     a.trace = nullptr;
-    hipLaunchKernelGGL(an_cnn_fwdbwd_kernel, dim3(1, rows), dim3(kFzThreads), (size_t)bf * 2 * sizeof(float), s, a);
+    hipLaunchKernelGGL(an_cnn_fwdbwd_kernel, dim3(1, rows), dim3(kFzThreads), (size_t)a.buf_floats * 2 * sizeof(float), s, a);
     return hipGetLastError();
 }
 

@@ -182,25 +182,9 @@ int an_build_tables(sg_ctx* ctx) {
     return SG_OK;
 }
 
-// frames entering / leaving every conv; false if the utterance is too short for conv8 (kernel 3, no pad)
-bool an_layer_frames(int F, int* Tin, int* Tout) {
-    int t = F;
-    for (int l = 0; l < kAnConv; ++l) {
-        Tin[l] = t;
-        Tout[l] = t + 2 * kAnPad[l] - 2;
-        if (Tout[l] < 1) return false;
-        t = kAnPool[l] ? Tout[l] / 2 : Tout[l];
-        if (t < 1) return false;
-    }
-    return Tin[kAnConv - 1] >= 3;
-}
-
 int an_ensure_workspace(sg_ctx* ctx, int B, int T, int F) {
     AnWorkspace& w = ctx->an_ws;
-    if (B <= w.B && F <= w.F && T <= w.T && w.scale) {
-        an_layer_frames(F, w.Tin, w.Tout);
-        return SG_OK;
-    }
+    if (B <= w.B && F <= w.F && T <= w.T && w.scale) return SG_OK;
     (void)hipDeviceSynchronize();
     for (void* p : w.allocs) (void)hipFree(p);
     const int cb = B > w.B ? B : w.B, cf = F > w.F ? F : w.F, ct = T > w.T ? T : w.T;
@@ -238,7 +222,6 @@ int an_ensure_workspace(sg_ctx* ctx, int B, int T, int F) {
         w = AnWorkspace();
         return SG_ERR_HIP;
     }
-    an_layer_frames(F, w.Tin, w.Tout);
     return SG_OK;
 }
 
@@ -326,21 +309,23 @@ int an_frontend_forward(sg_ctx* ctx, const float* x, const AnDims& d, hipStream_
     return SG_OK;
 }
 
-// features (B, Fnet, 32) -> conv stack; Fnet is the frame count the network sees (the front-end's, or the number of
-// FeCo clusters when the defense sits between front-end and network)
-// SG_AN_FUSED=0: the per-layer launch sequence of rounds 1-3 (the fused kernels' bit-exact counterpart: tests compare the
-// two); SG_AN_SLICES=n: n time slices per utterance instead of the planner's choice.  Read per call (tests flip them).
-bool an_use_fused(sg_ctx* ctx, int rows, int Fnet) {
-    const char* e = sg_tune_env("SG_AN_FUSED");
-    if (e && atoi(e) == 0) return false;
-    const AnWorkspace& w = ctx->an_ws;
-    return an_fused_supported(w.Tin, w.Tout, Fnet, rows, ctx->num_cus);
+// the launch-form knobs of this call (AnKnobs, sg_internal.h)
+AnKnobs an_knobs() {
+    AnKnobs k;
+    const char* e;
+    if ((e = sg_tune_env("SG_AN_FUSED"))) k.fused = atoi(e) != 0;
+    if ((e = sg_tune_env("SG_AN_HEAD"))) k.head = atoi(e) != 0;
+    if ((e = sg_tune_env("SG_AN_ONE"))) k.one = atoi(e) != 0;
+    if ((e = sg_tune_env("SG_AN_SLICES"))) k.slices = atoi(e);
+    return k;
 }
-int an_forced_slices() {
-    const char* e = sg_tune_env("SG_AN_SLICES");
-    return e ? atoi(e) : 0;
+// rows x Fnet frames through the network; Fnet is the frame count the network sees (the front-end's, or the number of FeCo
+// clusters when the defense sits between front-end and network)
+AnNetPlan an_plan(sg_ctx* ctx, const AnKnobs& k, int rows, int Fnet, bool want_grad) {
+    return an_net_plan(k, rows, Fnet, ctx->num_cus, k.fused && an_fused_device_ok(), want_grad);
 }
-AnFusedArgs an_fused_args(sg_ctx* ctx, int Fnet) {
+
+AnFusedArgs an_fused_args(sg_ctx* ctx, const AnNetPlan& p) {
     AnWorkspace& w = ctx->an_ws;
     const AnModel& m = ctx->an;
     AnFusedArgs a{};
@@ -349,37 +334,18 @@ AnFusedArgs an_fused_args(sg_ctx* ctx, int Fnet) {
         a.act[l] = w.act[l];
         a.pool[l] = w.pool[l];
         a.bias[l] = m.bias[l];
-        a.Tin[l] = w.Tin[l];
-        a.Tout[l] = w.Tout[l];
+        a.Tin[l] = p.Tin[l];
+        a.Tout[l] = p.Tout[l];
     }
     a.w25 = m.w25;
     a.pre_bias = m.pre_bias;
-    a.Fnet = Fnet;
+    a.Fnet = p.Fnet;
     return a;
 }
 
-// Where the network's head runs (round 6).  Default: inside the fused backward launch whenever a gradient follows (every
-// block computes its utterance's head: no an_tail launch, no d conv8 round trip) -- 3-5 % of a feature-level pass
-// (tools/an_head_ab.py: 188 -> 182 us at 64 utterances, 702 -> 665 at 512), neutral inside the device loops
-// (tools/an_head_loop_ab.py).  Forward + head + backward of whole utterances as ONE launch (S = 1) exists and is bit-equal,
-// but measured 3.5 % SLOWER inside the PGD loop at 256 / 512 utterances (profiles/r06_an_head_ab.txt): off unless
-// SG_AN_ONE=1.  SG_AN_HEAD=0 brings the separate an_tail launch back (both knobs behind SG_TUNE=1; the tests compare the
-// three forms bit for bit).
-static bool an_head_in_backward(sg_ctx* ctx, int rows, int Fnet) {
-    const char* e = sg_tune_env("SG_AN_HEAD");
-    if (e && atoi(e) == 0) return false;
-    return an_use_fused(ctx, rows, Fnet);
-}
-static bool an_one_launch(sg_ctx* ctx, int rows, int Fnet) {
-    const char* e = sg_tune_env("SG_AN_ONE");
-    if (!e || atoi(e) == 0) return false;
-    if (!an_head_in_backward(ctx, rows, Fnet)) return false;
-    AnWorkspace& w = ctx->an_ws;
-    an_layer_frames(Fnet, w.Tin, w.Tout);
-    return an_fused_slices(w.Tin, w.Tout, Fnet, rows, ctx->num_cus, an_forced_slices()) == 1;
-}
-static AnHeadArgs an_head_args(sg_ctx* ctx, const int64_t* y, const sg_loss_spec& ls, int coef_rows, float* scores, int64_t* decisions,
-                               float* loss, float* loss_trace, int64_t* dec_trace, uint8_t* success) {
+// what the head computes and where it writes, whichever launch runs it (an_tail, the fused backward, the one launch)
+AnHeadArgs an_head_args(sg_ctx* ctx, const int64_t* y, const sg_loss_spec& ls, int coef_rows, float* emb, float* scores, int64_t* decisions,
+                        float* loss, float* loss_trace, int64_t* dec_trace, uint8_t* success) {
     AnHeadArgs h{};
     h.on = 1;
     h.fc_w = ctx->an.fc_w;
@@ -389,6 +355,7 @@ static AnHeadArgs an_head_args(sg_ctx* ctx, const int64_t* y, const sg_loss_spec
     h.y = y;
     h.ls = ls;
     h.coef_rows = coef_rows;
+    h.emb_out = emb;
     h.scores_out = scores;
     h.dec_out = decisions;
     h.loss_out = loss;
@@ -398,43 +365,26 @@ static AnHeadArgs an_head_args(sg_ctx* ctx, const int64_t* y, const sg_loss_spec
     return h;
 }
 
-// features -> conv stack -> head -> d loss / d features, one launch (an_one_launch said yes)
-int an_net_forward_backward(sg_ctx* ctx, const float* feats, int B, int Fnet, const AnHeadArgs& head, float* dfeats_out, hipStream_t s) {
+// features (rows, Fnet, 32) -> conv stack
+int an_net_forward(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int B, hipStream_t s) {
     AnWorkspace& w = ctx->an_ws;
     const AnModel& m = ctx->an;
-    an_layer_frames(Fnet, w.Tin, w.Tout);
-    AnFusedArgs a = an_fused_args(ctx, Fnet);
-    a.feats = feats;
-    a.dfeats = dfeats_out;
-    a.head = head;
-    for (int l = 0; l < kAnConv; ++l) {
-        a.wq[l] = m.wfq[l];
-        a.wq_bwd[l] = m.wbq[l];
-    }
-    AN_STAGE(SG_STAGE_AN_FUSED_FWDBWD, launch_an_cnn_fwdbwd(a, B, ctx->num_cus, an_forced_slices(), s));
-    return SG_OK;
-}
-
-int an_net_forward(sg_ctx* ctx, const float* feats, int B, int Fnet, hipStream_t s) {
-    AnWorkspace& w = ctx->an_ws;
-    const AnModel& m = ctx->an;
-    an_layer_frames(Fnet, w.Tin, w.Tout);
-    if (an_use_fused(ctx, B, Fnet)) {
-        AnFusedArgs a = an_fused_args(ctx, Fnet);
+    if (p.form != AN_PER_LAYER) {
+        AnFusedArgs a = an_fused_args(ctx, p);
         a.feats = feats;
         for (int l = 0; l < kAnConv; ++l) a.wq[l] = m.wfq[l];
-        AN_STAGE(SG_STAGE_AN_FUSED_FWD, launch_an_cnn_fused(a, B, ctx->num_cus, false, an_forced_slices(), s));
+        AN_STAGE(SG_STAGE_AN_FUSED_FWD, launch_an_cnn_fused(a, p, B, false, s));
         return SG_OK;
     }
-    AN_STAGE(SG_STAGE_AN_PREFILTER_FWD, launch_an_prefilter(feats, w.pre, B, Fnet, m.w25, m.pre_bias, 0, s));
+    AN_STAGE(SG_STAGE_AN_PREFILTER_FWD, launch_an_prefilter(feats, w.pre, B, p.Fnet, m.w25, m.pre_bias, 0, s));
     for (int l = 0; l < kAnConv; ++l) {
         ConvGemmArgs a{};
         a.A = an_layer_input(w, l);
         a.W = m.wf[l];
         a.C = w.act[l];
         a.bias = m.bias[l];
-        a.Ta = w.Tin[l];
-        a.Tc = w.Tout[l];
+        a.Ta = p.Tin[l];
+        a.Tc = p.Tout[l];
         a.M = B * a.Tc;
         a.N = kAnCout[l];
         a.Kc = kAnCin[l];
@@ -448,34 +398,26 @@ int an_net_forward(sg_ctx* ctx, const float* feats, int B, int Fnet, hipStream_t
         a.chunks_per_split = a.total_chunks;
         a.Wq = a.N % 128 == 0 ? m.wfq[l] : nullptr;
         AN_STAGE(SG_STAGE_AN_CONV_FWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, EPI_BIAS_RELU, 1, s));
-        if (kAnPool[l]) AN_STAGE(SG_STAGE_AN_POOL_FWD, launch_an_pool_fwd(w.act[l], w.pool[l], B, w.Tout[l], kAnCout[l], s));
+        if (kAnPool[l]) AN_STAGE(SG_STAGE_AN_POOL_FWD, launch_an_pool_fwd(w.act[l], w.pool[l], B, p.Tout[l], kAnCout[l], s));
     }
     return SG_OK;
 }
 
-int an_forward_net(sg_ctx* ctx, const float* x, const AnDims& d, int flag, hipStream_t s) {
-    const float* feats = x;
-    if (flag == 0) {
-        int rc = an_frontend_forward(ctx, x, d, s);
-        if (rc) return rc;
-        feats = ctx->an_ws.feats;
-    }
-    return an_net_forward(ctx, feats, d.B, d.F, s);
-}
-
-// d loss / d conv8 pre-activation (ws.dact[6]) -> d loss / d features (B, Fnet, 32) in dfeats_out
-int an_net_backward(sg_ctx* ctx, int B, int Fnet, float* dfeats_out, hipStream_t s, const AnHeadArgs* head = nullptr) {
+// d loss / d conv8 pre-activation (ws.dact[6], or the head inside the launch) -> d loss / d features (rows, Fnet, 32)
+int an_net_backward(sg_ctx* ctx, const AnNetPlan& p, int B, const AnHeadArgs* head, float* dfeats_out, hipStream_t s) {
     AnWorkspace& w = ctx->an_ws;
     const AnModel& m = ctx->an;
-    if (an_use_fused(ctx, B, Fnet)) {
-        AnFusedArgs a = an_fused_args(ctx, Fnet);
+    if (p.form != AN_PER_LAYER) {
+        AnFusedArgs a = an_fused_args(ctx, p);
         a.dtop = w.dact[kAnConv - 1];
         a.dfeats = dfeats_out;
         if (head) a.head = *head;
         for (int l = 0; l < kAnConv; ++l) a.wq[l] = m.wbq[l];
-        AN_STAGE(SG_STAGE_AN_FUSED_BWD, launch_an_cnn_fused(a, B, ctx->num_cus, true, an_forced_slices(), s));
+        AN_STAGE(SG_STAGE_AN_FUSED_BWD, launch_an_cnn_fused(a, p, B, true, s));
         return SG_OK;
     }
+    // (the plan puts the head into a launch only in a fused form: nobody would have written dact[6])
+    if (head) return an_fail(ctx, SG_ERR_STATE, "AudioNet: the per-layer backward cannot run the head");
     for (int l = kAnConv - 1; l >= 0; --l) {
         // data gradient of conv l: reads dact[l] (B, Tout, Cout), writes the gradient of its input
         const bool in_pooled = l > 0 && kAnPool[l - 1];
@@ -484,8 +426,8 @@ int an_net_backward(sg_ctx* ctx, int B, int Fnet, float* dfeats_out, hipStream_t
         a.W = m.wb[l];
         a.C = l == 0 ? w.dpre : (in_pooled ? w.dpool[l - 1] : w.dact[l - 1]);
         a.mask = (l == 0 || in_pooled) ? nullptr : w.act[l - 1];
-        a.Ta = w.Tout[l];
-        a.Tc = w.Tin[l];
+        a.Ta = p.Tout[l];
+        a.Tc = p.Tin[l];
         a.M = B * a.Tc;
         a.N = kAnCin[l];
         a.Kc = kAnCout[l];
@@ -500,9 +442,53 @@ int an_net_backward(sg_ctx* ctx, int B, int Fnet, float* dfeats_out, hipStream_t
         a.Wq = a.N % 128 == 0 ? m.wbq[l] : nullptr;
         AN_STAGE(SG_STAGE_AN_CONV_BWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, a.mask ? EPI_RELU_MASK : EPI_NONE, 1, s));
         if (in_pooled)
-            AN_STAGE(SG_STAGE_AN_POOL_BWD, launch_an_pool_bwd(w.act[l - 1], w.dpool[l - 1], w.dact[l - 1], B, w.Tout[l - 1], kAnCout[l - 1], s));
+            AN_STAGE(SG_STAGE_AN_POOL_BWD, launch_an_pool_bwd(w.act[l - 1], w.dpool[l - 1], w.dact[l - 1], B, p.Tout[l - 1], kAnCout[l - 1], s));
     }
-    AN_STAGE(SG_STAGE_AN_PREFILTER_BWD, launch_an_prefilter(w.dpre, dfeats_out, B, Fnet, m.w25, 0.f, 1, s));
+    AN_STAGE(SG_STAGE_AN_PREFILTER_BWD, launch_an_prefilter(w.dpre, dfeats_out, B, p.Fnet, m.w25, 0.f, 1, s));
+    return SG_OK;
+}
+
+// the per-row records of a step that ran R EOT repeats, reduced to per-utterance ones right after the head (null: none)
+struct AnEotRecords {
+    int R, B;
+    float* loss_out;
+    int64_t* dec_out;
+};
+
+// One pass through the network by the plan's form: forward, head, and -- where dfeats_out is given -- backward to
+// d loss / d features.  Leaves the pass's frame counts in the workspace (sg_an_debug_activation).
+int an_net_step(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int rows, const AnHeadArgs& head, const AnEotRecords* eot,
+                float* dfeats_out, hipStream_t s) {
+    AnWorkspace& w = ctx->an_ws;
+    const AnModel& m = ctx->an;
+    const int L = kAnConv - 1;
+    const bool head_inside = p.form == AN_FUSED_HEAD || p.form == AN_ONE_LAUNCH;
+    if (head_inside && !dfeats_out) return an_fail(ctx, SG_ERR_STATE, "AudioNet: a plan with the head inside the backward needs a gradient target");
+    std::copy(p.Tin, p.Tin + kAnConv, w.Tin);
+    std::copy(p.Tout, p.Tout + kAnConv, w.Tout);
+    int rc;
+    if (p.form == AN_ONE_LAUNCH) {
+        AnFusedArgs a = an_fused_args(ctx, p);
+        a.feats = feats;
+        a.dfeats = dfeats_out;
+        a.head = head;
+        for (int l = 0; l < kAnConv; ++l) {
+            a.wq[l] = m.wfq[l];
+            a.wq_bwd[l] = m.wbq[l];
+        }
+        AN_STAGE(SG_STAGE_AN_FUSED_FWDBWD, launch_an_cnn_fwdbwd(a, p, rows, s));
+    } else {
+        if ((rc = an_net_forward(ctx, p, feats, rows, s))) return rc;
+        if (head_inside) {
+            if ((rc = an_net_backward(ctx, p, rows, &head, dfeats_out, s))) return rc;
+        } else {
+            AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], rows, p.Tout[L], head.fc_w, head.fc_b, head.S, head.threshold, head.y, head.ls,
+                                                      dfeats_out != nullptr, head.emb_out, head.scores_out, head.dec_out, head.loss_out, w.dact[L],
+                                                      head.loss_trace, head.dec_trace, head.success, s, head.coef_rows));
+        }
+    }
+    if (eot) AN_HIP(launch_eot_trace_reduce(head.loss_trace, head.dec_trace, eot->R, eot->B, eot->loss_out, eot->dec_out, s));
+    if (dfeats_out && !head_inside) return an_net_backward(ctx, p, rows, nullptr, dfeats_out, s);
     return SG_OK;
 }
 
@@ -548,15 +534,6 @@ float* an_step_target(sg_ctx* ctx, const AnDims& d) {
         w.x_alt = static_cast<float*>(p);
     }
     return w.x_alt;
-}
-
-int an_backward_net(sg_ctx* ctx, const float* x, const AnDims& d, int flag, float* grad_out, float* x_update, float* x_next,
-                    const float* lower, const float* upper, float step, int grad_sign, hipStream_t s, const AnHeadArgs* head = nullptr,
-                    bool net_done = false) {
-    AnWorkspace& w = ctx->an_ws;
-    int rc = net_done ? SG_OK : an_net_backward(ctx, d.B, d.F, flag == 1 ? grad_out : w.dfeats, s, head);
-    if (rc || flag == 1) return rc;
-    return an_frontend_backward(ctx, x, d, w.dfeats, grad_out, x_update, x_next, lower, upper, step, grad_sign, s);
 }
 
 }  // namespace
@@ -695,12 +672,14 @@ int sg_an_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, in
     if (rc) return rc;
     if (!x_dev) return an_fail(ctx, SG_ERR_ARG, "x is NULL");
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = an_forward_net(ctx, x_dev, d, flag, s))) return rc;
-    AnWorkspace& w = ctx->an_ws;
-    sg_loss_spec none{};
-    AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[kAnConv - 1], B, w.Tout[kAnConv - 1], ctx->an.fc_w, ctx->an.fc_b, ctx->an.S, -INFINITY, nullptr,
-                          none, 0, emb_dev, scores_dev, decisions_dev, nullptr, nullptr, nullptr, nullptr, nullptr, s));
-    return SG_OK;
+    const AnNetPlan plan = an_plan(ctx, an_knobs(), B, d.F, false);
+    const float* feats = x_dev;
+    if (flag == 0) {
+        if ((rc = an_frontend_forward(ctx, x_dev, d, s))) return rc;
+        feats = ctx->an_ws.feats;
+    }
+    const AnHeadArgs head = an_head_args(ctx, nullptr, sg_loss_spec{}, 0, emb_dev, scores_dev, decisions_dev, nullptr, nullptr, nullptr, nullptr);
+    return an_net_step(ctx, plan, feats, B, head, nullptr, nullptr, s);
 }
 
 int sg_an_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t capacity_floats, int32_t* rows_per_utt,
@@ -737,27 +716,16 @@ int sg_an_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
     if (loss->loss == SG_LOSS_LINEAR && !loss->coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
     hipStream_t s = (hipStream_t)stream;
     AnWorkspace& w = ctx->an_ws;
-    const int L = kAnConv - 1;
-    if (grad_dev && an_head_in_backward(ctx, B, d.F)) {
-        const AnHeadArgs head = an_head_args(ctx, y_dev, *loss, 0, scores_dev, decisions_dev, loss_dev, nullptr, nullptr, nullptr);
-        if (an_one_launch(ctx, B, d.F)) {
-            const float* feats = x_dev;
-            if (flag == 0) {
-                if ((rc = an_frontend_forward(ctx, x_dev, d, s))) return rc;
-                feats = w.feats;
-            }
-            if ((rc = an_net_forward_backward(ctx, feats, B, d.F, head, flag == 1 ? grad_dev : w.dfeats, s))) return rc;
-            return an_backward_net(ctx, x_dev, d, flag, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s, nullptr, true);
-        }
-        if ((rc = an_forward_net(ctx, x_dev, d, flag, s))) return rc;
-        return an_backward_net(ctx, x_dev, d, flag, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s, &head);
+    const AnNetPlan plan = an_plan(ctx, an_knobs(), B, d.F, grad_dev != nullptr);
+    const float* feats = x_dev;
+    if (flag == 0) {
+        if ((rc = an_frontend_forward(ctx, x_dev, d, s))) return rc;
+        feats = w.feats;
     }
-    if ((rc = an_forward_net(ctx, x_dev, d, flag, s))) return rc;
-    AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], B, w.Tout[L], ctx->an.fc_w, ctx->an.fc_b, ctx->an.S, -INFINITY, y_dev, *loss,
-                          grad_dev != nullptr, nullptr, scores_dev, decisions_dev, loss_dev, w.dact[L], nullptr, nullptr,
-                          nullptr, s));
-    if (grad_dev) return an_backward_net(ctx, x_dev, d, flag, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s);
-    return SG_OK;
+    const AnHeadArgs head = an_head_args(ctx, y_dev, *loss, 0, nullptr, scores_dev, decisions_dev, loss_dev, nullptr, nullptr, nullptr);
+    float* dfeats = !grad_dev ? nullptr : flag == 1 ? grad_dev : w.dfeats;
+    if ((rc = an_net_step(ctx, plan, feats, B, head, nullptr, dfeats, s)) || !grad_dev || flag == 1) return rc;
+    return an_frontend_backward(ctx, x_dev, d, w.dfeats, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s);
 }
 
 int sg_an_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
@@ -771,43 +739,25 @@ int sg_an_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
     hipStream_t s = (hipStream_t)stream;
     AnWorkspace& w = ctx->an_ws;
-    const int L = kAnConv - 1;
+    const AnKnobs knobs = an_knobs();
+    const AnNetPlan step_plan = an_plan(ctx, knobs, B, d.F, true), final_plan = an_plan(ctx, knobs, B, d.F, false);
     // the fused overlap-add steps from one waveform buffer into another: the iterate alternates between the caller's
     // buffer and a workspace twin and is copied home once if the attack ends on the twin
     float* xc = x_adv_dev;
     float* xn = an_step_target(ctx, d);
     if (!xn) xn = x_adv_dev;
     for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;
+        const bool last = it == p->max_iter;  // the final pass is a single forward
         d.keep_scale = it > 0;  // iterates stay in [-1, 1]
-        if (!last && an_head_in_backward(ctx, B, d.F)) {
-            // a gradient step: the head runs inside the backward launch (whole utterances per block: inside the one launch)
-            const AnHeadArgs head = an_head_args(ctx, y_dev, p->loss, 0, nullptr, nullptr, nullptr,
-                                                 loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
-                                                 decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr, nullptr);
-            if (an_one_launch(ctx, B, d.F)) {
-                if ((rc = an_frontend_forward(ctx, xc, d, s))) return rc;
-                if ((rc = an_net_forward_backward(ctx, w.feats, B, d.F, head, w.dfeats, s))) return rc;
-                rc = an_backward_net(ctx, xc, d, 0, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s, nullptr, true);
-            } else {
-                if ((rc = an_forward_net(ctx, xc, d, 0, s))) return rc;
-                rc = an_backward_net(ctx, xc, d, 0, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s, &head);
-            }
-            if (rc) return rc;
-            if (xn != xc) std::swap(xc, xn);
-            continue;
-        }
-        if ((rc = an_forward_net(ctx, xc, d, 0, s))) return rc;
-        AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], B, w.Tout[L], ctx->an.fc_w, ctx->an.fc_b, ctx->an.S, -INFINITY, y_dev, p->loss, !last,
-                              nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr, last ? loss_dev : nullptr,
-                              w.dact[L], loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
-                              decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr,
-                              last ? success_dev : nullptr, s));
-        if (!last) {
-            rc = an_backward_net(ctx, xc, d, 0, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s);
-            if (rc) return rc;
-            if (xn != xc) std::swap(xc, xn);
-        }
+        if ((rc = an_frontend_forward(ctx, xc, d, s))) return rc;
+        const AnHeadArgs head = an_head_args(ctx, y_dev, p->loss, 0, nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr,
+                                             last ? loss_dev : nullptr, loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
+                                             decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr, last ? success_dev : nullptr);
+        if ((rc = an_net_step(ctx, last ? final_plan : step_plan, w.feats, B, head, nullptr, last ? nullptr : w.dfeats, s))) return rc;
+        if (last) break;
+        rc = an_frontend_backward(ctx, xc, d, w.dfeats, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s);
+        if (rc) return rc;
+        if (xn != xc) std::swap(xc, xn);
     }
     if (xc != x_adv_dev) AN_HIP(hipMemcpyAsync(x_adv_dev, xc, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SG_OK;
@@ -840,12 +790,14 @@ int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
     if (rc) return rc;
     d.B = B;
     const int k = f->k;
-    int Tin[kAnConv], Tout[kAnConv];
-    if (k < 1 || k > d.F || f->max_iter < 1 || !an_layer_frames(k, Tin, Tout))
+    // the network sees k frames in every pass, the first one included: R x B rows at a gradient step, B at the final forward
+    const AnKnobs knobs = an_knobs();
+    const bool k_ok = k >= 1 && k <= d.F && f->max_iter >= 1;
+    const AnNetPlan step_plan = an_plan(ctx, knobs, B * reps, k_ok ? k : 0, true), final_plan = an_plan(ctx, knobs, B, k_ok ? k : 0, false);
+    if (!final_plan.frames_ok)
         return an_fail(ctx, SG_ERR_ARG, "FeCo: need 1 <= k <= %d frames, enough of them for the AudioNet stack, max_iter >= 1", d.F);
     hipStream_t s = (hipStream_t)stream;
     AnWorkspace& w = ctx->an_ws;
-    const int L = kAnConv - 1;
     for (int r = 0; r < reps; ++r)
         AN_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     float* xc = x_adv_dev;  // waveform ping-pong of the fused overlap-add (sg_an_pgd_run)
@@ -864,29 +816,17 @@ int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
         trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 1);
         // per-step records as the reference prints them (attack/FGSM.py:50-58): the loss averaged over the step's EOT
         // repeats, the decision voted over them
-        const bool direct = R == 1, rec = loss_trace_dev || decision_trace_dev;
-        float* ltr = !rec ? nullptr : (direct && loss_trace_dev ? loss_trace_dev + (size_t)it * B : w.trace_l);
-        int64_t* dtr = !rec ? nullptr : (direct && decision_trace_dev ? decision_trace_dev + (size_t)it * B : w.trace_d);
-        const bool head_in = !last && an_head_in_backward(ctx, rows, k);
-        if (head_in) {  // the head inside the backward launch (or forward + head + backward as one launch)
-            const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, nullptr, nullptr, ltr, dtr, nullptr);
-            if (an_one_launch(ctx, rows, k)) {
-                if ((rc = an_net_forward_backward(ctx, w.feco_out, rows, k, head, w.dfeco, s))) return rc;
-            } else {
-                if ((rc = an_net_forward(ctx, w.feco_out, rows, k, s))) return rc;
-                if ((rc = an_net_backward(ctx, rows, k, w.dfeco, s, &head))) return rc;
-            }
-        } else {
-            if ((rc = an_net_forward(ctx, w.feco_out, rows, k, s))) return rc;
-            AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], rows, w.Tout[L], ctx->an.fc_w, ctx->an.fc_b, ctx->an.S, -INFINITY, w.y_rep, p->loss, !last,
-                                  nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr, last ? loss_dev : nullptr,
-                                  w.dact[L], ltr, dtr, last ? success_dev : nullptr, s, B));
-        }
-        if (rec && !direct)
-            AN_HIP(launch_eot_trace_reduce(w.trace_l, w.trace_d, R, B, loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
-                                           decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr, s));
+        float* lrec = loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr;
+        int64_t* drec = decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr;
+        const bool direct = R == 1, rec = lrec || drec;
+        float* ltr = !rec ? nullptr : (direct && lrec ? lrec : w.trace_l);
+        int64_t* dtr = !rec ? nullptr : (direct && drec ? drec : w.trace_d);
+        const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr,
+                                             last ? loss_dev : nullptr, ltr, dtr, last ? success_dev : nullptr);
+        const AnEotRecords reduce = {R, B, lrec, drec};
+        rc = an_net_step(ctx, last ? final_plan : step_plan, w.feco_out, rows, head, rec && !direct ? &reduce : nullptr, last ? nullptr : w.dfeco, s);
+        if (rc) return rc;
         if (last) break;
-        if (!head_in && (rc = an_net_backward(ctx, rows, k, w.dfeco, s))) return rc;
         trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 0);
         if ((rc = sg_feco_compress_backward_reps(ctx, w.dfeco, w.feco_ids, w.feco_cnt, B, d.F, kAnMel, k, 1, R, w.dfeats, s))) return rc;
         trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 1);

@@ -50,6 +50,18 @@ constexpr int kAnPad[kAnConv] = {1, 1, 1, 1, 1, 1, 0};
 constexpr bool kAnPool[kAnConv] = {true, false, false, true, false, true, false};
 // torch.stft(center=True) on the pre-emphasised signal of T-1 samples: 1 + (T-1)/hop frames
 inline int an_num_frames(int T) { return T < kAnWin ? 0 : 1 + (T - 1) / kAnHop; }
+// frames entering / leaving every conv; false if the utterance is too short for conv8 (kernel 3, no pad)
+inline bool an_layer_frames(int F, int* Tin, int* Tout) {
+    int t = F;
+    for (int l = 0; l < kAnConv; ++l) {
+        Tin[l] = t;
+        Tout[l] = t + 2 * kAnPad[l] - 2;
+        if (Tout[l] < 1) return false;
+        t = kAnPool[l] ? Tout[l] / 2 : Tout[l];
+        if (t < 1) return false;
+    }
+    return Tin[kAnConv - 1] >= 3;
+}
 
 struct AnTables {            // device pointers
     float* window;           // [800] periodic hann
@@ -77,7 +89,8 @@ struct AnTables {            // device pointers
 };
 // how the AudioNet front-end runs (sg_an_configure)
 struct AnFrontCfg {
-    // defaults = the fastest measured combination (profiles/r05_an_frontend_ab.txt)
+    // defaults: float32 transforms (the reference's precision); cache and overlap-add chosen by size, each where it measured
+    // faster (profiles/r06_an_frontend_ab.txt; an_use_spec_cache, an_ola_pays)
     int fft32 = 1;       // transforms in float32 (the reference's precision) or float64
     int spec_cache = -1;  // the forward keeps every frame's packed spectrum for the backward of the same pass: 1 / 0, -1 = by size
     int ola = -1;        // overlap-add (+ update) inside the log-mel adjoint: 1 / 0, -1 = where it pays (an_ola_pays: large batches)
@@ -115,7 +128,9 @@ struct AnModel {
 
 struct AnWorkspace {
     int B = 0, T = 0, F = 0;
-    int Tin[kAnConv] = {}, Tout[kAnConv] = {};  // frames entering / leaving each conv (before pooling)
+    // frames entering / leaving each conv (before pooling) of the LAST pass (an_net_step writes them): what
+    // sg_an_debug_activation reports.  No decision reads them.
+    int Tin[kAnConv] = {}, Tout[kAnConv] = {};
     float* scale = nullptr;
     float* feats = nullptr;    // (B, F, 32) log-mel
     float* pre = nullptr;      // (B, F, 32) pre-filter output
@@ -564,13 +579,39 @@ struct AnFusedArgs {
     unsigned long long* trace;  // tuning aid (SG_AN_TRACE): per block 16 timestamps (100 MHz) at the stage boundaries, or null
     AnHeadArgs head;
 };
-// false: the utterance is too long for the LDS-resident form even in its finest cut (the per-layer sequence runs)
-bool an_fused_supported(const int* Tin, const int* Tout, int Fnet, int rows, int num_cus);
-// force_slices > 0: that many time slices per utterance instead of the planner's choice (tests: same bits for any cut)
-hipError_t launch_an_cnn_fused(AnFusedArgs a, int rows, int num_cus, bool backward, int force_slices, hipStream_t s);
-// forward + head + backward of whole utterances in one launch; hipErrorNotSupported unless the planner's cut is S = 1
-hipError_t launch_an_cnn_fwdbwd(AnFusedArgs a, int rows, int num_cus, int force_slices, hipStream_t s);
-int an_fused_slices(const int* Tin, const int* Tout, int Fnet, int rows, int num_cus, int force_slices);  // the cut the fused launches use (0: not supported)
+// Which launches run the CNN of one pass.  Knobs (behind SG_TUNE=1, read once per entry-point call: the tests flip them):
+// SG_AN_FUSED=0: the per-layer launch sequence of rounds 1-3, the fused kernels' bit-exact counterpart; SG_AN_HEAD=0: the
+// head as a separate an_tail launch; SG_AN_ONE=1: forward + head + backward as one launch where whole utterances fit a
+// block; SG_AN_SLICES=n: n time slices per utterance instead of the planner's choice (same bits for any cut).
+struct AnKnobs {
+    bool fused = true, head = true, one = false;
+    int slices = 0;
+};
+enum AnForm {
+    AN_PER_LAYER,   // prefilter, 7 contractions, pools; an_tail; the same backwards
+    AN_FUSED_TAIL,  // an_cnn_fwd, an_tail, an_cnn_bwd
+    AN_FUSED_HEAD,  // an_cnn_fwd, an_cnn_bwd with the head inside (a gradient follows: no an_tail, no d conv8 round trip)
+    AN_ONE_LAUNCH,  // an_cnn_fwdbwd: whole utterances per block (S = 1)
+};
+struct AnNetPlan {
+    bool frames_ok;                   // enough frames for the stack (an_layer_frames)
+    int Fnet;                         // frames the network sees
+    int Tin[kAnConv], Tout[kAnConv];
+    AnForm form;
+    int S;                            // time slices per utterance (fused forms)
+    int buf_floats;                   // floats per LDS buffer: forward, and backward fed by an_tail
+    int buf_floats_head;              // ... of a launch with the head inside (its scratch lives in the second buffer)
+    bool small;                       // S >= 3: the kernels built for one 32-row tile per wave
+};
+// Pure: the whole decision from its arguments.  device_ok: the device grants the fused kernels their dynamic LDS
+// (an_fused_device_ok).  want_grad: a backward follows the head.
+AnNetPlan an_net_plan(const AnKnobs& knobs, int rows, int Fnet, int num_cus, bool device_ok, bool want_grad);
+// the > 64 KB dynamic-LDS opt-in of the fused kernels, made once per device; false: the device refuses it
+bool an_fused_device_ok();
+// S, buf_floats and the kernel build come from the plan; hipErrorNotSupported if the plan is not a fused form
+hipError_t launch_an_cnn_fused(AnFusedArgs a, const AnNetPlan& plan, int rows, bool backward, hipStream_t s);
+// forward + head + backward of whole utterances in one launch; hipErrorNotSupported unless the plan says AN_ONE_LAUNCH
+hipError_t launch_an_cnn_fwdbwd(AnFusedArgs a, const AnNetPlan& plan, int rows, hipStream_t s);
 hipError_t launch_an_logmel_fwd(const AnTables& t, const float* x, int B, int T, int F, const float* scale, float* feats,
                                 int fft32, hipStream_t s);
 hipError_t launch_an_logmel_bwd(const AnTables& t, const float* x, int B, int T, int F, const float* scale,

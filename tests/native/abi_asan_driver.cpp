@@ -9,6 +9,11 @@
 // double receives -- which kernel, which grid, which arguments.  No kernel runs, so the buffers are dummies.  The output
 // of every device / knob setting is recorded in tests/native/conv_launch_table.expected and tests/test_launch_table.py
 // compares byte for byte: a changed CHOICE of kernel, which gives the same bits on the GPU, shows here.
+//
+// `abi_asan_driver --an-sequence all|passes` is the third ("passes": without the sg_an_configure variants): it walks the
+// AudioNet entry points (sg_api_audionet.hip) and prints one line per launch of ANY kernel, in order, plus the planned
+// fields of AnFusedArgs for the fused CNN kernels -- the four launch forms of the CNN give the same bits too.  Recorded in
+// tests/native/an_launch_sequence.expected (tests/test_an_launch_sequence.py).
 #include <cxxabi.h>
 
 #include <algorithm>
@@ -220,8 +225,125 @@ static int launch_table(const std::string& mode) {
     return 0;
 }
 
+// ---- the AudioNet launch sequence --------------------------------------------------------------------------------
+static std::string g_an_label;
+static int g_an_n = 0;
+
+// "void sg::(anonymous namespace)::k<1, (sg::E)2>(args)" -> "k<1,(E)2>"
+static std::string kernel_name(const char* mangled) {
+    int status = 0;
+    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+    std::string name = dm ? dm : mangled;
+    std::free(dm);
+    for (const char* drop : {"(anonymous namespace)::", "sg::", "void "})
+        for (size_t at; (at = name.find(drop)) != std::string::npos;) name.erase(at, std::strlen(drop));
+    int depth = 0;
+    for (size_t i = 0; i < name.size(); ++i) {  // the parameter list opens at template depth 0
+        depth += name[i] == '<' ? 1 : name[i] == '>' ? -1 : 0;
+        if (name[i] == '(' && depth == 0) { name.resize(i); break; }
+    }
+    name.erase(std::remove(name.begin(), name.end(), ' '), name.end());
+    return name;
+}
+
+static void record_an_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void** args) {
+    const std::string name = kernel_name(mangled);
+    std::printf("%s #%d | %s grid=%u,%u,%u block=%u lds=%zu", g_an_label.c_str(), ++g_an_n, name.c_str(), grid.x, grid.y, grid.z,
+                block.x * block.y * block.z, shmem);
+    if (name.find("an_cnn_") == 0) {
+        const sg::AnFusedArgs& a = *static_cast<const sg::AnFusedArgs*>(args[0]);
+        std::printf(" S=%d buf_floats=%d Fnet=%d head=%d Tin=", a.S, a.buf_floats, a.Fnet, a.head.on);
+        for (int l = 0; l < sg::kAnConv; ++l) std::printf("%s%d", l ? "," : "", a.Tin[l]);
+        std::printf(" Tout=");
+        for (int l = 0; l < sg::kAnConv; ++l) std::printf("%s%d", l ? "," : "", a.Tout[l]);
+    }
+    std::printf("\n");
+}
+
+static void an_case(sg_ctx* ctx, const std::string& label, int rc) {
+    if (rc != SG_OK) std::printf("%s #%d | rc=%d %s\n", label.c_str(), ++g_an_n, rc, sg_last_error(ctx));
+}
+#define AN_CASE(label, call) (g_an_label = (label), g_an_n = 0, an_case(ctx, g_an_label, (call)))
+
+struct AnBuffers {  // "device" buffers of one (B, T) shape, sized as the header says
+    int B, T, F;
+    std::vector<float> x, g, sc, loss, ltr;
+    std::vector<int64_t> y, dec, dtr;
+    std::vector<uint8_t> succ;
+    AnBuffers(int B_, int T_, int S, int steps)
+        : B(B_), T(T_), F(sg_an_num_frames(T_)), x((size_t)B_ * T_), g((size_t)B_ * T_), sc((size_t)B_ * S), loss(B_),
+          ltr((size_t)(steps + 1) * B_), y(B_, 0), dec(B_), dtr((size_t)(steps + 1) * B_), succ(B_) {}
+};
+
+static void walk_an_passes(sg_ctx* ctx, AnBuffers& b, const std::string& tag, bool all) {
+    sg_loss_spec ce{};
+    sg_pgd_params pp{};
+    pp.step_size = 4e-4f; pp.max_iter = 2; pp.grad_sign = 1; pp.eot_size = 1; pp.eot_batch_size = 1;
+    const std::string at = " B=" + std::to_string(b.B) + " T=" + std::to_string(b.T) + tag;
+    if (all) {
+        AN_CASE("forward" + at, sg_an_forward(ctx, b.x.data(), b.B, b.T, 0, b.dec.data(), b.sc.data(), nullptr, nullptr));
+        AN_CASE("loss_grad flag=1" + at, sg_an_loss_grad(ctx, b.x.data(), b.y.data(), b.B, b.F, 1, &ce, b.dec.data(), b.sc.data(), b.loss.data(), b.g.data(), nullptr));
+        AN_CASE("loss_grad no grad" + at, sg_an_loss_grad(ctx, b.x.data(), b.y.data(), b.B, b.T, 0, &ce, b.dec.data(), b.sc.data(), b.loss.data(), nullptr, nullptr));
+    }
+    AN_CASE("loss_grad flag=0" + at, sg_an_loss_grad(ctx, b.x.data(), b.y.data(), b.B, b.T, 0, &ce, b.dec.data(), b.sc.data(), b.loss.data(), b.g.data(), nullptr));
+    AN_CASE("pgd_run" + at, sg_an_pgd_run(ctx, b.x.data(), b.y.data(), b.x.data(), b.x.data(), b.B, b.T, &pp, b.succ.data(), b.dec.data(), b.sc.data(),
+                                          b.loss.data(), b.ltr.data(), b.dtr.data(), nullptr));
+}
+
+static void walk_an_feco(sg_ctx* ctx, AnBuffers& b, int k, bool random_eot2, bool trace, const std::string& tag) {
+    sg_pgd_params pp{};
+    pp.step_size = 4e-4f; pp.max_iter = 2; pp.grad_sign = 1; pp.eot_size = random_eot2 ? 2 : 1; pp.eot_batch_size = 1;
+    sg_feco_params fp{};
+    fp.k = k; fp.max_iter = 3; fp.random_init = random_eot2; fp.seed = 5;
+    AN_CASE("pgd_run_feco B=" + std::to_string(b.B) + " T=" + std::to_string(b.T) + " k=" + std::to_string(k) + (random_eot2 ? " random eot=2" : " even") +
+                (trace ? " trace" : "") + tag,
+            sg_an_pgd_run_feco(ctx, b.x.data(), b.y.data(), b.x.data(), b.x.data(), b.B, b.T, &pp, &fp, b.succ.data(), b.dec.data(), b.sc.data(), b.loss.data(),
+                               trace ? b.ltr.data() : nullptr, trace ? b.dtr.data() : nullptr, nullptr));
+}
+
+// One context per shape: the workspace keeps the largest batch and the longest utterance it has seen, and the two extremes
+// below together would not fit the sanitizer build.
+static int an_sequence(bool configure) {
+    hipdouble_set_launch_hook(record_an_launch);
+    const int Sa = 11;
+    AnModel an(Sa);
+    // (B, T): three small / odd shapes, the benchmark's, a batch at which the planner cuts S = 1 by itself, and an utterance of
+    // 180 s that no cut fits (the per-layer sequence)
+    const int shapes[6][2] = {{3, 16000}, {5, 40000}, {64, 48000}, {256, 16000}, {1, 2880000}, {4, 16000}};
+    for (auto& bt : shapes) {
+        sg_ctx* ctx = nullptr;
+        if (sg_create(0, &ctx) != SG_OK || sg_an_load(ctx, &an.desc) != SG_OK) return 1;
+        AnBuffers b(bt[0], bt[1], Sa, 2);
+        if (b.B != 4) walk_an_passes(ctx, b, "", true);
+        if (b.B == 4)
+            for (int k : {30, b.F / 2})
+                for (int random_eot2 = 0; random_eot2 <= 1; ++random_eot2)
+                    for (int trace = 0; trace <= 1; ++trace) walk_an_feco(ctx, b, k, random_eot2, trace, "");
+        if (configure && (b.B == 3 || b.B == 64 || b.B == 4)) {  // the front-end's settings (sg_an_configure): its kernels are part of the sequence
+            const int cfgs[4][3] = {{32, -1, 0}, {32, -1, 1}, {32, 0, -1}, {64, -1, -1}};
+            for (auto& c : cfgs) {
+                if (sg_an_configure(ctx, c[0], c[1], c[2]) != SG_OK) return 1;
+                const std::string tag = " fft=" + std::to_string(c[0]) + " cache=" + std::to_string(c[1]) + " ola=" + std::to_string(c[2]);
+                if (b.B == 4) walk_an_feco(ctx, b, 30, false, false, tag);
+                else walk_an_passes(ctx, b, tag, false);
+            }
+        }
+        sg_destroy(ctx);
+    }
+    {   // FeCo where the front-end's frames and the k frames the network sees plan differently: 18000 frames fit no cut, 30 do
+        sg_ctx* ctx = nullptr;
+        if (sg_create(0, &ctx) != SG_OK || sg_an_load(ctx, &an.desc) != SG_OK) return 1;
+        AnBuffers b(2, 2880000, Sa, 2);
+        walk_an_feco(ctx, b, 30, false, true, "");
+        sg_destroy(ctx);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && std::string(argv[1]) == "--launch-table") return launch_table(argv[2]);
+    if (argc == 3 && std::string(argv[1]) == "--an-sequence") return an_sequence(std::string(argv[2]) == "all");
+    setenv("SG_TUNE", "1", 1);  // the knobs this walk sets (SG_EOT_MAX_ROWS, SG_AN_SLICES, SG_AN_FUSED) count only behind it
     // ---- no context ------------------------------------------------------------------------------------------
     EXPECT(sg_version() == 100);
     EXPECT(sg_xv_num_frames(48000) == 300 && sg_xv_num_frames(100) == 0 && sg_an_num_frames(48000) == 300);

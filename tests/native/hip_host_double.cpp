@@ -8,7 +8,9 @@
 // counters, and a kernel launch is counted, shown to the launch hook (if one is set) and otherwise ignored -- no
 // kernel arithmetic runs here, GPU results are the business of `pytest -m gpu`.  Runs in the GPU-less build container.
 // The device the double plays can be resized from the environment, read at every query: HIPDOUBLE_CUS (compute units,
-// default 256) and HIPDOUBLE_OCCUPANCY (the answer to hipOccupancyMaxActiveBlocksPerMultiprocessor, default 2).
+// default 256), HIPDOUBLE_OCCUPANCY (the answer to hipOccupancyMaxActiveBlocksPerMultiprocessor, default 2) and
+// HIPDOUBLE_REFUSE_LDS=1 (hipFuncSetAttribute refuses a request for 160 KB or more: a device whose blocks cannot have the whole
+// LDS of a gfx950 CU, which the fused AudioNet kernels ask for).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -97,7 +99,9 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     return hipSuccess;
 }
 
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int value) {
+    return value >= 160 * 1024 && env_int("HIPDOUBLE_REFUSE_LDS", 0) ? hipErrorInvalidValue : hipSuccess;
+}
 hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, const void*, int, size_t) {
     *n = env_int("HIPDOUBLE_OCCUPANCY", 2);
     return hipSuccess;

@@ -374,6 +374,47 @@ def test_pgd_loops_with_the_head_inside_equal_the_separate_launches(hip, dev, mo
     monkeypatch.delenv("SG_AN_ONE", raising=False)
 
 
+@pytest.mark.parametrize("init,eot", [("even", 1), ("random", 2)])
+def test_feco_loop_with_the_head_inside_equals_the_separate_launches(hip, dev, monkeypatch, init, eot):
+    """The FeCo device loop (sg_an_pgd_run_feco: the network sees k = 30 cluster frames, the front-end 100) under the three
+    head forms -- separate an_tail (SG_AN_HEAD=0), head inside the backward (default), one launch (SG_AN_ONE=1
+    SG_AN_SLICES=1): adversarial audio, success flags, final decisions, scores and the per-step loss / decision records are
+    equal.  The stage trace names the form: the final pass is a forward + an_tail in every form, so an_tail runs at the
+    gradient steps (max_iter + 1 times in all) only in the first, and an_cnn_fwdbwd (once per step) only in the last."""
+    from speakerguard_amd import _native as N
+    from speakerguard_amd import synth
+    from speakerguard_amd.attack.utils import SEC4SR_CrossEntropy
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    B, T, K = 4, 16000, 3
+    x = torch.from_numpy(synth.make_waveforms(B, T, seed=173)).to(dev)
+    y = hip.make_decision(x)[0]
+    lower, upper = torch.clamp(x - 0.002, min=-1), torch.clamp(x + 0.002, max=1)
+    assert int(N.load().sg_an_num_frames(T) * 0.3) == 30
+
+    def run():
+        hip.begin_batch()  # the same generator key for every form
+        feco = FeCoDefense(0.3, max_iter=3, init=init, seed=7)
+        out = hip.pgd_run_feco(x, y, lower, upper, SEC4SR_CrossEntropy(), 0.0004, K, 1, feco, eot_size=eot, eot_batch_size=eot, trace=True)
+        return [t.clone() for t in out]
+
+    forms = (dict(SG_AN_HEAD="0"), dict(), dict(SG_AN_ONE="1", SG_AN_SLICES="1"))
+    ref = None
+    for i, knobs in enumerate(forms):
+        for k, v in knobs.items():
+            monkeypatch.setenv(k, v)
+        got = run()
+        tags = [t for t, _ in hip.trace_stages(run, max_records=1024)]
+        for k in knobs:
+            monkeypatch.delenv(k)
+        assert tags.count("an_tail") == (K + 1 if i == 0 else 1), (knobs, tags)
+        assert tags.count("an_cnn_fwdbwd") == (K if i == 2 else 0), (knobs, tags)
+        if ref is None:
+            ref = got
+        for name, a, b in zip(("x_adv", "success", "decisions", "scores", "loss", "loss trace", "decision trace"), got, ref):
+            assert torch.equal(a, b), (knobs, name)
+    assert not torch.equal(ref[0], x)  # the attack moved the audio
+
+
 def test_fused_cnn_is_the_path_that_runs(hip, dev, monkeypatch):
     """The stage trace names what ran: one fused launch per direction and no per-layer contraction with the default
     setting; the per-layer tags with SG_AN_FUSED=0."""
