@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced.  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* are (tags 60, 61).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -389,6 +389,10 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 #define SG_STAGE_AN_FUSED_FWD 50 /* the whole conv stack of a pass in one launch (round 4) */
 #define SG_STAGE_AN_FUSED_BWD 51 /* (round 6: with the network's head inside, when a gradient follows) */
 #define SG_STAGE_AN_FUSED_FWDBWD 52 /* forward + head + backward of whole utterances in one launch (round 6) */
+/* time-domain input defenses (sg_wav_defense_forward / _backward below: traced although they are per-stage entry points,
+ * because a defended attack step is the model's pass sequence plus exactly these launches) */
+#define SG_STAGE_TD_FWD 60
+#define SG_STAGE_TD_BWD 61
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -501,6 +505,54 @@ int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
                        const float* upper_dev, int32_t B, int32_t T, const sg_pgd_params* params,
                        const sg_feco_params* feco, uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev,
                        float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev, void* stream);
+
+/* ---- time-domain input defenses (defense/time_domain.py) -----------------------------------------------------
+ * The reference's waveform-level transforms and their gradients, x / out / g / gx all (B,T) float32 on the device, one
+ * utterance per row, 1 <= B <= 65535.  Every output value is one fixed sequence of float32 operations that depends neither
+ * on B nor on how a batch is cut into calls (the sequences: csrc/k_time_domain.hip header, restated in
+ * tests/time_domain_restate.py).  Both calls are stream-ordered, allocate nothing and never synchronise.
+ *   SG_TD_QT  :10-44 quantisation, param = q > 0: out = rint(x*s / q) * q / s, rint = round half to even, IEEE divisions.
+ *             saved_dev = ONE device float s, an INPUT: sg_input_scale(x, B*T) writes it first (32768 if the whole call lies
+ *             in [-1,1], else 1 -- the reference decides per call, :31, so QT alone couples the rows of a call).  BDR
+ *             (:46-48) is QT with q = 2^(bits - param), computed by the caller.  Backward: the identity (BPDA, :44) -- gx_dev
+ *             may alias g_dev, and then nothing is launched.
+ *   SG_TD_AS  :72-97 average smoothing, param = window k (odd, 1 <= k <= 31): out[t] = sum_j w xpad[t + j - (k-1)/2],
+ *             w = float32(1/k), zero padding, one fmaf chain in tap order.  saved_dev unused (NULL).  The operator is
+ *             symmetric: backward = forward applied to g.
+ *   SG_TD_MS  :100-127 median smoothing, param = window k (odd, 1 <= k <= 31), zero padding: out[t] = the window element of
+ *             rank (k-1)/2 under the order (value, window position) -- torch.median's value; the tie rule is ours.
+ *             saved_dev = (B,T) int8, written by the forward: window offset of the selected element, -(k-1)/2 .. (k-1)/2.
+ *             Backward: gx[i] = sum over t ascending, |t - i| <= (k-1)/2, of g[t] [sel[t] == i - t] (what autograd does for
+ *             torch.median(dim): scatter to the returned index); cotangents selected onto a pad entry are dropped.
+ *   SG_TD_AT  :50-70 additive noise at param dB SNR: P[b] = sum_t (x[b,t] / sqrt(T))^2, sigma[b] = sqrt(P[b] / 10^(param/10)),
+ *             out = x + n sigma[b].  n = noise_dev (B,T) when given (parity tests), else unit normals from Philox4x32-10,
+ *             regenerated by the backward, never stored: key and utterance of row b derive from seed, index_base, row_base,
+ *             rep_rows exactly as sg_dither documents; counter = (sample t, 0xA7000000, utterance lo, utterance hi), Box-Muller
+ *             on output words 0 and 1 like sg_nes_queries.  Counter word 1 holds the frame (< 2^31 / 160) in the dither's
+ *             stream and the pair index in the NES stream: the three never share a counter.
+ *             saved_dev = (3,B) floats: sigma and P written by the forward, row 2 the backward's workspace.
+ *             Backward (needs x_dev): gx[b,j] = g[b,j] + x[b,j] / (T 10^(param/10) sigma[b]) * sum_t g[b,t] n[b,t] -- exact
+ *             autograd of the reference, whose noise power depends on x.  DEVIATION: for a silent utterance (P[b] == 0) the
+ *             reference's gradient is NaN; here the second term is defined as 0, gx = g.
+ * SG_ERR_ARG for anything else (even or too long windows, q <= 0, unknown kind, missing saved_dev). */
+#define SG_TD_QT 0
+#define SG_TD_AS 1
+#define SG_TD_MS 2
+#define SG_TD_AT 3
+typedef struct sg_wav_defense {
+    int32_t kind;       /* SG_TD_* */
+    float param;        /* q | window | window | SNR in dB */
+    uint64_t seed;      /* AT only, like sg_dither: */
+    int64_t index_base;
+    int64_t row_base;
+    int32_t rep_rows;
+    const float* noise_dev;
+} sg_wav_defense;
+int sg_wav_defense_forward(sg_ctx* ctx, const sg_wav_defense* d, const float* x_dev, int32_t B, int32_t T, float* out_dev,
+                           void* saved_dev, void* stream);
+/* x_dev: the forward's input (read by AT only, may be NULL otherwise) */
+int sg_wav_defense_backward(sg_ctx* ctx, const sg_wav_defense* d, const float* x_dev, const float* g_dev, void* saved_dev,
+                            int32_t B, int32_t T, float* gx_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@ EXPORTS = (
     "sg_an_pgd_run", "sg_an_pgd_run_feco", "sg_conv1d_rows", "sg_wav_finalize", "sg_eer_threshold",
     "sg_xv_mfcc_backward", "sg_xv_cmvn_backward", "sg_feco_kmeans", "sg_feco_kmeans_seeded", "sg_feco_kmeans_compress", "sg_feco_compress_backward_reps", "sg_feco_compress", "sg_feco_compress_backward", "sg_feco_warped",
     "sg_an_logmel_backward", "sg_an_configure", "sg_xv_configure", "sg_xv_enroll_override", "sg_health", "sg_set_streamk", "sg_debug_lose_handoffs", "sg_debug_feco_epoch", "sg_feco_set_two_cu", "sg_trace_begin", "sg_trace_end",
+    "sg_wav_defense_forward", "sg_wav_defense_backward",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -37,6 +38,8 @@ STAGE_NAMES.update({20: "an_logmel_fwd", 21: "an_prefilter_fwd", 22: "an_pool_fw
                     50: "an_cnn_fwd", 51: "an_cnn_bwd", 52: "an_cnn_fwdbwd"})
 STAGE_NAMES.update({30 + l: "an_conv%d_fwd" % (l + 2) for l in range(7)})
 STAGE_NAMES.update({40 + l: "an_conv%d_dgrad" % (l + 2) for l in range(7)})
+STAGE_NAMES.update({60: "td_fwd", 61: "td_bwd"})  # time-domain input defenses (SG_STAGE_TD_*)
+SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
 
 
 class NativeError(RuntimeError):
@@ -80,6 +83,11 @@ class PgdParams(C.Structure):
 class FecoParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("max_iter", C.c_int32), ("random_init", C.c_int32), ("seed", C.c_uint64),
                 ("index_base", C.c_int64)]
+
+
+class WavDefense(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("param", C.c_float), ("seed", C.c_uint64), ("index_base", C.c_int64),
+                ("row_base", C.c_int64), ("rep_rows", C.c_int32), ("noise_dev", C.c_void_p)]
 
 
 _lib = None
@@ -154,6 +162,8 @@ def load():
         "sg_feco_compress_backward_reps": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "sg_feco_compress": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "sg_feco_compress_backward": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "sg_wav_defense_forward": (C.c_int, [vp, C.POINTER(WavDefense), vp, i32, i32, vp, vp, vp]),
+        "sg_wav_defense_backward": (C.c_int, [vp, C.POINTER(WavDefense), vp, vp, vp, i32, i32, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

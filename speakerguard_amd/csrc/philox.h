@@ -22,4 +22,22 @@ __device__ __forceinline__ uint32_t philox4x32_10_w0(uint64_t key, uint32_t c0, 
     return c0;
 }
 
+// the same generator, first TWO output words (a Box-Muller pair from one counter): returns word 0, *w1 = word 1
+__device__ __forceinline__ uint32_t philox4x32_10_w01(uint64_t key, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t* w1) {
+    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    *w1 = c1;
+    return c0;
+}
+
 }  // namespace sg

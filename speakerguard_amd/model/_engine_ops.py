@@ -40,7 +40,7 @@ class EngineOps:
     _index_base = 0    # global index of the first utterance of the chunk being attacked
     _draw = 0          # passes since begin_batch
     _nes_draw = 0      # NES.forward calls since begin_batch
-    _def_draw = 0      # calls of a randomised defense (FeCoDefense(init='random')) since begin_batch
+    _def_draw = 0      # calls of a randomised defense (FeCoDefense(init='random'), time_domain.AT) since begin_batch
     _row_base = 0      # position of this call's row 0 inside the full model call it is a slice of (shard.QueryShardedModel)
     _row_scale = 1     # rows every utterance of the chunk contributes to the call (NES: its queries), set by the caller
     _rep_rows = 0      # > 0: the full call's rows are EOT repeats of _rep_rows rows (adaptive_attack/EOT.py sets it)
@@ -58,11 +58,12 @@ class EngineOps:
         """(index_base, row_base, rep_rows) of the model call being made, see sg_dither."""
         return int(self._index_base) * int(self._row_scale), int(self._row_base), int(self._rep_rows)
 
-    def defense_seed(self, user_seed):
+    def defense_seed(self, user_seed, tag=0x4665436F):
         """Generator key of the next call of a randomised defense sitting on this model (defended_model): keyed like the
         dither -- (seed, attack call, restart, call number inside the chunk) + global utterance index -- so that the clusterings an
-        utterance sees do not depend on the shard layout either (rows: ``row_keys()``)."""
-        key = self.noise_seed(int(user_seed) ^ 0x4665436F, self._def_draw)
+        utterance sees do not depend on the shard layout either (rows: ``row_keys()``).  `tag` separates the key domains of
+        different defenses (default: FeCo's; defense.time_domain.AT passes its own ``seed_tag``)."""
+        key = self.noise_seed(int(user_seed) ^ int(tag), self._def_draw)
         self._def_draw += 1
         return key
 

@@ -5,7 +5,8 @@ including the native ``loss_grad`` / ``pgd_run`` entry points the attacks use.  
 feature-level defenses are applied for the forward calls exactly like ``process_sequential``
 (:46-65).  The gradient THROUGH feature-level defenses is chained by hand for
 defenses that expose ``fwd`` / ``bwd`` (``speakerguard_amd.defense.feature_level.FeCoDefense`` at the feature levels,
-``speakerguard_amd.adaptive_attack.BPDA.BPDA(f, sub_f)`` -- the reference's straight-through wrapper, BPDA.py:7-65 -- around any
+``speakerguard_amd.defense.time_domain.QT / BDR / AT / AS / MS`` at the waveform -- native kernels in both directions --
+and ``speakerguard_amd.adaptive_attack.BPDA.BPDA(f, sub_f)`` -- the reference's straight-through wrapper, BPDA.py:7-65 -- around any
 input-level transform) on the native xv_plda / audionet_csine base models in sequential order; any other defended
 configuration raises in ``loss_grad`` instead of silently ignoring the defense.
 """
@@ -51,10 +52,14 @@ class defended_model:
         return any(getattr(method, 'batch_coupled', False) for _, method in (self.defense or []))
 
     def _fwd(self, d, xx):
-        """``d.fwd(xx)``; a randomised defense (FeCoDefense(init='random')) takes its generator key from the base
-        model's noise bookkeeping (attack call, chunk, call number) instead of its own call counter."""
-        if getattr(d, 'init', None) == 'random' and hasattr(self.base_model, 'defense_seed'):
-            return d.fwd(xx, seed=self.base_model.defense_seed(d.seed), row_keys=self.base_model.row_keys())
+        """``d.fwd(xx)``; a randomised defense (FeCoDefense(init='random'), or any defense with ``randomised`` set:
+        defense.time_domain.AT) takes its generator key from the base model's noise bookkeeping (attack call, chunk, call
+        number) instead of its own call counter, in the key domain of its ``seed_tag`` when it has one."""
+        base = self.base_model
+        if (getattr(d, 'init', None) == 'random' or getattr(d, 'randomised', False)) and hasattr(base, 'defense_seed'):
+            tag = getattr(d, 'seed_tag', None)
+            seed = base.defense_seed(d.seed) if tag is None else base.defense_seed(d.seed, tag)
+            return d.fwd(xx, seed=seed, row_keys=base.row_keys())
         return d.fwd(xx)
 
     def _apply(self, d, xx):
