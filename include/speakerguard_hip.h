@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* are (tags 60, 61).  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -393,6 +393,9 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * because a defended attack step is the model's pass sequence plus exactly these launches) */
 #define SG_STAGE_TD_FWD 60
 #define SG_STAGE_TD_BWD 61
+/* frequency-domain input defenses (sg_wav_filter_forward / _backward), traced for the same reason */
+#define SG_STAGE_FD_FWD 62
+#define SG_STAGE_FD_BWD 63
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -553,6 +556,37 @@ int sg_wav_defense_forward(sg_ctx* ctx, const sg_wav_defense* d, const float* x_
 /* x_dev: the forward's input (read by AT only, may be NULL otherwise) */
 int sg_wav_defense_backward(sg_ctx* ctx, const sg_wav_defense* d, const float* x_dev, const float* g_dev, void* saved_dev,
                             int32_t B, int32_t T, float* gx_dev, void* stream);
+
+/* ---- frequency-domain input defenses (defense/frequency_domain.py LPF :33-70, BPF :72-112) ----------------------
+ * A Butterworth filter followed by a clamp, x / out / g / gx (B,T) float32 on the device, one utterance per row, zero initial
+ * state.  The filter is handed over as the float64 second-order sections of the design (scipy's `sos` layout: S rows of
+ * b0 b1 b2 a0 a1 a2, 1 <= S <= 16, a HOST pointer read during the call) and runs as that cascade in float32, as a parallel
+ * scan, one launch per direction -- NOT as the reference's single direct form (b, a) in float32, whose default BPF is
+ * unstable after its float32 cast (DESIGN.md "The frequency-domain defenses").  Every output value is one fixed sequence of
+ * float32 operations that depends neither on B nor on how a batch is cut into calls (csrc/k_freq_domain.hip header,
+ * restated in tests/freq_domain_restate.py).  Both calls are stream-ordered, allocate nothing and never synchronise; the
+ * derived float32 tables travel as kernel arguments.
+ *   forward   v = H x; out = clamp(v, lo, hi); mask (B,T) int8 = 1 where lo <= v <= hi, else 0 (torch's clamp gradient).
+ *             SG_FD_CLIP_RANGE: the reference's per-call rule (:46-51) -- [-1, 1] when the whole call lies in the unit range,
+ *             else [-2^(bits-1), 2^(bits-1) - 1] -- decided on the device from *scale_dev, the float sg_input_scale(x, B*T)
+ *             wrote (32768 = unit range); SG_FD_CLIP_GIVEN: [clip_lo, clip_hi] (infinities allowed), scale_dev unused.
+ *   backward  gx = H^T (g . mask), H^T the anti-causal filter flip(H flip(.)): the forward's sequence on the reversed row.
+ * SG_ERR_ARG for S outside 1..16, B or T < 1, a missing pointer, a non-finite sos entry, a zero a0, a section whose poles
+ * (of the float64 row or of its float32 rounding) are not strictly inside the unit circle, an unknown clip_mode. */
+#define SG_FD_CLIP_RANGE 0
+#define SG_FD_CLIP_GIVEN 1
+typedef struct sg_wav_filter {
+    int32_t n_sections;
+    const double* sos;   /* host, (n_sections, 6) */
+    int32_t clip_mode;   /* SG_FD_CLIP_* */
+    int32_t bits;        /* SG_FD_CLIP_RANGE: the integer range's width (the reference's `bits`, 16) */
+    float clip_lo;       /* SG_FD_CLIP_GIVEN */
+    float clip_hi;
+} sg_wav_filter;
+int sg_wav_filter_forward(sg_ctx* ctx, const sg_wav_filter* f, const float* x_dev, int32_t B, int32_t T,
+                          const float* scale_dev, float* out_dev, int8_t* mask_dev, void* stream);
+int sg_wav_filter_backward(sg_ctx* ctx, const sg_wav_filter* f, const float* g_dev, const int8_t* mask_dev, int32_t B,
+                           int32_t T, float* gx_dev, void* stream);
 
 #ifdef __cplusplus
 }

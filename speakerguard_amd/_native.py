@@ -24,7 +24,7 @@ EXPORTS = (
     "sg_an_pgd_run", "sg_an_pgd_run_feco", "sg_conv1d_rows", "sg_wav_finalize", "sg_eer_threshold",
     "sg_xv_mfcc_backward", "sg_xv_cmvn_backward", "sg_feco_kmeans", "sg_feco_kmeans_seeded", "sg_feco_kmeans_compress", "sg_feco_compress_backward_reps", "sg_feco_compress", "sg_feco_compress_backward", "sg_feco_warped",
     "sg_an_logmel_backward", "sg_an_configure", "sg_xv_configure", "sg_xv_enroll_override", "sg_health", "sg_set_streamk", "sg_debug_lose_handoffs", "sg_debug_feco_epoch", "sg_feco_set_two_cu", "sg_trace_begin", "sg_trace_end",
-    "sg_wav_defense_forward", "sg_wav_defense_backward",
+    "sg_wav_defense_forward", "sg_wav_defense_backward", "sg_wav_filter_forward", "sg_wav_filter_backward",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -39,7 +39,9 @@ STAGE_NAMES.update({20: "an_logmel_fwd", 21: "an_prefilter_fwd", 22: "an_pool_fw
 STAGE_NAMES.update({30 + l: "an_conv%d_fwd" % (l + 2) for l in range(7)})
 STAGE_NAMES.update({40 + l: "an_conv%d_dgrad" % (l + 2) for l in range(7)})
 STAGE_NAMES.update({60: "td_fwd", 61: "td_bwd"})  # time-domain input defenses (SG_STAGE_TD_*)
+STAGE_NAMES.update({62: "fd_fwd", 63: "fd_bwd"})  # frequency-domain input defenses (SG_STAGE_FD_*)
 SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
+SG_FD_CLIP_RANGE, SG_FD_CLIP_GIVEN = 0, 1
 
 
 class NativeError(RuntimeError):
@@ -88,6 +90,11 @@ class FecoParams(C.Structure):
 class WavDefense(C.Structure):
     _fields_ = [("kind", C.c_int32), ("param", C.c_float), ("seed", C.c_uint64), ("index_base", C.c_int64),
                 ("row_base", C.c_int64), ("rep_rows", C.c_int32), ("noise_dev", C.c_void_p)]
+
+
+class WavFilter(C.Structure):
+    _fields_ = [("n_sections", C.c_int32), ("sos", C.POINTER(C.c_double)), ("clip_mode", C.c_int32), ("bits", C.c_int32),
+                ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
 
 
 _lib = None
@@ -164,6 +171,8 @@ def load():
         "sg_feco_compress_backward": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         "sg_wav_defense_forward": (C.c_int, [vp, C.POINTER(WavDefense), vp, i32, i32, vp, vp, vp]),
         "sg_wav_defense_backward": (C.c_int, [vp, C.POINTER(WavDefense), vp, vp, vp, i32, i32, vp, vp]),
+        "sg_wav_filter_forward": (C.c_int, [vp, C.POINTER(WavFilter), vp, i32, i32, vp, vp, vp, vp]),
+        "sg_wav_filter_backward": (C.c_int, [vp, C.POINTER(WavFilter), vp, vp, i32, i32, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
