@@ -37,6 +37,7 @@ ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefi
               -fno-omit-frame-pointer -Iinclude -Wall -Wno-unused-function
 ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 ASAN_EXE   := $(ASAN_DIR)/abi_asan_driver
+ASAN_DEF   := $(ASAN_DIR)/defended_asan_driver
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
@@ -50,14 +51,24 @@ $(ASAN_DIR)/abi_asan_driver.o: tests/native/abi_asan_driver.cpp $(CSRC)/sg_inter
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
+$(ASAN_DIR)/defended_asan_driver.o: tests/native/defended_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
 # (the host objects reference their embedded-code-object symbols even when none is embedded: define them empty)
 $(ASAN_EXE): $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/abi_asan_driver.o
 	nm -u $(ASAN_OBJS) | grep -o '__hip_fatbin_[0-9a-f]*' | sort -u | sed 's/.*/char &[8];/' > $(ASAN_DIR)/fatbin_syms.c
 	gcc -c $(ASAN_DIR)/fatbin_syms.c -o $(ASAN_DIR)/fatbin_syms.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $^ $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE)
+# the defended device loop's own walk (sg_xv_pgd_run_defended): a second program over the same objects
+$(ASAN_DEF): $(ASAN_EXE) $(ASAN_DIR)/defended_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/defended_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

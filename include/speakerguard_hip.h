@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63).  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63), and so is sg_xv_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -396,6 +396,10 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 /* frequency-domain input defenses (sg_wav_filter_forward / _backward), traced for the same reason */
 #define SG_STAGE_FD_FWD 62
 #define SG_STAGE_FD_BWD 63
+/* the defended device loop (sg_xv_pgd_run_defended): its stage launches carry the four tags above; its own are */
+#define SG_STAGE_DEF_SCALE 64     /* scale / clip decision of a stage that is not first, and of the MFCC, from the pass's rows */
+#define SG_STAGE_DEF_REPLICATE 65 /* the iterate copied once per EOT repeat of the pass */
+#define SG_STAGE_DEF_REP_SUM 66   /* repeat sum of the cotangents, carried on or turned into the sign step (one launch) */
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -587,6 +591,54 @@ int sg_wav_filter_forward(sg_ctx* ctx, const sg_wav_filter* f, const float* x_de
                           const float* scale_dev, float* out_dev, int8_t* mask_dev, void* stream);
 int sg_wav_filter_backward(sg_ctx* ctx, const sg_wav_filter* f, const float* g_dev, const int8_t* mask_dev, int32_t B,
                            int32_t T, float* gx_dev, void* stream);
+
+/* ---- input-level defenses inside the device-resident x-vector PGD loop ---------------------------------------
+ * sg_xv_pgd_run for a model that carries a chain of 1 .. SG_WAV_CHAIN_MAX waveform-level defenses (flag 0, sequential
+ * order), applied in chain order to the waveform before the MFCC.  A stage is one sg_wav_defense or one sg_wav_filter,
+ * exactly as the single-stage calls above take them (sg_wav_filter.sos: a HOST pointer read during the call); the stage
+ * kernels and their arithmetic contracts are those calls'.  Arguments and outputs as sg_xv_pgd_run.
+ *
+ * Per step `it` and repeat group starting at repeat g0: chain forward on the iterate (each stage keeps its saved state and
+ * its input), front-end / TDNN / tail and the backward to the DEFENDED waveform, chain backward in reverse order, then
+ * x <- clamp(project(x + step * sign(sum over the repeats))).  The final pass (it == max_iter) is one forward repeat, chain
+ * included.  reps = eot_size when a stage is randomised (SG_TD_AT) or dither != 0, else 1.  Every repeat is its own row
+ * (row = repeat * B + utterance, G repeats per pass chosen as in sg_xv_pgd_run); the per-repeat cotangents are summed AFTER
+ * the chain's backward, in repeat order ((g0 + g1) + g2) + ..., in float32, earlier groups carried through the workspace.
+ * A chain of SG_TD_QT stages only (identity backward) keeps sg_xv_pgd_run's pass: the repeats share the defended rows and
+ * the overlap-add sums them and takes the step.
+ * Keys: a stage's AT key for a pass is seed + it * 0x9E3779B97F4A7C15 + g0 * 0xC2B2AE3D27D4EB4F (seed as handed in),
+ * rep_rows = B when the pass holds more than one repeat, else 0; index_base / row_base are the caller's: the dither's
+ * scheme, so noise depends on (utterance, step, repeat) only.
+ * Scale decisions: the iterate's (a QT / filter stage that is first) once per call; a QT / filter stage that is not first,
+ * and the MFCC, from their own input at every pass, over the rows of that pass, on the device.  DEVIATION: the reference
+ * decides per model call of EOT_batch_size * B rows, the loop per pass of G * B rows; the two differ only when a preceding
+ * stage pushes samples past the check_input_range bound (|x| > 1 / 0.9).
+ * All buffers come from the context's workspace and are grown before the loop; inside it nothing is allocated, nothing
+ * synchronises and nothing is copied to the host.
+ * SG_ERR_ARG before any launch: chain NULL, n_stages outside 1 .. SG_WAV_CHAIN_MAX, an unknown tag, whatever the
+ * single-stage calls refuse about a spec, a stage with noise_dev set (explicit noise is not supported in the loop). */
+#define SG_WAV_CHAIN_MAX 8
+#define SG_WAV_STAGE_DEFENSE 0
+#define SG_WAV_STAGE_FILTER 1
+typedef struct sg_wav_stage {
+    int32_t tag; /* SG_WAV_STAGE_* */
+    union {
+        sg_wav_defense defense;
+        sg_wav_filter filter;
+    } u;
+} sg_wav_stage;
+int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev,
+                           const float* upper_dev, int32_t B, int32_t T, const sg_pgd_params* params,
+                           const sg_wav_stage* chain, int32_t n_stages, uint8_t* success_dev, int64_t* decisions_dev,
+                           float* scores_dev, float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev,
+                           void* stream);
+
+/* The loop's repeat-summing update on caller buffers: planes (G, n) float32, total = ((carry +) p0 + p1) + ... in that
+ * order (carry may be NULL).  sum_out != NULL: the total is written there (may alias carry).  x != NULL:
+ * x <- min(max(x + step * grad_sign * sign(total), lower), upper), bit for bit sg_pgd_update on that total. */
+int sg_wav_rep_sum_update(sg_ctx* ctx, const float* planes_dev, int32_t G, int64_t n, const float* carry_dev,
+                          float* sum_out_dev, float* x_dev, const float* lower_dev, const float* upper_dev,
+                          float step_size, int32_t grad_sign, void* stream);
 
 #ifdef __cplusplus
 }

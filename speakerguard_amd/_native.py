@@ -25,6 +25,7 @@ EXPORTS = (
     "sg_xv_mfcc_backward", "sg_xv_cmvn_backward", "sg_feco_kmeans", "sg_feco_kmeans_seeded", "sg_feco_kmeans_compress", "sg_feco_compress_backward_reps", "sg_feco_compress", "sg_feco_compress_backward", "sg_feco_warped",
     "sg_an_logmel_backward", "sg_an_configure", "sg_xv_configure", "sg_xv_enroll_override", "sg_health", "sg_set_streamk", "sg_debug_lose_handoffs", "sg_debug_feco_epoch", "sg_feco_set_two_cu", "sg_trace_begin", "sg_trace_end",
     "sg_wav_defense_forward", "sg_wav_defense_backward", "sg_wav_filter_forward", "sg_wav_filter_backward",
+    "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -40,7 +41,11 @@ STAGE_NAMES.update({30 + l: "an_conv%d_fwd" % (l + 2) for l in range(7)})
 STAGE_NAMES.update({40 + l: "an_conv%d_dgrad" % (l + 2) for l in range(7)})
 STAGE_NAMES.update({60: "td_fwd", 61: "td_bwd"})  # time-domain input defenses (SG_STAGE_TD_*)
 STAGE_NAMES.update({62: "fd_fwd", 63: "fd_bwd"})  # frequency-domain input defenses (SG_STAGE_FD_*)
+# the defended device loop's own launches (SG_STAGE_DEF_*)
+STAGE_NAMES.update({64: "def_scale", 65: "def_replicate", 66: "def_rep_sum"})
 SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
+SG_WAV_CHAIN_MAX = 8
+SG_WAV_STAGE_DEFENSE, SG_WAV_STAGE_FILTER = 0, 1
 SG_FD_CLIP_RANGE, SG_FD_CLIP_GIVEN = 0, 1
 
 
@@ -97,6 +102,15 @@ class WavFilter(C.Structure):
                 ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
 
 
+class _WavStageU(C.Union):
+    _fields_ = [("defense", WavDefense), ("filter", WavFilter)]
+
+
+class WavStage(C.Structure):
+    """sg_wav_stage: one stage of sg_xv_pgd_run_defended's chain"""
+    _fields_ = [("tag", C.c_int32), ("u", _WavStageU)]
+
+
 _lib = None
 
 
@@ -142,6 +156,9 @@ def load():
         "sg_pgd_update": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, i32, vp]),
         "sg_loss_eval": (C.c_int, [vp, vp, vp, i32, i32, f32, C.POINTER(LossSpec), vp, vp, vp, vp]),
         "sg_xv_pgd_run": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),
+        "sg_xv_pgd_run_defended": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(WavStage), i32,
+                                             vp, vp, vp, vp, vp, vp, vp]),
+        "sg_wav_rep_sum_update": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, f32, i32, vp]),
         "sg_cw2_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp, vp, vp]),
         "sg_nes_queries": (C.c_int, [vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i64, i32, vp, vp, vp, vp]),
         "sg_nes_grad": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_uint64, i64, i32, vp, i32, f32, i32, vp, vp]),

@@ -3,6 +3,7 @@ from .PGD import PGD
 
 
 class CWinf(PGD):
+    fuse_input_defenses = False  # against native input-level defenses CWinf keeps the step loop ("Defenses inside the loop")
 
     def __init__(self, model, task='CSI', epsilon=0.002, step_size=0.0004, max_iter=10, num_random_init=0,
                  loss='Margin', targeted=False,

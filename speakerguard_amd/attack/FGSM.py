@@ -3,8 +3,10 @@
 ``attack_batch`` is the hot loop (FGSM.py:38-70).  When the model is the native x-vector engine
 and nothing between attack and model needs Python (no defense wrapper), the whole loop, EOT repeats
 over the front-end's random dither included -- max_iter x (forward, hand-coded backward, sign step,
-projection) + the final forward-only pass -- is ONE C-ABI call (``model.pgd_run``).  Otherwise
-the same loop runs step by step over ``model.loss_grad`` / ``model.pgd_update``.
+projection) + the final forward-only pass -- is ONE C-ABI call (``model.pgd_run``).  A wrapper that
+carries only native waveform-level defenses in sequential order runs the same way, the chain inside
+the loop (``model.pgd_run_defended``).  Otherwise the same loop runs step by step over
+``model.loss_grad`` / ``model.pgd_update``.
 """
 import numpy as np
 import torch
@@ -59,6 +61,31 @@ class FGSM(Attack):
         from ..defense.feature_level import FeCoDefense
         return d if flag == 1 and isinstance(d, FeCoDefense) else None
 
+    def _fused_input_chain(self):
+        """The defense objects of ``defended_model(base, [(0, d1), (0, d2), ...])`` in chain order when the base model runs
+        that loop on the device (xv_plda.pgd_run_defended): sequential order, every defense at the waveform level and a
+        native waveform defense object (defense.time_domain / defense.frequency_domain) as it stands -- no BPDA wrapper,
+        no Python callable, no explicit noise.  Else None: the step loop below."""
+        m = self.model
+        defense = getattr(m, 'defense', None)
+        base = getattr(m, 'base_model', None)
+        if not self.fuse_input_defenses or not defense or base is None or not hasattr(base, 'pgd_run_defended'):
+            return None
+        if getattr(m, 'order', None) != 'sequential':
+            return None
+        from ..defense.time_domain import _WavDefense
+        if not all(flag == 0 and isinstance(d, _WavDefense) for flag, d in defense):
+            return None
+        chain = m.flag2defense.get(0, [])  # what process_sequential applies, in its order
+        if len(chain) != len(defense) or not 1 <= len(chain) <= 8:
+            return None
+        # A randomised stage (AT) draws DIFFERENT noise on the two routes for the same seed: the device loop keys a pass by
+        # (step, repeat), the step loop by the defense's call number.  An attack's result must not change under its user, so
+        # such a chain keeps the step loop unless the caller asks for the device loop's schedule.
+        if any(getattr(d, 'randomised', False) for d in chain) and not self.fuse_randomised_input_defenses:
+            return None
+        return chain
+
     def _can_fuse(self):
         m = self.model
         if getattr(m, 'defense', None) is not None:
@@ -69,10 +96,16 @@ class FGSM(Attack):
         return hasattr(base, 'pgd_run')
 
     fuse_defended = True  # False: PGD against a FeCo-defended model runs the host-chained loop (tests compare the two)
+    fuse_input_defenses = True  # False: ... against native input-level defenses likewise (tests, tools/defended_loop_time.py)
+    fuse_randomised_input_defenses = False  # True: chains holding AT run on the device too, with the device loop's noise keys
 
-    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, feco=None):
+    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, feco=None, chain=None):
         base = getattr(self.model, 'base_model', self.model)
-        if feco is not None:
+        if chain is not None:
+            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_defended(
+                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, chain,
+                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
+        elif feco is not None:
             x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_feco(
                 x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, feco,
                 self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
@@ -94,6 +127,9 @@ class FGSM(Attack):
         feco = self._fused_feco(x_batch.shape[0])
         if feco is not None:
             return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, feco=feco)
+        chain = self._fused_input_chain()
+        if chain is not None:
+            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, chain=chain)
         x_batch = x_batch.clone()
         lower = lower.expand_as(x_batch).contiguous()
         upper = upper.expand_as(x_batch).contiguous()

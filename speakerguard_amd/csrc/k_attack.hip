@@ -3,6 +3,8 @@
 //   nes_queries   adaptive_attack/NES.py:19-25  antithetic Gaussian queries around x
 //   nes_grad      adaptive_attack/NES.py:47-54  loss-weighted noise average (noise regenerated, never stored)
 //   fakebob_step  attack/FAKEBOB.py:93-104      momentum, per-example LR sign step, epsilon-ball clamp
+//   wav_rep_sum_update  the defended PGD loop: cotangents of the EOT repeats summed in repeat order, then carried on or
+//                 turned into the sign step (attack/FGSM.py:65,68)
 #include "loss_device.h"
 #include "sg_internal.h"
 
@@ -201,6 +203,81 @@ hipError_t launch_fakebob_step(float* x, float* grad, const float* prev_grad, co
                                hipStream_t s) {
     hipLaunchKernelGGL(fakebob_step_kernel, dim3((T + 255) / 256, n), dim3(256), 0, s, x, grad, prev_grad, lr, lower, upper,
                        T, momentum, one_m_momentum, grad_sign);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- repeat sum + PGD update (sg_xv_pgd_run_defended)
+// planes (G, n): plane r starts r * n floats after plane 0.  total[i] = ((carry[i] +) p0[i] + p1[i]) + ... + p(G-1)[i], plain
+// float32 additions in that order.  sum_out: the total (may alias carry: every element is read before it is written, by the
+// thread that writes it).  x: the update of pgd_update_kernel (k_misc.hip) on the total, bit for bit -- step * grad_sign
+// times a sign in {-1, 0, 1} is exact, so neither the association nor a contraction can change the sum with x.
+// One pass: a thread owns the four elements 4 j .. 4 j + 3.  x, lower, upper, carry, sum_out and plane 0 are read and
+// written as 16-byte vectors when their bases are aligned (`vec`, decided by the launcher).  Plane r is misaligned by
+// m = (r n) & 3 floats when n is no multiple of 4: its four elements then come from the two ALIGNED vectors that cover
+// them (the neighbouring thread's second vector is this thread's first: the second request hits the cache, HBM traffic
+// stays one pass), unless one of the two would reach outside [planes, planes + G n) -- the first thread of the head, the
+// last of the tail -- or the thread owns the ragged end of the row (n & 3 elements): those go element by element.
+typedef float rs_f4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void wav_rep_sum_update_kernel(const float* __restrict__ planes, int G, int64_t n,
+                                                                 const float* carry, float* sum_out, float* __restrict__ x,
+                                                                 const float* __restrict__ lo, const float* __restrict__ hi,
+                                                                 float step, int grad_sign, int vec) {
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const float s = step * (float)grad_sign;
+    if (vec && i0 + 3 < n) {
+        rs_f4 tot = *reinterpret_cast<const rs_f4*>(planes + i0);
+        if (carry) tot = *reinterpret_cast<const rs_f4*>(carry + i0) + tot;
+        const int64_t end = (int64_t)G * n;
+        for (int r = 1; r < G; ++r) {
+            const int64_t a = (int64_t)r * n + i0;
+            const int m = (int)(a & 3);  // uniform over the launch
+            rs_f4 p;
+            if (m == 0) {
+                p = *reinterpret_cast<const rs_f4*>(planes + a);
+            } else if (a - m + 8 <= end) {  // (a - m >= 0: r >= 1)
+                const rs_f4 u = *reinterpret_cast<const rs_f4*>(planes + (a - m));
+                const rs_f4 v = *reinterpret_cast<const rs_f4*>(planes + (a - m + 4));
+                p = m == 1 ? rs_f4{u.y, u.z, u.w, v.x} : m == 2 ? rs_f4{u.z, u.w, v.x, v.y} : rs_f4{u.w, v.x, v.y, v.z};
+            } else {
+                p = rs_f4{planes[a], planes[a + 1], planes[a + 2], planes[a + 3]};
+            }
+            tot = tot + p;
+        }
+        if (sum_out) *reinterpret_cast<rs_f4*>(sum_out + i0) = tot;
+        if (x) {
+            rs_f4 xv = *reinterpret_cast<const rs_f4*>(x + i0);
+            const rs_f4 lv = *reinterpret_cast<const rs_f4*>(lo + i0), hv = *reinterpret_cast<const rs_f4*>(hi + i0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float sg = tot[c] > 0.f ? 1.f : (tot[c] < 0.f ? -1.f : 0.f);
+                xv[c] = fminf(fmaxf(xv[c] + s * sg, lv[c]), hv[c]);
+            }
+            *reinterpret_cast<rs_f4*>(x + i0) = xv;
+        }
+        return;
+    }
+    for (int64_t i = i0; i < n && i < i0 + 4; ++i) {
+        float tot = planes[i];
+        if (carry) tot = carry[i] + tot;
+        for (int r = 1; r < G; ++r) tot = tot + planes[(int64_t)r * n + i];
+        if (sum_out) sum_out[i] = tot;
+        if (x) {
+            const float sg = tot > 0.f ? 1.f : (tot < 0.f ? -1.f : 0.f);
+            x[i] = fminf(fmaxf(x[i] + s * sg, lo[i]), hi[i]);
+        }
+    }
+}
+
+hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, const float* carry, float* sum_out, float* x,
+                                     const float* lo, const float* hi, float step, int grad_sign, hipStream_t s) {
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(carry) |
+                            reinterpret_cast<uintptr_t>(sum_out) | reinterpret_cast<uintptr_t>(x) |
+                            reinterpret_cast<uintptr_t>(x ? lo : nullptr) | reinterpret_cast<uintptr_t>(x ? hi : nullptr);
+    const int64_t blocks = (n + 1023) / 1024;
+    hipLaunchKernelGGL(wav_rep_sum_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, planes, G, n, carry, sum_out, x, lo, hi,
+                       step, grad_sign, (int)(bases % 16 == 0));
     return hipGetLastError();
 }
 

@@ -236,38 +236,60 @@ int fd_tables(const double* sos, int S, FdTables* tab, const char** why) {
     return 0;
 }
 
-int fd_check(sg_ctx* ctx, const char* who, const sg_wav_filter* f, const void* a, const void* b, const void* c, int32_t B,
-             int32_t T, FdTables* tab) {
-    if (!ctx) return SG_ERR_ARG;
-    if (!f || !a || !b || !c || !f->sos) return fd_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || T < 1 || T > kFdMaxT) return fd_fail(ctx, SG_ERR_ARG, "%s: need B >= 1 and 1 <= T <= %d (B %d, T %d)", who, kFdMaxT, B, T);
+// what a spec alone can get wrong about its sections; builds the kernel's tables on the way
+int fd_check_sections(sg_ctx* ctx, const char* who, const sg_wav_filter* f, FdTables* tab) {
     if (f->n_sections < 1 || f->n_sections > kFdMaxSections)
         return fd_fail(ctx, SG_ERR_ARG, "%s: 1 .. %d sections are built (%d)", who, kFdMaxSections, f->n_sections);
     const char* why = "";
     const int bad = fd_tables(f->sos, f->n_sections, tab, &why);
     if (bad) return fd_fail(ctx, SG_ERR_ARG, "%s: section %d of %d: %s", who, bad, f->n_sections, why);
+    return SG_OK;
+}
+
+int fd_check(sg_ctx* ctx, const char* who, const sg_wav_filter* f, const void* a, const void* b, const void* c, int32_t B,
+             int32_t T, FdTables* tab) {
+    if (!ctx) return SG_ERR_ARG;
+    if (!f || !a || !b || !c || !f->sos) return fd_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    if (B < 1 || T < 1 || T > kFdMaxT) return fd_fail(ctx, SG_ERR_ARG, "%s: need B >= 1 and 1 <= T <= %d (B %d, T %d)", who, kFdMaxT, B, T);
+    if (int rc = fd_check_sections(ctx, who, f, tab)) return rc;
     if (hipSetDevice(ctx->device) != hipSuccess) return fd_fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
     return SG_OK;
 }
 
+// the forward's clip range from the spec: [lo_a, hi_a] in the unit range (or given), [lo_b, hi_b] otherwise
+int fd_clip(sg_ctx* ctx, const char* who, const sg_wav_filter* f, bool have_scale, float* lo_a, float* hi_a, float* lo_b, float* hi_b) {
+    *lo_a = -1.f, *hi_a = 1.f, *lo_b = 0.f, *hi_b = 0.f;
+    if (f->clip_mode == SG_FD_CLIP_RANGE) {
+        if (!have_scale) return fd_fail(ctx, SG_ERR_ARG, "%s: SG_FD_CLIP_RANGE needs scale_dev", who);
+        if (f->bits < 2 || f->bits > 24) return fd_fail(ctx, SG_ERR_ARG, "%s: bits must be 2 .. 24 (%d)", who, f->bits);
+        *lo_b = -(float)(1 << (f->bits - 1)), *hi_b = (float)((1 << (f->bits - 1)) - 1);
+    } else if (f->clip_mode == SG_FD_CLIP_GIVEN) {
+        if (!(f->clip_lo <= f->clip_hi)) return fd_fail(ctx, SG_ERR_ARG, "%s: need clip_lo <= clip_hi", who);
+        *lo_a = f->clip_lo, *hi_a = f->clip_hi;
+    } else {
+        return fd_fail(ctx, SG_ERR_ARG, "%s: unknown clip_mode %d", who, f->clip_mode);
+    }
+    return SG_OK;
+}
+
 }  // namespace
+
+int sg::wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f) {
+    if (!f->sos) return fd_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    FdTables tab;
+    if (int rc = fd_check_sections(ctx, who, f, &tab)) return rc;
+    float lo_a, hi_a, lo_b, hi_b;
+    return fd_clip(ctx, who, f, true, &lo_a, &hi_a, &lo_b, &hi_b);
+}
 
 extern "C" int sg_wav_filter_forward(sg_ctx* ctx, const sg_wav_filter* f, const float* x_dev, int32_t B, int32_t T,
                                      const float* scale_dev, float* out_dev, int8_t* mask_dev, void* stream) {
     FdTables tab;
     int rc = fd_check(ctx, "sg_wav_filter_forward", f, x_dev, out_dev, mask_dev, B, T, &tab);
     if (rc) return rc;
-    float lo_a = -1.f, hi_a = 1.f, lo_b = 0.f, hi_b = 0.f;
-    if (f->clip_mode == SG_FD_CLIP_RANGE) {
-        if (!scale_dev) return fd_fail(ctx, SG_ERR_ARG, "sg_wav_filter_forward: SG_FD_CLIP_RANGE needs scale_dev");
-        if (f->bits < 2 || f->bits > 24) return fd_fail(ctx, SG_ERR_ARG, "sg_wav_filter_forward: bits must be 2 .. 24 (%d)", f->bits);
-        lo_b = -(float)(1 << (f->bits - 1)), hi_b = (float)((1 << (f->bits - 1)) - 1);
-    } else if (f->clip_mode == SG_FD_CLIP_GIVEN) {
-        if (!(f->clip_lo <= f->clip_hi)) return fd_fail(ctx, SG_ERR_ARG, "sg_wav_filter_forward: need clip_lo <= clip_hi");
-        lo_a = f->clip_lo, hi_a = f->clip_hi, scale_dev = nullptr;
-    } else {
-        return fd_fail(ctx, SG_ERR_ARG, "sg_wav_filter_forward: unknown clip_mode %d", f->clip_mode);
-    }
+    float lo_a, hi_a, lo_b, hi_b;
+    if ((rc = fd_clip(ctx, "sg_wav_filter_forward", f, scale_dev != nullptr, &lo_a, &hi_a, &lo_b, &hi_b))) return rc;
+    if (f->clip_mode == SG_FD_CLIP_GIVEN) scale_dev = nullptr;
     hipStream_t s = (hipStream_t)stream;
     trace_mark(ctx, SG_STAGE_FD_FWD, s, 0);
     hipLaunchKernelGGL(fd_cascade_kernel<false>, dim3(B), dim3(kFdThreads), 0, s, x_dev, (const int8_t*)nullptr, out_dev, mask_dev,

@@ -251,10 +251,8 @@ int td_window(float param) {
     return ((float)k == param && k >= 1 && k <= kTdMaxK && (k & 1)) ? k : 0;
 }
 
-int td_check(sg_ctx* ctx, const char* who, const sg_wav_defense* d, const void* a, const void* b, int32_t B, int32_t T) {
-    if (!ctx) return SG_ERR_ARG;
-    if (!d || !a || !b) return td_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || B > 65535 || T < 1) return td_fail(ctx, SG_ERR_ARG, "%s: need 1 <= B <= 65535 and T >= 1 (B %d, T %d)", who, B, T);
+// what a spec alone can get wrong (both directions, and the defended loop before its first launch)
+int td_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d) {
     switch (d->kind) {
     case SG_TD_QT:
         if (!(d->param > 0.f) || !std::isfinite(d->param)) return td_fail(ctx, SG_ERR_ARG, "%s: QT needs a finite q > 0 (%g)", who, d->param);
@@ -270,6 +268,14 @@ int td_check(sg_ctx* ctx, const char* who, const sg_wav_defense* d, const void* 
     default:
         return td_fail(ctx, SG_ERR_ARG, "%s: unknown kind %d", who, d->kind);
     }
+    return SG_OK;
+}
+
+int td_check(sg_ctx* ctx, const char* who, const sg_wav_defense* d, const void* a, const void* b, int32_t B, int32_t T) {
+    if (!ctx) return SG_ERR_ARG;
+    if (!d || !a || !b) return td_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    if (B < 1 || B > 65535 || T < 1) return td_fail(ctx, SG_ERR_ARG, "%s: need 1 <= B <= 65535 and T >= 1 (B %d, T %d)", who, B, T);
+    if (int rc = td_check_spec(ctx, who, d)) return rc;
     if (hipSetDevice(ctx->device) != hipSuccess) return td_fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
     return SG_OK;
 }
@@ -278,6 +284,8 @@ inline float at_snr(float param_db) { return (float)std::pow(10.0, (double)param
 inline AtNoise at_noise(const sg_wav_defense* d) { return AtNoise{d->noise_dev, d->seed, d->index_base, d->row_base, d->rep_rows}; }
 
 }  // namespace
+
+int sg::wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d) { return td_check_spec(ctx, who, d); }
 
 extern "C" int sg_wav_defense_forward(sg_ctx* ctx, const sg_wav_defense* d, const float* x_dev, int32_t B, int32_t T,
                                       float* out_dev, void* saved_dev, void* stream) {

@@ -459,6 +459,116 @@ int run_backward_to_input(sg_ctx* ctx, const float* x, const PassDims& d, int fl
     return SG_OK;
 }
 
+// ---- pieces of the device-resident PGD loops (sg_xv_pgd_run, sg_xv_pgd_run_defended)
+// G: as many EOT repeats as one pass may hold (activation tensors < 2 GiB); more run as further groups
+int eot_group_size(sg_ctx* ctx, int B, int T, int reps, int* G) {
+    *G = 1;
+    if (reps > 1) {
+        int Fl[kLayers];
+        const int F = num_frames(T);
+        if (!layer_frames(F, Fl)) return fail(ctx, SG_ERR_ARG, "%d frames are too few for the TDNN context", F);
+        size_t per_utt = 0;
+        for (int l = 0; l < kLayers; ++l) per_utt = std::max(per_utt, (size_t)Fl[l] * kCoutPad[l] * sizeof(float));
+        long max_rows = (long)(0x7FFFFFFFull / per_utt);
+        if (const char* e = sg_tune_env("SG_EOT_MAX_ROWS")) max_rows = std::min<long>(max_rows, atol(e));  // tests: force groups
+        *G = (int)std::min<long>(reps, std::max<long>(1, max_rows / B));
+    }
+    return SG_OK;
+}
+
+// per-step records (attack/FGSM.py:50-58: loss averaged, decision voted over ALL EOT repeats of the step): when the
+// repeats of a step run as several passes (G < reps) every pass leaves its rows here and the last one reduces them
+int grow_eot_rows(sg_ctx* ctx, size_t rows, hipStream_t s) {
+    Workspace& w = ctx->ws;
+    if (w.eot_rows_cap >= rows) return SG_OK;
+    // grown: the old pair is released (nothing enqueued still uses it once the stream has drained), not left in the
+    // workspace's pool until sg_destroy
+    if (w.eot_loss_rows || w.eot_dec_rows) {
+        SG_HIP(hipStreamSynchronize(s));
+        for (void* old : {static_cast<void*>(w.eot_loss_rows), static_cast<void*>(w.eot_dec_rows)}) {
+            auto it = std::find(w.allocs.begin(), w.allocs.end(), old);
+            if (it != w.allocs.end()) {
+                (void)hipFree(old);
+                w.allocs.erase(it);
+            }
+        }
+        w.eot_loss_rows = nullptr;
+        w.eot_dec_rows = nullptr;
+        w.eot_rows_cap = 0;
+    }
+    int rc;
+    if ((rc = dev_alloc(ctx, w.allocs, &w.eot_loss_rows, rows))) return rc;
+    if ((rc = dev_alloc(ctx, w.allocs, &w.eot_dec_rows, rows))) return rc;
+    w.eot_rows_cap = rows;
+    return SG_OK;
+}
+
+// buffers of the defended loop for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the
+// replicated iterate and the two cotangent planes.  Grown here, before the loop; a request the buffers already cover costs nothing.
+int ensure_def_workspace(sg_ctx* ctx, int rows, int T, int n_out, int n_saved, bool rep, hipStream_t s) {
+    DefWorkspace& dw = ctx->def_ws;
+    const size_t plane = (size_t)rows * T;
+    if (dw.scales && plane <= dw.plane && rows <= dw.rows && n_out <= dw.n_out && n_saved <= dw.n_saved && (dw.rep || !rep)) return SG_OK;
+    SG_HIP(hipStreamSynchronize(s));  // nothing enqueued may still use the old buffers
+    const size_t cp = std::max(plane, dw.plane);
+    const int cr = std::max(rows, dw.rows), co = std::max(n_out, dw.n_out), cs = std::max(n_saved, dw.n_saved);
+    const bool crep = rep || dw.rep;
+    free_pool(dw.allocs);
+    dw = DefWorkspace();
+    int rc = 0;
+    for (int i = 0; i < co; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.out[i], cp);
+    for (int i = 0; i < cs; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.saved[i], cp);
+    rc |= dev_alloc(ctx, dw.allocs, &dw.stats, (size_t)SG_WAV_CHAIN_MAX * 3 * cr);
+    rc |= dev_alloc(ctx, dw.allocs, &dw.scales, SG_WAV_CHAIN_MAX);
+    if (crep) {
+        rc |= dev_alloc(ctx, dw.allocs, &dw.x_rep, cp);
+        rc |= dev_alloc(ctx, dw.allocs, &dw.g[0], cp);
+        rc |= dev_alloc(ctx, dw.allocs, &dw.g[1], cp);
+    }
+    if (rc) {
+        free_pool(dw.allocs);
+        dw = DefWorkspace();
+        return fail(ctx, SG_ERR_HIP, "workspace allocation of the defended loop failed: %s", ctx->err.c_str());
+    }
+    dw.plane = cp; dw.rows = cr; dw.n_out = co; dw.n_saved = cs; dw.rep = crep;
+    return SG_OK;
+}
+
+struct LoopOut {  // a loop's caller buffers: the state at the final pass, and the optional per-step records
+    uint8_t* success; int64_t* decisions; float* scores; float* loss; float* loss_trace; int64_t* decision_trace;
+};
+// the tail of the pass of `rows` = Gi * B rows (repeats g0 .. g0 + Gi - 1 of step `it`, nrep repeats in the step, at most G
+// per pass) and the step's records
+int run_loop_tail(sg_ctx* ctx, const sg_loss_spec& loss, const LoopOut& o, int B, int rows, int it, int g0, int Gi, int G, int nrep,
+                  bool last, hipStream_t s) {
+    Workspace& w = ctx->ws;
+    const bool want_rec = o.loss_trace || o.decision_trace;
+    TailArgs t{};
+    t.fc1_part = w.fc1_part; t.nsplit = kFc1SplitK; t.B = rows; t.m = &ctx->xv; t.y = w.y_rep; t.loss = loss;
+    t.want_grad = !last; t.demb = w.demb;
+    t.scores = last ? o.scores : nullptr;
+    t.decisions = last ? o.decisions : nullptr;
+    t.loss_out = last ? o.loss : nullptr;
+    t.success = last ? o.success : nullptr;
+    // per-step records as the reference prints them (attack/FGSM.py:50-58): the loss averaged over the step's EOT
+    // repeats and the decision voted over them (attack/utils.py:118-125).  A pass of several repeats records its
+    // rows into the workspace and a small reduction writes the step's row; with more repeats than one pass holds
+    // (G < reps: activations past 2 GiB, or SG_EOT_MAX_ROWS) the passes of the step collect their rows in repeat
+    // order and the reduction runs after the last one, over all `nrep` repeats.
+    const bool direct = nrep == 1, grouped = nrep > G;
+    float* lrows = grouped ? w.eot_loss_rows + (size_t)g0 * B : w.loss;
+    int64_t* drows = grouped ? w.eot_dec_rows + (size_t)g0 * B : w.decisions;
+    t.loss_trace = !want_rec ? nullptr : (direct && o.loss_trace ? o.loss_trace + (size_t)it * B : lrows);
+    t.decision_trace = !want_rec ? nullptr : (direct && o.decision_trace ? o.decision_trace + (size_t)it * B : drows);
+    t.coef_rows = B;  // SG_LOSS_LINEAR: the caller's (B, S) table serves every repeat of an utterance
+    SG_STAGE(SG_STAGE_TAIL, launch_tail(t, s));
+    if (want_rec && !direct && g0 + Gi >= nrep)
+        SG_HIP(launch_eot_trace_reduce(grouped ? w.eot_loss_rows : w.loss, grouped ? w.eot_dec_rows : w.decisions, nrep, B,
+                                       o.loss_trace ? o.loss_trace + (size_t)it * B : nullptr,
+                                       o.decision_trace ? o.decision_trace + (size_t)it * B : nullptr, s));
+    return SG_OK;
+}
+
 }  // namespace
 
 // ============================================================================== C-ABI
@@ -498,6 +608,7 @@ void sg_destroy(sg_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     free_pool(ctx->ws.allocs);
+    free_pool(ctx->def_ws.allocs);
     free_pool(ctx->an_ws.allocs);  // (leaked until round 4: found by the sanitizer build's leak check, `make asan`)
     free_pool(ctx->xv.allocs);
     free_pool(ctx->model_allocs);
@@ -915,16 +1026,7 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     // other.  G: as many repeats as one pass may hold (activation tensors < 2 GiB); more run as further groups, the sum
     // handed on through ws.grad.
     int G = 1;
-    if (reps > 1) {
-        int Fl[kLayers];
-        const int F = num_frames(T);
-        if (!layer_frames(F, Fl)) return fail(ctx, SG_ERR_ARG, "%d frames are too few for the TDNN context", F);
-        size_t per_utt = 0;
-        for (int l = 0; l < kLayers; ++l) per_utt = std::max(per_utt, (size_t)Fl[l] * kCoutPad[l] * sizeof(float));
-        long max_rows = (long)(0x7FFFFFFFull / per_utt);
-        if (const char* e = sg_tune_env("SG_EOT_MAX_ROWS")) max_rows = std::min<long>(max_rows, atol(e));  // tests: force groups
-        G = (int)std::min<long>(reps, std::max<long>(1, max_rows / B));
-    }
+    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
     PassDims d;
     rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d);  // workspace for the largest pass
     if (rc) return rc;
@@ -934,26 +1036,7 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     // per-step records (attack/FGSM.py:50-58: loss averaged, decision voted over ALL EOT repeats of the step): when the
     // repeats of a step run as several passes (G < reps) every pass leaves its rows here and the last one reduces them
     const bool want_rec = loss_trace_dev || decision_trace_dev;
-    if (want_rec && G < reps && w.eot_rows_cap < (size_t)reps * B) {
-        // grown: the old pair is released (nothing enqueued still uses it once the stream has drained), not left in the
-        // workspace's pool until sg_destroy
-        if (w.eot_loss_rows || w.eot_dec_rows) {
-            SG_HIP(hipStreamSynchronize(s));
-            for (void* old : {static_cast<void*>(w.eot_loss_rows), static_cast<void*>(w.eot_dec_rows)}) {
-                auto it = std::find(w.allocs.begin(), w.allocs.end(), old);
-                if (it != w.allocs.end()) {
-                    (void)hipFree(old);
-                    w.allocs.erase(it);
-                }
-            }
-            w.eot_loss_rows = nullptr;
-            w.eot_dec_rows = nullptr;
-            w.eot_rows_cap = 0;
-        }
-        if ((rc = dev_alloc(ctx, w.allocs, &w.eot_loss_rows, (size_t)reps * B))) return rc;
-        if ((rc = dev_alloc(ctx, w.allocs, &w.eot_dec_rows, (size_t)reps * B))) return rc;
-        w.eot_rows_cap = (size_t)reps * B;
-    }
+    if (want_rec && G < reps && (rc = grow_eot_rows(ctx, (size_t)reps * B, s))) return rc;
     for (int it = 0; it <= p->max_iter; ++it) {
         const bool last = it == p->max_iter;
         const int nrep = last ? 1 : reps;
@@ -968,29 +1051,8 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
             d.keep_scale = it > 0 || g0 > 0;
             if ((rc = run_frontend(ctx, x_adv_dev, d, SG_FLAG_WAV, &dz, !last, s))) return rc;
             if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
-            TailArgs t{};
-            t.fc1_part = w.fc1_part; t.nsplit = kFc1SplitK; t.B = d.B; t.m = &ctx->xv; t.y = w.y_rep; t.loss = p->loss;
-            t.want_grad = !last; t.demb = w.demb;
-            t.scores = last ? scores_dev : nullptr;
-            t.decisions = last ? decisions_dev : nullptr;
-            t.loss_out = last ? loss_dev : nullptr;
-            t.success = last ? success_dev : nullptr;
-            // per-step records as the reference prints them (attack/FGSM.py:50-58): the loss averaged over the step's EOT
-            // repeats and the decision voted over them (attack/utils.py:118-125).  A pass of several repeats records its
-            // rows into the workspace and a small reduction writes the step's row; with more repeats than one pass holds
-            // (G < reps: activations past 2 GiB, or SG_EOT_MAX_ROWS) the passes of the step collect their rows in repeat
-            // order and the reduction runs after the last one, over all `nrep` repeats.
-            const bool direct = nrep == 1, grouped = nrep > G;
-            float* lrows = grouped ? w.eot_loss_rows + (size_t)g0 * B : w.loss;
-            int64_t* drows = grouped ? w.eot_dec_rows + (size_t)g0 * B : w.decisions;
-            t.loss_trace = !want_rec ? nullptr : (direct && loss_trace_dev ? loss_trace_dev + (size_t)it * B : lrows);
-            t.decision_trace = !want_rec ? nullptr : (direct && decision_trace_dev ? decision_trace_dev + (size_t)it * B : drows);
-            t.coef_rows = B;  // SG_LOSS_LINEAR: the caller's (B, S) table serves every repeat of an utterance
-            SG_STAGE(SG_STAGE_TAIL, launch_tail(t, s));
-            if (want_rec && !direct && g0 + Gi >= nrep)
-                SG_HIP(launch_eot_trace_reduce(grouped ? w.eot_loss_rows : w.loss, grouped ? w.eot_dec_rows : w.decisions, nrep, B,
-                                               loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
-                                               decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr, s));
+            const LoopOut out{success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+            if ((rc = run_loop_tail(ctx, p->loss, out, B, d.B, it, g0, Gi, G, nrep, last, s))) return rc;
             if (!last) {
                 const bool final_group = g0 + Gi >= nrep;
                 rc = run_backward_to_input(ctx, x_adv_dev, d, SG_FLAG_WAV, &dz, final_group ? nullptr : w.grad,
@@ -1000,6 +1062,168 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
             }
         }
     }
+    return SG_OK;
+}
+
+int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
+                           int32_t B, int32_t T, const sg_pgd_params* p, const sg_wav_stage* chain, int32_t n_stages,
+                           uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+                           float* loss_trace_dev, int64_t* decision_trace_dev, void* stream) {
+    static const char* who = "sg_xv_pgd_run_defended";
+    int rc;
+    if (!ctx) return SG_ERR_ARG;
+    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return fail(ctx, SG_ERR_ARG, "NULL argument");
+    if (B < 1 || T < kWin) return fail(ctx, SG_ERR_ARG, "need B >= 1 and a waveform of at least one 25 ms window");
+    if (p->max_iter < 0) return fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
+    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
+    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
+    if (eot_size % eot_bs) return fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
+    // ---- the chain: everything a stage call would refuse, before the first launch
+    if (!chain || n_stages < 1 || n_stages > SG_WAV_CHAIN_MAX)
+        return fail(ctx, SG_ERR_ARG, "%s: a chain of 1 .. %d stages is needed (%d)", who, SG_WAV_CHAIN_MAX, n_stages);
+    bool randomised = false, identity = true;
+    int n_saved = 0;
+    for (int i = 0; i < n_stages; ++i) {
+        const sg_wav_stage& st = chain[i];
+        if (st.tag == SG_WAV_STAGE_DEFENSE) {
+            if ((rc = wav_defense_check_spec(ctx, who, &st.u.defense))) return rc;
+            if (st.u.defense.noise_dev) return fail(ctx, SG_ERR_ARG, "%s: stage %d carries noise_dev: explicit noise is not supported in the loop", who, i);
+            randomised |= st.u.defense.kind == SG_TD_AT;
+            identity &= st.u.defense.kind == SG_TD_QT;
+            n_saved += st.u.defense.kind == SG_TD_MS;
+        } else if (st.tag == SG_WAV_STAGE_FILTER) {
+            if ((rc = wav_filter_check_spec(ctx, who, &st.u.filter))) return rc;
+            identity = false;
+            ++n_saved;
+        } else {
+            return fail(ctx, SG_ERR_ARG, "%s: stage %d has the unknown tag %d", who, i, st.tag);
+        }
+    }
+    // Repeats: a randomised stage (AT) or the dither makes the repeats of a step differ; otherwise one pass stands for all.
+    const int reps = (randomised || p->dither.dither != 0.f) ? eot_size : 1;
+    hipStream_t s = (hipStream_t)stream;
+    int G = 1;
+    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
+    // A chain whose backward is the identity (QT / BDR only) keeps sg_xv_pgd_run's pass: the repeats share the defended
+    // rows (the MFCC kernels read them once per repeat) and the overlap-add sums the repeats and takes the step.  Any
+    // other chain runs every repeat as its own row through chain, model and both backwards; the sum comes last.
+    const bool per_row = !identity;
+    const int rows_max = per_row ? B * G : B;
+    if (rows_max > 65535) return fail(ctx, SG_ERR_ARG, "%s: %d rows per pass, the stage kernels take at most 65535: split the batch", who, rows_max);
+    PassDims d;
+    rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d);  // workspace for the largest pass
+    if (rc) return rc;
+    if ((rc = ensure_def_workspace(ctx, rows_max, T, n_stages, n_saved, per_row, s))) return rc;
+    Workspace& w = ctx->ws;
+    DefWorkspace& dw = ctx->def_ws;
+    for (int r = 0; r < G; ++r)
+        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    const bool want_rec = loss_trace_dev || decision_trace_dev;
+    if (want_rec && G < reps && (rc = grow_eot_rows(ctx, (size_t)reps * B, s))) return rc;
+    const LoopOut out{success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+    const size_t n = (size_t)B * T;
+    // does stage i read a scale / clip decision?  (QT / BDR always; a filter under the reference's per-call rule)
+    const auto needs_scale = [&](int i) {
+        return chain[i].tag == SG_WAV_STAGE_DEFENSE ? chain[i].u.defense.kind == SG_TD_QT : chain[i].u.filter.clip_mode == SG_FD_CLIP_RANGE;
+    };
+    // the iterate is clamped into [lower, upper] within [-1, 1] at every step: its own decision is taken once
+    if (needs_scale(0)) SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(x_adv_dev, (int64_t)n, ctx->range_scratch, dw.scales, 0, s));
+
+    for (int it = 0; it <= p->max_iter; ++it) {
+        const bool last = it == p->max_iter;
+        const int nrep = last ? 1 : reps;
+        for (int g0 = 0; g0 < nrep; g0 += G) {
+            const int Gi = std::min(G, nrep - g0);
+            const int rows = per_row ? B * Gi : B;
+            const uint64_t pass_key = (uint64_t)it * 0x9E3779B97F4A7C15ull + (uint64_t)g0 * 0xC2B2AE3D27D4EB4Full;
+            // ---- chain forward
+            const float* cur = x_adv_dev;
+            if (per_row && Gi > 1) {
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
+                for (int r = 0; r < Gi; ++r)
+                    SG_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, x_adv_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
+                cur = dw.x_rep;
+            }
+            sg_wav_defense spec[SG_WAV_CHAIN_MAX];      // the pass's specs (AT: with the pass's key), reused by the backward
+            const float* stage_in[SG_WAV_CHAIN_MAX];
+            void* stage_saved[SG_WAV_CHAIN_MAX];
+            int next_saved = 0;
+            for (int i = 0; i < n_stages; ++i) {
+                stage_in[i] = cur;
+                if (i > 0 && needs_scale(i))
+                    SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(cur, (int64_t)rows * T, ctx->range_scratch, dw.scales + i, 0, s));
+                if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
+                    sg_wav_defense& sd = spec[i];
+                    sd = chain[i].u.defense;
+                    void* saved = nullptr;
+                    if (sd.kind == SG_TD_QT) saved = dw.scales + i;
+                    else if (sd.kind == SG_TD_MS) saved = dw.saved[next_saved++];
+                    else if (sd.kind == SG_TD_AT) {
+                        saved = dw.stats + (size_t)i * 3 * dw.rows;
+                        sd.seed += pass_key;
+                        sd.rep_rows = Gi > 1 ? B : 0;
+                    }
+                    stage_saved[i] = saved;
+                    if ((rc = sg_wav_defense_forward(ctx, &sd, cur, rows, T, dw.out[i], saved, s))) return rc;
+                } else {
+                    int8_t* mask = dw.saved[next_saved++];
+                    stage_saved[i] = mask;
+                    if ((rc = sg_wav_filter_forward(ctx, &chain[i].u.filter, cur, rows, T, dw.scales + i, dw.out[i], mask, s))) return rc;
+                }
+                cur = dw.out[i];
+            }
+            // ---- the model on the defended waveform
+            sg_dither dz = p->dither;
+            dz.seed += pass_key;
+            d.B = B * Gi;
+            d.Bu = !per_row && Gi > 1 ? B : 0;
+            if (per_row && Gi > 1) dz.rep_rows = B;  // rows are repeats of B utterances: repeat r keys its dither like d.Bu does
+            d.keep_scale = false;  // the MFCC's decision: from the defended rows of every pass, as a model call takes it
+            if ((rc = run_frontend(ctx, cur, d, SG_FLAG_WAV, &dz, !last, s))) return rc;
+            if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
+            if ((rc = run_loop_tail(ctx, p->loss, out, B, d.B, it, g0, Gi, G, nrep, last, s))) return rc;
+            if (last) continue;
+            const bool final_group = g0 + Gi >= nrep;
+            if (!per_row) {  // identity backward: d loss / d defended IS d loss / d iterate
+                rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, final_group ? nullptr : w.grad,
+                                           final_group ? x_adv_dev : nullptr, lower_dev, upper_dev, p->step_size, p->grad_sign, s,
+                                           g0 > 0 ? w.grad : nullptr);
+                if (rc) return rc;
+                continue;
+            }
+            if ((rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, dw.g[0], nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+            // ---- chain backward, last stage first
+            int gi = 0;
+            for (int i = n_stages - 1; i >= 0; --i) {
+                if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
+                    if (spec[i].kind == SG_TD_QT) continue;  // BPDA's identity: nothing to launch
+                    rc = sg_wav_defense_backward(ctx, &spec[i], stage_in[i], dw.g[gi], stage_saved[i], rows, T, dw.g[gi ^ 1], s);
+                } else {
+                    rc = sg_wav_filter_backward(ctx, &chain[i].u.filter, dw.g[gi], static_cast<const int8_t*>(stage_saved[i]), rows, T,
+                                                dw.g[gi ^ 1], s);
+                }
+                if (rc) return rc;
+                gi ^= 1;
+            }
+            // ---- the repeats' sum, carried to the next group or turned into the step
+            SG_STAGE(SG_STAGE_DEF_REP_SUM,
+                     launch_wav_rep_sum_update(dw.g[gi], Gi, (int64_t)n, g0 > 0 ? w.grad : nullptr, final_group ? nullptr : w.grad,
+                                               final_group ? x_adv_dev : nullptr, lower_dev, upper_dev, p->step_size, p->grad_sign, s));
+        }
+    }
+    return SG_OK;
+}
+
+int sg_wav_rep_sum_update(sg_ctx* ctx, const float* planes_dev, int32_t G, int64_t n, const float* carry_dev, float* sum_out_dev,
+                          float* x_dev, const float* lower_dev, const float* upper_dev, float step_size, int32_t grad_sign,
+                          void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    if (!planes_dev || G < 1 || n < 1 || (!sum_out_dev && !x_dev) || (x_dev && (!lower_dev || !upper_dev)))
+        return fail(ctx, SG_ERR_ARG, "sg_wav_rep_sum_update: bad argument");
+    SG_HIP(hipSetDevice(ctx->device));
+    SG_HIP(launch_wav_rep_sum_update(planes_dev, G, n, carry_dev, sum_out_dev, x_dev, lower_dev, upper_dev, step_size, grad_sign,
+                                     (hipStream_t)stream));
     return SG_OK;
 }
 

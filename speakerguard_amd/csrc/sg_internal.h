@@ -257,6 +257,22 @@ struct Workspace {
     std::vector<void*> allocs;
 };
 
+// Buffers of the defended device loop (sg_xv_pgd_run_defended), grown before the loop, never inside it.  `plane` = one
+// (rows, T) float32 waveform of the largest pass, rows = G * B when every EOT repeat runs as its own row.
+struct DefWorkspace {
+    size_t plane = 0;                  // floats per plane the buffers were sized for
+    int rows = 0;                      // rows the AT statistics were sized for
+    int n_out = 0, n_saved = 0;        // stage outputs / int8 planes held
+    bool rep = false;                  // x_rep and the two cotangent planes are held
+    float* out[SG_WAV_CHAIN_MAX] = {};   // stage outputs (the next stage's input; AT's backward reads its input here)
+    int8_t* saved[SG_WAV_CHAIN_MAX] = {};  // MS's `sel` / a filter's clamp mask, handed out in chain order
+    float* stats = nullptr;            // [SG_WAV_CHAIN_MAX][3][rows] AT's sigma, power, backward workspace
+    float* scales = nullptr;           // [SG_WAV_CHAIN_MAX] the scale / clip decision of a QT / BDR / filter stage
+    float* x_rep = nullptr;            // the iterate, once per repeat of the pass
+    float* g[2] = {};                  // cotangent planes of the chain's backward (ping-pong)
+    std::vector<void*> allocs;
+};
+
 }  // namespace sg
 
 struct sg_ctx {
@@ -271,6 +287,7 @@ struct sg_ctx {
     unsigned* sk_flags = nullptr;
     sg::XvModel xv;
     sg::Workspace ws;
+    sg::DefWorkspace def_ws;
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
@@ -511,6 +528,15 @@ hipError_t launch_frames_to_wave(const float* dframes, int B, int T, int F, int 
                                  hipStream_t s);
 hipError_t launch_pgd_update(float* x, const float* g, const float* lo, const float* hi, int64_t n,
                              float step, int grad_sign, hipStream_t s);
+// planes (G, n): the cotangents of G EOT repeats; total = ((carry +) p0 + p1) + ... in float32, in that order.  sum_out != null:
+// the total is written there (may alias carry); x != null: x <- clamp(x + step * grad_sign * sign(total), lo, hi), the bits
+// of launch_pgd_update on the same total.  One pass over memory (k_attack.hip).
+hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, const float* carry, float* sum_out, float* x,
+                                     const float* lo, const float* hi, float step, int grad_sign, hipStream_t s);
+// what sg_wav_defense_* / sg_wav_filter_* refuse about the spec itself, said before any launch (k_time_domain.hip,
+// k_freq_domain.hip): SG_OK or SG_ERR_ARG with the context's error text set
+int wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d);
+int wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f);
 // out[r][0..ncol) = in[r][0..ncol), out[r][ncol..ld_out) = 0
 hipError_t launch_copy_cols(const float* in, int ld_in, float* out, int ld_out, int64_t rows, int ncol, hipStream_t s);
 hipError_t launch_sum_cols(const float* in, int ld_in, int nsplit, long long slab_stride, float* out, int ld_out,

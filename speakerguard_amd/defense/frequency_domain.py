@@ -58,6 +58,15 @@ class _Butterworth(_WavDefense):
         f.clip_mode, f.bits, f.clip_lo, f.clip_hi = clip_mode, int(self.bits), lo, hi
         return f
 
+    def stage(self):
+        """This filter as one stage of the device-resident defended loop (sg_wav_stage).  The stage points at ``self.sos``: the
+        object must outlive the call, which reads the sections on the host."""
+        st = N.WavStage()
+        st.tag = N.SG_WAV_STAGE_FILTER
+        st.u.filter = self._filter
+        st._keep = self.sos
+        return st
+
     def fwd(self, audio):
         x, shape = self._rows(audio)
         ctx, s = _context(x.device), N.current_stream_ptr(x.device)

@@ -56,6 +56,17 @@ class _WavDefense:
         d.kind, d.param = N.SG_TD[self.kind], float(param)
         return d
 
+    def stage(self):
+        """This defense as one stage of the device-resident defended loop (sg_wav_stage; xv_plda.pgd_run_defended).  AT's key
+        and row bookkeeping are filled in by the caller."""
+        st = N.WavStage()
+        st.tag = N.SG_WAV_STAGE_DEFENSE
+        st.u.defense = self._spec(self._stage_param())
+        return st
+
+    def _stage_param(self):
+        return self.param
+
     def _forward(self, spec, x, saved):
         out = torch.empty_like(x)
         _context(x.device).call("sg_wav_defense_forward", C.byref(spec), N._ptr(x), x.shape[0], x.shape[1], N._ptr(out),
@@ -92,6 +103,9 @@ class QT(_WavDefense):
     def _q(self):
         return self.param
 
+    def _stage_param(self):
+        return self._q()
+
     def fwd(self, audio):
         x, shape = self._rows(audio)
         scale = torch.empty(1, device=x.device, dtype=torch.float32)
@@ -113,6 +127,9 @@ class BDR(QT):
 
 
 class _Windowed(_WavDefense):
+    def _stage_param(self):
+        return self._window()
+
     def _window(self):
         k = self.param
         if int(k) != k or int(k) % 2 != 1:

@@ -353,11 +353,8 @@ class xv_plda(EngineOps):
                       N._ptr(scores), N._ptr(loss), N._ptr(grad), self._stream())
         return dec, scores, loss, grad
 
-    def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
-                trace=False):
-        """attack/FGSM.py:38-70 attack_batch as one device-resident loop, including EOT over the front-end's random
-        dither (eot_size fresh-noise passes per gradient step, gradients summed on the device; the traces record each
-        step's loss averaged and decision voted over its repeats, like the reference's verbose print)."""
+    def _pgd_args(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace):
+        """the tensors and the parameter block the device loops share -> (x_adv, y, lower, upper, B, T, params, outputs)"""
         x, B, T = self._prep(x, 0)
         self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
         x_adv = x.clone()
@@ -378,10 +375,48 @@ class xv_plda(EngineOps):
         loss = torch.empty(B, device=self.device, dtype=torch.float32)
         ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
         dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
+        return x_adv, y, lower, upper, B, T, p, (success, dec, scores, loss, ltr, dtr)
+
+    def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
+                trace=False):
+        """attack/FGSM.py:38-70 attack_batch as one device-resident loop, including EOT over the front-end's random
+        dither (eot_size fresh-noise passes per gradient step, gradients summed on the device; the traces record each
+        step's loss averaged and decision voted over its repeats, like the reference's verbose print)."""
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
         self.ctx.call("sg_xv_pgd_run", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      N._ptr(success), N._ptr(dec), N._ptr(scores), N._ptr(loss), N._ptr(ltr), N._ptr(dtr),
-                      self._stream())
-        return x_adv, success, dec, scores, loss, ltr, dtr
+                      *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
+
+    def pgd_run_defended(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, eot_size=1,
+                         eot_batch_size=1, trace=False):
+        """``pgd_run`` against this model behind a chain of native waveform-level defenses (defense.time_domain /
+        defense.frequency_domain objects, applied in order before the MFCC): the step loop of ``attack_batch`` over
+        ``defended_model._loss_grad_through_defenses`` as ONE device-resident call (sg_xv_pgd_run_defended).  Every randomised
+        stage (AT) gets one base key, drawn in chain order like ``defended_model._fwd`` draws them; the loop derives the
+        key of step ``it``, repeat ``r`` from it as ``fused_pass_seed(key, it, r)``.  ``last_fused_seed`` (the dither's base
+        key) and ``last_fused_defense_seeds`` (one entry per stage, None for a deterministic one) let tests replay."""
+        chain = list(chain)
+        if not 1 <= len(chain) <= N.SG_WAV_CHAIN_MAX:
+            raise ValueError("a chain of 1 .. %d input-level defenses runs on the device, got %d" % (N.SG_WAV_CHAIN_MAX, len(chain)))
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
+        stages = (N.WavStage * len(chain))()
+        keep, keys = [], []
+        index_base, row_base, _ = self.row_keys()
+        for i, d in enumerate(chain):
+            st = d.stage()
+            keep.append(st)  # (a filter's stage keeps its sections alive)
+            key = None
+            if getattr(d, 'randomised', False):
+                key = self.defense_seed(d.seed, d.seed_tag)
+                st.u.defense.seed, st.u.defense.index_base, st.u.defense.row_base = key, index_base, row_base
+            keys.append(key)
+            stages[i] = st
+        self.last_fused_defense_seeds = keys
+        self.ctx.call("sg_xv_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
+                      stages, len(chain), *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
 
     def time_layer(self, layer, B, T, iters=20):
         ms, fl, rows = C.c_float(), C.c_double(), C.c_int32()
