@@ -38,6 +38,7 @@ ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefi
 ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 ASAN_EXE   := $(ASAN_DIR)/abi_asan_driver
 ASAN_DEF   := $(ASAN_DIR)/defended_asan_driver
+ASAN_AN    := $(ASAN_DIR)/an_defended_asan_driver
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
@@ -55,6 +56,10 @@ $(ASAN_DIR)/defended_asan_driver.o: tests/native/defended_asan_driver.cpp includ
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
+$(ASAN_DIR)/an_defended_asan_driver.o: tests/native/an_defended_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
 # (the host objects reference their embedded-code-object symbols even when none is embedded: define them empty)
 $(ASAN_EXE): $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/abi_asan_driver.o
 	nm -u $(ASAN_OBJS) | grep -o '__hip_fatbin_[0-9a-f]*' | sort -u | sed 's/.*/char &[8];/' > $(ASAN_DIR)/fatbin_syms.c
@@ -66,9 +71,15 @@ $(ASAN_DEF): $(ASAN_EXE) $(ASAN_DIR)/defended_asan_driver.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
 	    $(ASAN_DIR)/defended_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE) $(ASAN_DEF)
+# ... and AudioNet's (sg_an_pgd_run_defended): a third
+$(ASAN_AN): $(ASAN_EXE) $(ASAN_DIR)/an_defended_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/an_defended_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_AN)
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

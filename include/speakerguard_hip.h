@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63), and so is sg_xv_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63), and so are sg_xv_pgd_run_defended and sg_an_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -396,7 +396,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 /* frequency-domain input defenses (sg_wav_filter_forward / _backward), traced for the same reason */
 #define SG_STAGE_FD_FWD 62
 #define SG_STAGE_FD_BWD 63
-/* the defended device loop (sg_xv_pgd_run_defended): its stage launches carry the four tags above; its own are */
+/* the defended device loops (sg_xv_pgd_run_defended, sg_an_pgd_run_defended): their stage launches carry the four tags above; their own are */
 #define SG_STAGE_DEF_SCALE 64     /* scale / clip decision of a stage that is not first, and of the MFCC, from the pass's rows */
 #define SG_STAGE_DEF_REPLICATE 65 /* the iterate copied once per EOT repeat of the pass */
 #define SG_STAGE_DEF_REP_SUM 66   /* repeat sum of the cotangents, carried on or turned into the sign step (one launch) */
@@ -639,6 +639,36 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
 int sg_wav_rep_sum_update(sg_ctx* ctx, const float* planes_dev, int32_t G, int64_t n, const float* carry_dev,
                           float* sum_out_dev, float* x_dev, const float* lower_dev, const float* upper_dev,
                           float step_size, int32_t grad_sign, void* stream);
+
+/* ---- input-level defenses inside the device-resident AudioNet PGD loops ---------------------------------------
+ * sg_xv_pgd_run_defended transposed onto sg_an_pgd_run (feco == NULL) and onto sg_an_pgd_run_feco (feco != NULL): the same
+ * chain of 1 .. SG_WAV_CHAIN_MAX stages in front of the log-mel front-end, the same stage kernels, the same checks, all made
+ * before the first launch.  Arguments and outputs as sg_an_pgd_run; params->dither is not read (AudioNet has no dither).
+ *
+ * feco == NULL.  reps = eot_size when the chain holds SG_TD_AT, else 1; G = min(reps, 65535 / B) repeats per pass, every
+ * repeat its own row (row = repeat * B + utterance).  Per step `it` and group starting at repeat g0: chain forward, log-mel /
+ * CNN / head on the defended rows, the adjoint to a workspace plane, chain backward last stage first, then the repeat sum
+ * ((g0 + g1) + g2) + ... in float32 (sg_wav_rep_sum_update), carried to the next group or turned into the sign step.  AT's
+ * key for a pass is seed + it * 0x9E3779B97F4A7C15 + g0 * 0xC2B2AE3D27D4EB4F, rep_rows = B when the pass holds more than one
+ * repeat.  Per-step records: loss averaged, decision voted over the step's repeats.  The final pass is one forward repeat,
+ * chain included.  A chain of SG_TD_QT stages only (identity backward) keeps sg_an_pgd_run's pass: B defended rows, and the
+ * log-mel adjoint steps the iterate directly (the fused overlap-add and its waveform ping-pong where they apply).
+ *
+ * feco != NULL (a level-1 FeCoDefense behind the chain; B >= 2 as in sg_an_pgd_run_feco): the chain must be deterministic.
+ * Per step: chain forward on B rows, log-mel, sg_feco_kmeans_compress with eot_size repeats when random_init (key
+ * feco->seed + it * 0x9E3779B97F4A7C15) else one, the CNN on the repeats as one batch, sg_feco_compress_backward_reps (the
+ * repeats summed at the feature level), ONE log-mel adjoint to a plane of B rows, chain backward, the sign step.
+ *
+ * Scale decisions: the iterate's (a QT / filter stage that is first) once per call; a later stage's and the model's range
+ * decision from their own input at every pass, over the rows of that pass.
+ * Nothing is allocated, synchronised or copied to the host inside the loop.
+ * SG_ERR_ARG before any launch: what sg_xv_pgd_run_defended refuses about the chain, eot_size % eot_batch_size != 0, more
+ * than 65535 rows per pass, feco with B < 2, feco with SG_TD_AT in the chain, feco->k outside what the AudioNet stack takes. */
+int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev,
+                           const float* upper_dev, int32_t B, int32_t T, const sg_pgd_params* params,
+                           const sg_wav_stage* chain, int32_t n_stages, const sg_feco_params* feco, uint8_t* success_dev,
+                           int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* loss_trace_dev,
+                           int64_t* decision_trace_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ EXPORTS = (
     "sg_xv_mfcc_backward", "sg_xv_cmvn_backward", "sg_feco_kmeans", "sg_feco_kmeans_seeded", "sg_feco_kmeans_compress", "sg_feco_compress_backward_reps", "sg_feco_compress", "sg_feco_compress_backward", "sg_feco_warped",
     "sg_an_logmel_backward", "sg_an_configure", "sg_xv_configure", "sg_xv_enroll_override", "sg_health", "sg_set_streamk", "sg_debug_lose_handoffs", "sg_debug_feco_epoch", "sg_feco_set_two_cu", "sg_trace_begin", "sg_trace_end",
     "sg_wav_defense_forward", "sg_wav_defense_backward", "sg_wav_filter_forward", "sg_wav_filter_backward",
-    "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update",
+    "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update", "sg_an_pgd_run_defended",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -107,7 +107,7 @@ class _WavStageU(C.Union):
 
 
 class WavStage(C.Structure):
-    """sg_wav_stage: one stage of sg_xv_pgd_run_defended's chain"""
+    """sg_wav_stage: one stage of the chain of sg_xv_pgd_run_defended / sg_an_pgd_run_defended"""
     _fields_ = [("tag", C.c_int32), ("u", _WavStageU)]
 
 
@@ -158,6 +158,8 @@ def load():
         "sg_xv_pgd_run": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),
         "sg_xv_pgd_run_defended": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(WavStage), i32,
                                              vp, vp, vp, vp, vp, vp, vp]),
+        "sg_an_pgd_run_defended": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(WavStage), i32,
+                                             C.POINTER(FecoParams), vp, vp, vp, vp, vp, vp, vp]),
         "sg_wav_rep_sum_update": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, f32, i32, vp]),
         "sg_cw2_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp, vp, vp]),
         "sg_nes_queries": (C.c_int, [vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i64, i32, vp, vp, vp, vp]),

@@ -5,8 +5,9 @@ and nothing between attack and model needs Python (no defense wrapper), the whol
 over the front-end's random dither included -- max_iter x (forward, hand-coded backward, sign step,
 projection) + the final forward-only pass -- is ONE C-ABI call (``model.pgd_run``).  A wrapper that
 carries only native waveform-level defenses in sequential order runs the same way, the chain inside
-the loop (``model.pgd_run_defended``).  Otherwise the same loop runs step by step over
-``model.loss_grad`` / ``model.pgd_update``.
+the loop (``model.pgd_run_defended``), and so does such a chain in front of one FeCoDefense on AudioNet
+(``model.pgd_run_defended_feco``).  Otherwise the same loop runs step by step over ``model.loss_grad`` /
+``model.pgd_update``.
 """
 import numpy as np
 import torch
@@ -63,7 +64,7 @@ class FGSM(Attack):
 
     def _fused_input_chain(self):
         """The defense objects of ``defended_model(base, [(0, d1), (0, d2), ...])`` in chain order when the base model runs
-        that loop on the device (xv_plda.pgd_run_defended): sequential order, every defense at the waveform level and a
+        that loop on the device (xv_plda / audionet_csine ``pgd_run_defended``): sequential order, every defense at the waveform level and a
         native waveform defense object (defense.time_domain / defense.frequency_domain) as it stands -- no BPDA wrapper,
         no Python callable, no explicit noise.  Else None: the step loop below."""
         m = self.model
@@ -86,6 +87,31 @@ class FGSM(Attack):
             return None
         return chain
 
+    def _fused_chain_feco(self, n_audios):
+        """(chain, feco) of ``defended_model(base, [(0, d1), ..., (1, FeCoDefense)])`` when the base model runs that loop on the
+        device (audionet_csine.pgd_run_defended_feco): sequential order, every level-0 defense a native waveform defense object
+        as it stands and not randomised (the clusterings' gradients are summed behind ONE chain pass), exactly one level-1
+        defense and that a FeCoDefense, nothing at any other level, at least two utterances (``_fused_feco``), both fuse flags
+        on.  Else None: the step loop below."""
+        m = self.model
+        defense = getattr(m, 'defense', None)
+        base = getattr(m, 'base_model', None)
+        if not (self.fuse_defended and self.fuse_input_defenses) or not defense or base is None or n_audios < 2:
+            return None
+        if not hasattr(base, 'pgd_run_defended_feco') or getattr(m, 'order', None) != 'sequential':
+            return None
+        from ..defense.feature_level import FeCoDefense
+        from ..defense.time_domain import _WavDefense
+        chain = [d for flag, d in defense if flag == 0]
+        rest = [(flag, d) for flag, d in defense if flag != 0]
+        if len(rest) != 1 or rest[0][0] != 1 or not isinstance(rest[0][1], FeCoDefense):
+            return None
+        if not 1 <= len(chain) <= 8 or chain != m.flag2defense.get(0, []) or m.flag2defense.get(1, []) != [rest[0][1]]:
+            return None
+        if not all(isinstance(d, _WavDefense) and not getattr(d, 'randomised', False) for d in chain):
+            return None
+        return chain, rest[0][1]
+
     def _can_fuse(self):
         m = self.model
         if getattr(m, 'defense', None) is not None:
@@ -101,7 +127,11 @@ class FGSM(Attack):
 
     def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, feco=None, chain=None):
         base = getattr(self.model, 'base_model', self.model)
-        if chain is not None:
+        if chain is not None and feco is not None:
+            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_defended_feco(
+                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, chain, feco,
+                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
+        elif chain is not None:
             x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_defended(
                 x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, chain,
                 self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
@@ -130,6 +160,9 @@ class FGSM(Attack):
         chain = self._fused_input_chain()
         if chain is not None:
             return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, chain=chain)
+        both = self._fused_chain_feco(x_batch.shape[0])
+        if both is not None:
+            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, feco=both[1], chain=both[0])
         x_batch = x_batch.clone()
         lower = lower.expand_as(x_batch).contiguous()
         upper = upper.expand_as(x_batch).contiguous()

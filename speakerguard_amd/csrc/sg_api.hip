@@ -503,37 +503,6 @@ int grow_eot_rows(sg_ctx* ctx, size_t rows, hipStream_t s) {
     return SG_OK;
 }
 
-// buffers of the defended loop for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the
-// replicated iterate and the two cotangent planes.  Grown here, before the loop; a request the buffers already cover costs nothing.
-int ensure_def_workspace(sg_ctx* ctx, int rows, int T, int n_out, int n_saved, bool rep, hipStream_t s) {
-    DefWorkspace& dw = ctx->def_ws;
-    const size_t plane = (size_t)rows * T;
-    if (dw.scales && plane <= dw.plane && rows <= dw.rows && n_out <= dw.n_out && n_saved <= dw.n_saved && (dw.rep || !rep)) return SG_OK;
-    SG_HIP(hipStreamSynchronize(s));  // nothing enqueued may still use the old buffers
-    const size_t cp = std::max(plane, dw.plane);
-    const int cr = std::max(rows, dw.rows), co = std::max(n_out, dw.n_out), cs = std::max(n_saved, dw.n_saved);
-    const bool crep = rep || dw.rep;
-    free_pool(dw.allocs);
-    dw = DefWorkspace();
-    int rc = 0;
-    for (int i = 0; i < co; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.out[i], cp);
-    for (int i = 0; i < cs; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.saved[i], cp);
-    rc |= dev_alloc(ctx, dw.allocs, &dw.stats, (size_t)SG_WAV_CHAIN_MAX * 3 * cr);
-    rc |= dev_alloc(ctx, dw.allocs, &dw.scales, SG_WAV_CHAIN_MAX);
-    if (crep) {
-        rc |= dev_alloc(ctx, dw.allocs, &dw.x_rep, cp);
-        rc |= dev_alloc(ctx, dw.allocs, &dw.g[0], cp);
-        rc |= dev_alloc(ctx, dw.allocs, &dw.g[1], cp);
-    }
-    if (rc) {
-        free_pool(dw.allocs);
-        dw = DefWorkspace();
-        return fail(ctx, SG_ERR_HIP, "workspace allocation of the defended loop failed: %s", ctx->err.c_str());
-    }
-    dw.plane = cp; dw.rows = cr; dw.n_out = co; dw.n_saved = cs; dw.rep = crep;
-    return SG_OK;
-}
-
 struct LoopOut {  // a loop's caller buffers: the state at the final pass, and the optional per-step records
     uint8_t* success; int64_t* decisions; float* scores; float* loss; float* loss_trace; int64_t* decision_trace;
 };
@@ -570,6 +539,128 @@ int run_loop_tail(sg_ctx* ctx, const sg_loss_spec& loss, const LoopOut& o, int B
 }
 
 }  // namespace
+
+// ---- the chain of the defended device loops (declared in sg_internal.h: sg_api_audionet.hip runs it too)
+namespace sg {
+
+int ensure_def_workspace(sg_ctx* ctx, int rows, int T, int n_out, int n_saved, bool rep, hipStream_t s) {
+    DefWorkspace& dw = ctx->def_ws;
+    const size_t plane = (size_t)rows * T;
+    if (dw.scales && plane <= dw.plane && rows <= dw.rows && n_out <= dw.n_out && n_saved <= dw.n_saved && (dw.rep || !rep)) return SG_OK;
+    SG_HIP(hipStreamSynchronize(s));  // nothing enqueued may still use the old buffers
+    const size_t cp = std::max(plane, dw.plane);
+    const int cr = std::max(rows, dw.rows), co = std::max(n_out, dw.n_out), cs = std::max(n_saved, dw.n_saved);
+    const bool crep = rep || dw.rep;
+    free_pool(dw.allocs);
+    dw = DefWorkspace();
+    int rc = 0;
+    for (int i = 0; i < co; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.out[i], cp);
+    for (int i = 0; i < cs; ++i) rc |= dev_alloc(ctx, dw.allocs, &dw.saved[i], cp);
+    rc |= dev_alloc(ctx, dw.allocs, &dw.stats, (size_t)SG_WAV_CHAIN_MAX * 3 * cr);
+    rc |= dev_alloc(ctx, dw.allocs, &dw.scales, SG_WAV_CHAIN_MAX);
+    if (crep) {
+        rc |= dev_alloc(ctx, dw.allocs, &dw.x_rep, cp);
+        rc |= dev_alloc(ctx, dw.allocs, &dw.g[0], cp);
+        rc |= dev_alloc(ctx, dw.allocs, &dw.g[1], cp);
+    }
+    if (rc) {
+        free_pool(dw.allocs);
+        dw = DefWorkspace();
+        return fail(ctx, SG_ERR_HIP, "workspace allocation of the defended loop failed: %s", ctx->err.c_str());
+    }
+    dw.plane = cp; dw.rows = cr; dw.n_out = co; dw.n_saved = cs; dw.rep = crep;
+    return SG_OK;
+}
+
+int def_chain_check(sg_ctx* ctx, const char* who, const sg_wav_stage* chain, int n_stages, DefChainInfo* info) {
+    int rc;
+    if (!chain || n_stages < 1 || n_stages > SG_WAV_CHAIN_MAX)
+        return fail(ctx, SG_ERR_ARG, "%s: a chain of 1 .. %d stages is needed (%d)", who, SG_WAV_CHAIN_MAX, n_stages);
+    info->randomised = false;
+    info->identity = true;
+    info->n_saved = 0;
+    for (int i = 0; i < n_stages; ++i) {
+        const sg_wav_stage& st = chain[i];
+        if (st.tag == SG_WAV_STAGE_DEFENSE) {
+            if ((rc = wav_defense_check_spec(ctx, who, &st.u.defense))) return rc;
+            if (st.u.defense.noise_dev) return fail(ctx, SG_ERR_ARG, "%s: stage %d carries noise_dev: explicit noise is not supported in the loop", who, i);
+            info->randomised |= st.u.defense.kind == SG_TD_AT;
+            info->identity &= st.u.defense.kind == SG_TD_QT;
+            info->n_saved += st.u.defense.kind == SG_TD_MS;
+        } else if (st.tag == SG_WAV_STAGE_FILTER) {
+            if ((rc = wav_filter_check_spec(ctx, who, &st.u.filter))) return rc;
+            info->identity = false;
+            ++info->n_saved;
+        } else {
+            return fail(ctx, SG_ERR_ARG, "%s: stage %d has the unknown tag %d", who, i, st.tag);
+        }
+    }
+    return SG_OK;
+}
+
+// does the stage read a scale / clip decision?  (QT / BDR always; a filter under the reference's per-call rule)
+static bool def_stage_needs_scale(const sg_wav_stage& st) {
+    return st.tag == SG_WAV_STAGE_DEFENSE ? st.u.defense.kind == SG_TD_QT : st.u.filter.clip_mode == SG_FD_CLIP_RANGE;
+}
+
+int def_chain_first_scale(sg_ctx* ctx, const sg_wav_stage* chain, const float* x, int64_t n, hipStream_t s) {
+    if (def_stage_needs_scale(chain[0])) SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(x, n, ctx->range_scratch, ctx->def_ws.scales, 0, s));
+    return SG_OK;
+}
+
+int def_chain_forward(sg_ctx* ctx, const sg_wav_stage* chain, int n_stages, const float* x, int rows, int T, uint64_t pass_key,
+                      int rep_rows, DefChainTape* tape, const float** out, hipStream_t s) {
+    DefWorkspace& dw = ctx->def_ws;
+    const float* cur = x;
+    int rc, next_saved = 0;
+    for (int i = 0; i < n_stages; ++i) {
+        tape->in[i] = cur;
+        if (i > 0 && def_stage_needs_scale(chain[i]))
+            SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(cur, (int64_t)rows * T, ctx->range_scratch, dw.scales + i, 0, s));
+        if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
+            sg_wav_defense& sd = tape->spec[i];
+            sd = chain[i].u.defense;
+            void* saved = nullptr;
+            if (sd.kind == SG_TD_QT) saved = dw.scales + i;
+            else if (sd.kind == SG_TD_MS) saved = dw.saved[next_saved++];
+            else if (sd.kind == SG_TD_AT) {
+                saved = dw.stats + (size_t)i * 3 * dw.rows;
+                sd.seed += pass_key;
+                sd.rep_rows = rep_rows;
+            }
+            tape->saved[i] = saved;
+            if ((rc = sg_wav_defense_forward(ctx, &sd, cur, rows, T, dw.out[i], saved, s))) return rc;
+        } else {
+            int8_t* mask = dw.saved[next_saved++];
+            tape->saved[i] = mask;
+            if ((rc = sg_wav_filter_forward(ctx, &chain[i].u.filter, cur, rows, T, dw.scales + i, dw.out[i], mask, s))) return rc;
+        }
+        cur = dw.out[i];
+    }
+    *out = cur;
+    return SG_OK;
+}
+
+int def_chain_backward(sg_ctx* ctx, const sg_wav_stage* chain, int n_stages, const DefChainTape& tape, int rows, int T, int* gi_out,
+                       hipStream_t s) {
+    DefWorkspace& dw = ctx->def_ws;
+    int rc, gi = 0;
+    for (int i = n_stages - 1; i >= 0; --i) {
+        if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
+            if (tape.spec[i].kind == SG_TD_QT) continue;  // BPDA's identity: nothing to launch
+            rc = sg_wav_defense_backward(ctx, &tape.spec[i], tape.in[i], dw.g[gi], tape.saved[i], rows, T, dw.g[gi ^ 1], s);
+        } else {
+            rc = sg_wav_filter_backward(ctx, &chain[i].u.filter, dw.g[gi], static_cast<const int8_t*>(tape.saved[i]), rows, T,
+                                        dw.g[gi ^ 1], s);
+        }
+        if (rc) return rc;
+        gi ^= 1;
+    }
+    *gi_out = gi;
+    return SG_OK;
+}
+
+}  // namespace sg
 
 // ============================================================================== C-ABI
 extern "C" {
@@ -1079,26 +1170,10 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
     const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
     if (eot_size % eot_bs) return fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
     // ---- the chain: everything a stage call would refuse, before the first launch
-    if (!chain || n_stages < 1 || n_stages > SG_WAV_CHAIN_MAX)
-        return fail(ctx, SG_ERR_ARG, "%s: a chain of 1 .. %d stages is needed (%d)", who, SG_WAV_CHAIN_MAX, n_stages);
-    bool randomised = false, identity = true;
-    int n_saved = 0;
-    for (int i = 0; i < n_stages; ++i) {
-        const sg_wav_stage& st = chain[i];
-        if (st.tag == SG_WAV_STAGE_DEFENSE) {
-            if ((rc = wav_defense_check_spec(ctx, who, &st.u.defense))) return rc;
-            if (st.u.defense.noise_dev) return fail(ctx, SG_ERR_ARG, "%s: stage %d carries noise_dev: explicit noise is not supported in the loop", who, i);
-            randomised |= st.u.defense.kind == SG_TD_AT;
-            identity &= st.u.defense.kind == SG_TD_QT;
-            n_saved += st.u.defense.kind == SG_TD_MS;
-        } else if (st.tag == SG_WAV_STAGE_FILTER) {
-            if ((rc = wav_filter_check_spec(ctx, who, &st.u.filter))) return rc;
-            identity = false;
-            ++n_saved;
-        } else {
-            return fail(ctx, SG_ERR_ARG, "%s: stage %d has the unknown tag %d", who, i, st.tag);
-        }
-    }
+    DefChainInfo ci;
+    if ((rc = def_chain_check(ctx, who, chain, n_stages, &ci))) return rc;
+    const bool randomised = ci.randomised, identity = ci.identity;
+    const int n_saved = ci.n_saved;
     // Repeats: a randomised stage (AT) or the dither makes the repeats of a step differ; otherwise one pass stands for all.
     const int reps = (randomised || p->dither.dither != 0.f) ? eot_size : 1;
     hipStream_t s = (hipStream_t)stream;
@@ -1122,12 +1197,8 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
     if (want_rec && G < reps && (rc = grow_eot_rows(ctx, (size_t)reps * B, s))) return rc;
     const LoopOut out{success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
     const size_t n = (size_t)B * T;
-    // does stage i read a scale / clip decision?  (QT / BDR always; a filter under the reference's per-call rule)
-    const auto needs_scale = [&](int i) {
-        return chain[i].tag == SG_WAV_STAGE_DEFENSE ? chain[i].u.defense.kind == SG_TD_QT : chain[i].u.filter.clip_mode == SG_FD_CLIP_RANGE;
-    };
     // the iterate is clamped into [lower, upper] within [-1, 1] at every step: its own decision is taken once
-    if (needs_scale(0)) SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(x_adv_dev, (int64_t)n, ctx->range_scratch, dw.scales, 0, s));
+    if ((rc = def_chain_first_scale(ctx, chain, x_adv_dev, (int64_t)n, s))) return rc;
 
     for (int it = 0; it <= p->max_iter; ++it) {
         const bool last = it == p->max_iter;
@@ -1145,34 +1216,8 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
                 trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
                 cur = dw.x_rep;
             }
-            sg_wav_defense spec[SG_WAV_CHAIN_MAX];      // the pass's specs (AT: with the pass's key), reused by the backward
-            const float* stage_in[SG_WAV_CHAIN_MAX];
-            void* stage_saved[SG_WAV_CHAIN_MAX];
-            int next_saved = 0;
-            for (int i = 0; i < n_stages; ++i) {
-                stage_in[i] = cur;
-                if (i > 0 && needs_scale(i))
-                    SG_STAGE(SG_STAGE_DEF_SCALE, launch_input_scale(cur, (int64_t)rows * T, ctx->range_scratch, dw.scales + i, 0, s));
-                if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
-                    sg_wav_defense& sd = spec[i];
-                    sd = chain[i].u.defense;
-                    void* saved = nullptr;
-                    if (sd.kind == SG_TD_QT) saved = dw.scales + i;
-                    else if (sd.kind == SG_TD_MS) saved = dw.saved[next_saved++];
-                    else if (sd.kind == SG_TD_AT) {
-                        saved = dw.stats + (size_t)i * 3 * dw.rows;
-                        sd.seed += pass_key;
-                        sd.rep_rows = Gi > 1 ? B : 0;
-                    }
-                    stage_saved[i] = saved;
-                    if ((rc = sg_wav_defense_forward(ctx, &sd, cur, rows, T, dw.out[i], saved, s))) return rc;
-                } else {
-                    int8_t* mask = dw.saved[next_saved++];
-                    stage_saved[i] = mask;
-                    if ((rc = sg_wav_filter_forward(ctx, &chain[i].u.filter, cur, rows, T, dw.scales + i, dw.out[i], mask, s))) return rc;
-                }
-                cur = dw.out[i];
-            }
+            DefChainTape tape;  // reused by the backward
+            if ((rc = def_chain_forward(ctx, chain, n_stages, cur, rows, T, pass_key, Gi > 1 ? B : 0, &tape, &cur, s))) return rc;
             // ---- the model on the defended waveform
             sg_dither dz = p->dither;
             dz.seed += pass_key;
@@ -1195,17 +1240,7 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
             if ((rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, dw.g[0], nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
             // ---- chain backward, last stage first
             int gi = 0;
-            for (int i = n_stages - 1; i >= 0; --i) {
-                if (chain[i].tag == SG_WAV_STAGE_DEFENSE) {
-                    if (spec[i].kind == SG_TD_QT) continue;  // BPDA's identity: nothing to launch
-                    rc = sg_wav_defense_backward(ctx, &spec[i], stage_in[i], dw.g[gi], stage_saved[i], rows, T, dw.g[gi ^ 1], s);
-                } else {
-                    rc = sg_wav_filter_backward(ctx, &chain[i].u.filter, dw.g[gi], static_cast<const int8_t*>(stage_saved[i]), rows, T,
-                                                dw.g[gi ^ 1], s);
-                }
-                if (rc) return rc;
-                gi ^= 1;
-            }
+            if ((rc = def_chain_backward(ctx, chain, n_stages, tape, rows, T, &gi, s))) return rc;
             // ---- the repeats' sum, carried to the next group or turned into the step
             SG_STAGE(SG_STAGE_DEF_REP_SUM,
                      launch_wav_rep_sum_update(dw.g[gi], Gi, (int64_t)n, g0 > 0 ? w.grad : nullptr, final_group ? nullptr : w.grad,

@@ -1,5 +1,6 @@
 // C-ABI entry points of the AudioNet CSI-NE path (include/speakerguard_hip.h, "sg_an_*"):
 // model load (BatchNorm folding), workspace, forward / backward / PGD kernel sequences.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -536,6 +537,168 @@ float* an_step_target(sg_ctx* ctx, const AnDims& d) {
     return w.x_alt;
 }
 
+// ---- the defended loops (sg_an_pgd_run_defended)
+struct AnDefCall {  // the caller's buffers and the chain, as the entry point received them
+    float* x_adv; const int64_t* y; const float* lower; const float* upper;
+    int B, T;
+    const sg_pgd_params* p;
+    const sg_wav_stage* chain; int n_stages;
+    const sg_feco_params* feco;
+    uint8_t* success; int64_t* decisions; float* scores; float* loss; float* loss_trace; int64_t* decision_trace;
+};
+
+// an on-demand workspace buffer of at least `need` elements (grown before a loop: the stream drains first)
+template <typename T>
+int an_grow(sg_ctx* ctx, T** buf, size_t* cap, size_t need, hipStream_t s) {
+    AnWorkspace& w = ctx->an_ws;
+    if (*buf && *cap >= need) return SG_OK;
+    if (*buf) {
+        AN_HIP(hipStreamSynchronize(s));
+        (void)hipFree(*buf);
+        w.allocs.erase(std::remove(w.allocs.begin(), w.allocs.end(), static_cast<void*>(*buf)), w.allocs.end());
+        *buf = nullptr;
+        *cap = 0;
+    }
+    int rc = an_alloc(ctx, w.allocs, buf, need);
+    if (rc) return rc;
+    *cap = need;
+    return SG_OK;
+}
+
+// Chains with a backward of their own, no feature-level stage: every EOT repeat is a row of its own through chain, model and
+// both backwards (G repeats per pass); the repeats' cotangents are summed after the chain's backward, in repeat order.
+int an_def_loop_rows(sg_ctx* ctx, const AnDefCall& c, AnDims d, int reps, int G, hipStream_t s) {
+    AnWorkspace& w = ctx->an_ws;
+    DefWorkspace& dw = ctx->def_ws;
+    const sg_pgd_params* p = c.p;
+    const int B = c.B, T = c.T, F = d.F;
+    const size_t n = (size_t)B * T;
+    const AnKnobs knobs = an_knobs();
+    const int tail = reps % G;  // repeats of a last, smaller group
+    const AnNetPlan full_plan = an_plan(ctx, knobs, B * G, F, true), tail_plan = an_plan(ctx, knobs, B * (tail ? tail : G), F, true),
+                    final_plan = an_plan(ctx, knobs, B, F, false);
+    const bool want_rec = c.loss_trace || c.decision_trace;
+    int rc;
+    for (int it = 0; it <= p->max_iter; ++it) {
+        const bool last = it == p->max_iter;  // the final pass is one forward repeat, chain included
+        const int nrep = last ? 1 : reps;
+        float* lrec = c.loss_trace ? c.loss_trace + (size_t)it * B : nullptr;
+        int64_t* drec = c.decision_trace ? c.decision_trace + (size_t)it * B : nullptr;
+        for (int g0 = 0; g0 < nrep; g0 += G) {
+            const int Gi = std::min(G, nrep - g0), rows = B * Gi;
+            const bool final_group = g0 + Gi >= nrep;
+            const uint64_t pass_key = (uint64_t)it * 0x9E3779B97F4A7C15ull + (uint64_t)g0 * 0xC2B2AE3D27D4EB4Full;
+            const float* cur = c.x_adv;
+            if (Gi > 1) {
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
+                for (int r = 0; r < Gi; ++r)
+                    AN_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, c.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
+                cur = dw.x_rep;
+            }
+            DefChainTape tape;
+            if ((rc = def_chain_forward(ctx, c.chain, c.n_stages, cur, rows, T, pass_key, Gi > 1 ? B : 0, &tape, &cur, s))) return rc;
+            d.B = rows;
+            d.keep_scale = false;  // the model's range decision: from the defended rows of every pass, as a model call takes it
+            if ((rc = an_frontend_forward(ctx, cur, d, s))) return rc;
+            // per-step records (attack/FGSM.py:50-58): loss averaged, decision voted over ALL repeats of the step.  One pass of
+            // several repeats records its rows and reduces them right after the head; when the repeats run as several passes
+            // (G < reps) every pass leaves its rows in repeat order and the last one reduces them.
+            const bool direct = nrep == 1, grouped = nrep > G;
+            float* lrows = grouped ? w.eot_loss_rows + (size_t)g0 * B : w.trace_l;
+            int64_t* drows = grouped ? w.eot_dec_rows + (size_t)g0 * B : w.trace_d;
+            float* ltr = !want_rec ? nullptr : (direct && lrec ? lrec : lrows);
+            int64_t* dtr = !want_rec ? nullptr : (direct && drec ? drec : drows);
+            const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? c.scores : nullptr, last ? c.decisions : nullptr,
+                                                 last ? c.loss : nullptr, ltr, dtr, last ? c.success : nullptr);
+            const AnEotRecords reduce = {nrep, B, lrec, drec};
+            const AnNetPlan& plan = last ? final_plan : (Gi == G ? full_plan : tail_plan);
+            rc = an_net_step(ctx, plan, w.feats, rows, head, want_rec && !direct && !grouped ? &reduce : nullptr, last ? nullptr : w.dfeats, s);
+            if (rc) return rc;
+            if (want_rec && grouped && final_group)
+                AN_HIP(launch_eot_trace_reduce(w.eot_loss_rows, w.eot_dec_rows, nrep, B, lrec, drec, s));
+            if (last) continue;
+            if ((rc = an_frontend_backward(ctx, cur, d, w.dfeats, dw.g[0], nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+            int gi = 0;
+            if ((rc = def_chain_backward(ctx, c.chain, c.n_stages, tape, rows, T, &gi, s))) return rc;
+            // the repeats' sum, carried to the next group or turned into the step
+            AN_STAGE(SG_STAGE_DEF_REP_SUM,
+                     launch_wav_rep_sum_update(dw.g[gi], Gi, (int64_t)n, g0 > 0 ? w.grad_carry : nullptr, final_group ? nullptr : w.grad_carry,
+                                               final_group ? c.x_adv : nullptr, c.lower, c.upper, p->step_size, p->grad_sign, s));
+        }
+    }
+    return SG_OK;
+}
+
+// One pass of B defended rows per step: a QT / BDR-only chain (identity backward) in front of the model, and any
+// deterministic chain in front of FeCo (R clusterings per step, their gradients summed at the feature level).  With an
+// identity backward the log-mel adjoint steps the iterate directly (sg_an_pgd_run's waveform ping-pong); otherwise it
+// writes a plane, the chain's backward follows and the repeat-sum kernel over that one plane is the update.
+int an_def_loop_single(sg_ctx* ctx, const AnDefCall& c, AnDims d, bool identity, int R, hipStream_t s) {
+    AnWorkspace& w = ctx->an_ws;
+    DefWorkspace& dw = ctx->def_ws;
+    const sg_pgd_params* p = c.p;
+    const sg_feco_params* f = c.feco;
+    const int B = c.B, T = c.T, F = d.F, Fnet = f ? f->k : F;
+    const size_t n = (size_t)B * T;
+    const AnKnobs knobs = an_knobs();
+    const AnNetPlan step_plan = an_plan(ctx, knobs, B * R, Fnet, true), final_plan = an_plan(ctx, knobs, B, Fnet, false);
+    d.B = B;
+    float* xc = c.x_adv;  // waveform ping-pong of the fused overlap-add (sg_an_pgd_run); a chain with a backward steps in place
+    float* xn = identity ? an_step_target(ctx, d) : nullptr;
+    if (!xn) xn = c.x_adv;
+    int rc;
+    for (int it = 0; it <= p->max_iter; ++it) {
+        const bool last = it == p->max_iter;
+        const int Ri = last ? 1 : R, rows = B * Ri;
+        const float* cur = xc;
+        DefChainTape tape;
+        if ((rc = def_chain_forward(ctx, c.chain, c.n_stages, cur, B, T, 0, 0, &tape, &cur, s))) return rc;
+        d.keep_scale = false;  // the model's range decision: from the defended rows of every pass
+        if ((rc = an_frontend_forward(ctx, cur, d, s))) return rc;
+        const float* net_in = w.feats;
+        if (f) {
+            const uint64_t key = f->seed + (uint64_t)it * 0x9E3779B97F4A7C15ull;  // repeat r: + r * 0xC2B2AE3D27D4EB4F
+            trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 0);
+            rc = sg_feco_kmeans_compress(ctx, w.feats, B, F, kAnMel, f->k, f->max_iter, f->random_init, key, f->index_base, Ri,
+                                         w.feco_ids, w.feco_out, w.feco_cnt, s);
+            if (rc) return rc;
+            trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 1);
+            net_in = w.feco_out;
+        }
+        float* lrec = c.loss_trace ? c.loss_trace + (size_t)it * B : nullptr;
+        int64_t* drec = c.decision_trace ? c.decision_trace + (size_t)it * B : nullptr;
+        const bool direct = Ri == 1, rec = lrec || drec;
+        float* ltr = !rec ? nullptr : (direct && lrec ? lrec : w.trace_l);
+        int64_t* dtr = !rec ? nullptr : (direct && drec ? drec : w.trace_d);
+        const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? c.scores : nullptr, last ? c.decisions : nullptr,
+                                             last ? c.loss : nullptr, ltr, dtr, last ? c.success : nullptr);
+        const AnEotRecords reduce = {Ri, B, lrec, drec};
+        rc = an_net_step(ctx, last ? final_plan : step_plan, net_in, rows, head, rec && !direct ? &reduce : nullptr,
+                         last ? nullptr : (f ? w.dfeco : w.dfeats), s);
+        if (rc) return rc;
+        if (last) break;
+        if (f) {
+            trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 0);
+            if ((rc = sg_feco_compress_backward_reps(ctx, w.dfeco, w.feco_ids, w.feco_cnt, B, F, kAnMel, f->k, 1, Ri, w.dfeats, s))) return rc;
+            trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 1);
+        }
+        if (identity) {  // d loss / d defended IS d loss / d iterate: straight into the update
+            rc = an_frontend_backward(ctx, cur, d, w.dfeats, nullptr, xc, xn, c.lower, c.upper, p->step_size, p->grad_sign, s);
+            if (rc) return rc;
+            if (xn != xc) std::swap(xc, xn);
+            continue;
+        }
+        if ((rc = an_frontend_backward(ctx, cur, d, w.dfeats, dw.g[0], nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+        int gi = 0;
+        if ((rc = def_chain_backward(ctx, c.chain, c.n_stages, tape, B, T, &gi, s))) return rc;
+        AN_STAGE(SG_STAGE_DEF_REP_SUM, launch_wav_rep_sum_update(dw.g[gi], 1, (int64_t)n, nullptr, nullptr, xc, c.lower, c.upper, p->step_size,
+                                                                 p->grad_sign, s));
+    }
+    if (xc != c.x_adv) AN_HIP(hipMemcpyAsync(c.x_adv, xc, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return SG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -836,6 +999,66 @@ int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
     }
     if (xc != x_adv_dev) AN_HIP(hipMemcpyAsync(x_adv_dev, xc, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SG_OK;
+}
+
+int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
+                           int32_t B, int32_t T, const sg_pgd_params* p, const sg_wav_stage* chain, int32_t n_stages,
+                           const sg_feco_params* feco, uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev,
+                           float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev, void* stream) {
+    static const char* who = "sg_an_pgd_run_defended";
+    int rc;
+    if (!ctx) return SG_ERR_ARG;
+    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return an_fail(ctx, SG_ERR_ARG, "NULL argument");
+    if (B < 1 || T < kAnFft) return an_fail(ctx, SG_ERR_ARG, "need B >= 1 and a waveform of at least one 1024-sample STFT frame");
+    if (p->max_iter < 0) return an_fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
+    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
+    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
+    if (eot_size % eot_bs) return an_fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
+    // ---- the chain: everything a stage call would refuse, before the first launch
+    DefChainInfo ci;
+    if ((rc = def_chain_check(ctx, who, chain, n_stages, &ci))) return rc;
+    if (feco) {
+        // (one utterance: the reference drops empty clusters, sg_an_pgd_run_feco)
+        if (B < 2) return an_fail(ctx, SG_ERR_ARG, "%s: the FeCo loop needs a batch of at least 2 utterances", who);
+        // the clusterings' gradients are summed at the feature level, behind ONE chain pass: that pass must not be random
+        if (ci.randomised) return an_fail(ctx, SG_ERR_ARG, "%s: a randomised stage (AT) in front of FeCo is not supported in the loop", who);
+    }
+    // Repeats: AT makes the repeats of a step differ (AudioNet has no dither); otherwise one pass stands for all.  With FeCo
+    // only the clustering is repeated (R times, behind one chain and front-end pass).
+    const int reps = !feco && ci.randomised ? eot_size : 1;
+    const int R = feco && feco->random_init ? eot_size : 1;
+    long cap = 65535;  // rows a stage kernel takes
+    if (const char* e = sg_tune_env("SG_EOT_MAX_ROWS")) cap = std::min<long>(cap, atol(e));  // tests: force groups
+    const int G = (int)std::min<long>(reps, std::max<long>(1, cap / B));
+    const bool per_row = !ci.identity;  // the chain has a backward of its own: cotangent planes are needed
+    const int chain_rows = B * G;
+    if (chain_rows > 65535) return an_fail(ctx, SG_ERR_ARG, "%s: %d rows per pass, the stage kernels take at most 65535: split the batch", who, chain_rows);
+    AnDims d;
+    if ((rc = an_check(ctx, feco ? B * R : chain_rows, T, 0, &d))) return rc;  // workspace for the largest pass
+    if (feco) {
+        const bool k_ok = feco->k >= 1 && feco->k <= d.F && feco->max_iter >= 1;
+        if (!an_plan(ctx, an_knobs(), B, k_ok ? feco->k : 0, false).frames_ok)
+            return an_fail(ctx, SG_ERR_ARG, "FeCo: need 1 <= k <= %d frames, enough of them for the AudioNet stack, max_iter >= 1", d.F);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = ensure_def_workspace(ctx, chain_rows, T, n_stages, ci.n_saved, per_row, s)))
+        return an_fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
+    AnWorkspace& w = ctx->an_ws;
+    const bool want_rec = loss_trace_dev || decision_trace_dev;
+    if (G < reps) {  // the repeats of a step run as several passes
+        if ((rc = an_grow(ctx, &w.grad_carry, &w.grad_carry_cap, (size_t)B * T, s))) return rc;
+        size_t cap_rows = w.eot_rows_cap;
+        if (want_rec && (rc = an_grow(ctx, &w.eot_loss_rows, &cap_rows, (size_t)reps * B, s))) return rc;
+        if (want_rec && (rc = an_grow(ctx, &w.eot_dec_rows, &w.eot_rows_cap, (size_t)reps * B, s))) return rc;
+    }
+    for (int r = 0; r < (feco ? R : G); ++r)
+        AN_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    // the iterate is clamped into [lower, upper] within [-1, 1] at every step: a first stage's decision is taken once
+    if ((rc = def_chain_first_scale(ctx, chain, x_adv_dev, (int64_t)B * T, s))) return an_fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
+    const AnDefCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p, chain, n_stages, feco,
+                      success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+    if (feco || ci.identity) return an_def_loop_single(ctx, c, d, ci.identity, R, s);
+    return an_def_loop_rows(ctx, c, d, reps, G, s);
 }
 
 }  // extern "C"

@@ -154,6 +154,13 @@ struct AnWorkspace {
     size_t spec_cache_bytes = 0;
     bool spec_cache_refused = false;  // an allocation failed once: the passes run without the cache
     float* x_alt = nullptr;      // (B, T) the other half of the waveform ping-pong of the fused overlap-add update (on demand)
+    // the defended loop (sg_an_pgd_run_defended) when a step's EOT repeats run as several passes: the cotangent sum carried
+    // from group to group, and the per-repeat records the last group reduces (both on demand, before the loop)
+    float* grad_carry = nullptr;     // (n) floats, n = utterances x T of the call
+    size_t grad_carry_cap = 0;
+    float* eot_loss_rows = nullptr;  // (reps * utterances)
+    int64_t* eot_dec_rows = nullptr;
+    size_t eot_rows_cap = 0;
     // which input the mel cache belongs to (sg_an_logmel_backward(reuse_forward) checks pointer and shape, not contents)
     const float* cache_x = nullptr;
     int cache_B = 0, cache_T = 0;
@@ -257,7 +264,7 @@ struct Workspace {
     std::vector<void*> allocs;
 };
 
-// Buffers of the defended device loop (sg_xv_pgd_run_defended), grown before the loop, never inside it.  `plane` = one
+// Buffers of the defended device loops (sg_xv_pgd_run_defended, sg_an_pgd_run_defended), grown before the loop, never inside it.  `plane` = one
 // (rows, T) float32 waveform of the largest pass, rows = G * B when every EOT repeat runs as its own row.
 struct DefWorkspace {
     size_t plane = 0;                  // floats per plane the buffers were sized for
@@ -537,6 +544,33 @@ hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, cons
 // k_freq_domain.hip): SG_OK or SG_ERR_ARG with the context's error text set
 int wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d);
 int wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f);
+
+// ---- the chain of the defended device loops (sg_api.hip), shared by sg_xv_pgd_run_defended and sg_an_pgd_run_defended
+// buffers for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the replicated iterate and the two
+// cotangent planes.  Called before the loop; a request the buffers already cover costs nothing.
+int ensure_def_workspace(sg_ctx* ctx, int rows, int T, int n_out, int n_saved, bool rep, hipStream_t s);
+struct DefChainInfo {
+    bool randomised;  // holds AT: the EOT repeats of a step differ
+    bool identity;    // QT / BDR only: the chain's backward is the identity
+    int n_saved;      // int8 planes its stages keep (MS, filters)
+};
+// everything a stage call would refuse about the chain, said before any launch: SG_OK or SG_ERR_ARG with the error text set
+int def_chain_check(sg_ctx* ctx, const char* who, const sg_wav_stage* chain, int n_stages, DefChainInfo* info);
+struct DefChainTape {  // what one pass's forward leaves for its backward
+    sg_wav_defense spec[SG_WAV_CHAIN_MAX];  // the pass's specs (AT: with the pass's key)
+    const float* in[SG_WAV_CHAIN_MAX];
+    void* saved[SG_WAV_CHAIN_MAX];
+};
+// the scale / clip decision of a first stage that reads one, from the iterate (n floats), once per call
+int def_chain_first_scale(sg_ctx* ctx, const sg_wav_stage* chain, const float* x, int64_t n, hipStream_t s);
+// x (rows, T) through the chain into the workspace's stage outputs; *out = the defended rows.  AT's key is its spec's seed +
+// pass_key, rep_rows > 0: the rows are EOT repeats of rep_rows utterances.  A later stage's scale / clip decision: from its input.
+int def_chain_forward(sg_ctx* ctx, const sg_wav_stage* chain, int n_stages, const float* x, int rows, int T, uint64_t pass_key,
+                      int rep_rows, DefChainTape* tape, const float** out, hipStream_t s);
+// the cotangent in the workspace's plane g[0] back through the chain, last stage first, ping-ponging the two planes; *gi: the
+// plane that holds the result.  Nothing is launched for QT / BDR.
+int def_chain_backward(sg_ctx* ctx, const sg_wav_stage* chain, int n_stages, const DefChainTape& tape, int rows, int T, int* gi,
+                       hipStream_t s);
 // out[r][0..ncol) = in[r][0..ncol), out[r][ncol..ld_out) = 0
 hipError_t launch_copy_cols(const float* in, int ld_in, float* out, int ld_out, int64_t rows, int ncol, hipStream_t s);
 hipError_t launch_sum_cols(const float* in, int ld_in, int nsplit, long long slab_stride, float* out, int ld_out,

@@ -178,11 +178,8 @@ class audionet_csine(EngineOps):
     def fused_pass_seed(base_seed, it, r=0):
         return (int(base_seed) + it * 0x9E3779B97F4A7C15 + r * 0xC2B2AE3D27D4EB4F) & 0xFFFFFFFFFFFFFFFF
 
-    def pgd_run_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, feco, eot_size=1, eot_batch_size=1,
-                     trace=False):
-        """attack/FGSM.py:38-70 attack_batch against defended_model(self, [(1, feco)]) (BASELINE.json configs[3]) as one
-        device-resident loop: log-mel -> FeCo -> CNN forward, hand-chained backward, EOT repeats over the defense's
-        random initial frames (``feco.init == 'random'``) summed on the device.  `feco`: a FeCoDefense."""
+    def _pgd_args(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace):
+        """the tensors and the parameter block the device loops share -> (x_adv, y, lower, upper, B, T, params, outputs)"""
         x, B, T = self._prep(x, 0)
         self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
         x_adv = x.clone()
@@ -195,45 +192,92 @@ class audionet_csine(EngineOps):
         p.loss = loss_spec.native()
         p.step_size, p.max_iter, p.grad_sign = float(step_size), int(max_iter), int(grad_sign)
         p.eot_size, p.eot_batch_size = int(eot_size), int(eot_batch_size)
+        success = torch.empty(B, device=self.device, dtype=torch.uint8)
+        dec = torch.empty(B, device=self.device, dtype=torch.int64)
+        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
+        loss = torch.empty(B, device=self.device, dtype=torch.float32)
+        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
+        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
+        return x_adv, y, lower, upper, B, T, p, (success, dec, scores, loss, ltr, dtr)
+
+    def _feco_params(self, feco, T):
+        """sg_feco_params of one fused call: one key per call, from the model's noise bookkeeping (attack call, restart, call
+        number); the passes inside derive theirs from it; a row is keyed by its utterance's GLOBAL index (chunk base + row)"""
         f = N.FecoParams()
         f.k = int(N.load().sg_an_num_frames(T) * feco.param)  # feature_level.py:184
         f.max_iter = int(feco.max_iter)
         f.random_init = int(feco.init == 'random')
-        # one key per fused call, from the model's noise bookkeeping (attack call, restart, call number); the passes
-        # inside derive theirs from it; a row is keyed by its utterance's GLOBAL index (chunk base + row)
         f.seed = self.defense_seed(feco.seed)
         feco.calls += 1
         self.last_fused_seed = int(f.seed)
         f.index_base = int(feco.index_base) + self.row_keys()[0]
-        success = torch.empty(B, device=self.device, dtype=torch.uint8)
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
-        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
+        return f
+
+    def _wav_stages(self, chain):
+        """the chain as a sg_wav_stage array.  Every randomised stage (AT) gets one base key, drawn in chain order like
+        ``defended_model._fwd`` draws them; ``last_fused_defense_seeds`` keeps them (None for a deterministic stage)."""
+        chain = list(chain)
+        if not 1 <= len(chain) <= N.SG_WAV_CHAIN_MAX:
+            raise ValueError("a chain of 1 .. %d input-level defenses runs on the device, got %d" % (N.SG_WAV_CHAIN_MAX, len(chain)))
+        stages = (N.WavStage * len(chain))()
+        keep, keys = [], []
+        index_base, row_base, _ = self.row_keys()
+        for i, d in enumerate(chain):
+            st = d.stage()
+            keep.append(st)  # (a filter's stage keeps its sections alive)
+            key = None
+            if getattr(d, 'randomised', False):
+                key = self.defense_seed(d.seed, d.seed_tag)
+                st.u.defense.seed, st.u.defense.index_base, st.u.defense.row_base = key, index_base, row_base
+            keys.append(key)
+            stages[i] = st
+        self.last_fused_defense_seeds = keys
+        return stages, keep
+
+    def pgd_run_defended(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, eot_size=1,
+                         eot_batch_size=1, trace=False):
+        """``pgd_run`` against this model behind a chain of native waveform-level defenses (defense.time_domain /
+        defense.frequency_domain objects, applied in order before the log-mel front-end): the step loop of ``attack_batch`` over
+        ``defended_model._loss_grad_through_defenses`` as ONE device-resident call (sg_an_pgd_run_defended).  The loop derives
+        AT's key of step ``it``, repeat ``r`` from the stage's base key as ``fused_pass_seed(key, it, r)``."""
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
+        stages, keep = self._wav_stages(chain)
+        self.ctx.call("sg_an_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
+                      stages, len(stages), None, *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
+
+    def pgd_run_defended_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, feco, eot_size=1,
+                              eot_batch_size=1, trace=False):
+        """``pgd_run_feco`` with a chain of native, deterministic waveform-level defenses in front of the log-mel front-end:
+        ``defended_model(self, [(0, d1), ..., (1, feco)])`` as ONE device-resident call (sg_an_pgd_run_defended with feco).
+        Keys and ``feco.calls`` bookkeeping as ``pgd_run_feco``."""
+        if any(getattr(d, 'randomised', False) for d in chain):
+            raise ValueError("a randomised input-level defense in front of FeCo keeps the step loop")
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
+        stages, keep = self._wav_stages(chain)
+        f = self._feco_params(feco, T)
+        self.ctx.call("sg_an_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
+                      stages, len(stages), C.byref(f), *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
+
+    def pgd_run_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, feco, eot_size=1, eot_batch_size=1,
+                     trace=False):
+        """attack/FGSM.py:38-70 attack_batch against defended_model(self, [(1, feco)]) (BASELINE.json configs[3]) as one
+        device-resident loop: log-mel -> FeCo -> CNN forward, hand-chained backward, EOT repeats over the defense's
+        random initial frames (``feco.init == 'random'``) summed on the device.  `feco`: a FeCoDefense."""
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
+        f = self._feco_params(feco, T)
         self.ctx.call("sg_an_pgd_run_feco", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      C.byref(f), N._ptr(success), N._ptr(dec), N._ptr(scores), N._ptr(loss), N._ptr(ltr), N._ptr(dtr),
-                      self._stream())
-        return x_adv, success, dec, scores, loss, ltr, dtr
+                      C.byref(f), *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
 
     def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
                 trace=False):
-        x, B, T = self._prep(x, 0)
-        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
-        x_adv = x.clone()
-        y = y.to(self.device, torch.int64).contiguous()
-        lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()
-        upper = upper.to(self.device, torch.float32).expand_as(x).contiguous()
-        p = N.PgdParams()
-        p.loss = loss_spec.native()
-        p.step_size, p.max_iter, p.grad_sign = float(step_size), int(max_iter), int(grad_sign)
-        p.eot_size, p.eot_batch_size = int(eot_size), int(eot_batch_size)
-        success = torch.empty(B, device=self.device, dtype=torch.uint8)
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
-        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
         self.ctx.call("sg_an_pgd_run", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      N._ptr(success), N._ptr(dec), N._ptr(scores), N._ptr(loss), N._ptr(ltr), N._ptr(dtr), self._stream())
-        return x_adv, success, dec, scores, loss, ltr, dtr
+                      *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
