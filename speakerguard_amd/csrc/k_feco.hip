@@ -26,7 +26,6 @@
 //   * the ids of the LAST assignment step are the result.
 // Given the ids, the compression is the reference's :204-216 on the ORIGINAL frames: mean of the cluster's frames, an
 // empty cluster i falls back to frame i when `force` (batch > 1) and is dropped otherwise (the host compacts).
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 
@@ -38,16 +37,6 @@
 using namespace sg;
 
 namespace {
-
-int feco_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
 
 // tuning aid (SG_FECO_TRACE=1): phase timestamps (100 MHz) of block (0, 0): per iteration [start, after the assignment,
 // after the member lists, after the update] for the first 16 iterations, then [loop end, kernel end, kernel start]
@@ -723,8 +712,8 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     if (!ctx) return SG_ERR_ARG;
     if (!feats_dev || !assign_dev || B <= 0 || F <= 0 || D <= 0 || D > kFecoMaxD || k <= 0 || k > F || max_iter <= 0 || reps < 1 ||
         reps > 65535)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
-    if (hipSetDevice(ctx->device) != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipSetDevice failed");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipSetDevice failed");
     // LDS holds the centred centroids (rows padded to 32 / 64 floats), ids, member lists and -- when they fit -- the chunk
     // counts of the fast member lists and the centred frames (else the frames are re-read from HBM / L2 in every step).
     // 150 KB cover ~19 s at D <= 32, ratio 0.5 (F = 1930, k = 965); beyond that the call is refused.
@@ -749,7 +738,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     auto bytes = [&](int jc, int fast, int xin) { return (size_t)feco_layout(F, k, dpad, jc, fast, xin).total * sizeof(float); };
     if (bytes(JC, 0, 0) > kLdsMax) JC = 1;
     if (bytes(JC, 0, 0) > kLdsMax)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: %d clusters x %d dims + %d frames need %zu bytes of LDS (limit %zu): "
+        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: %d clusters x %d dims + %d frames need %zu bytes of LDS (limit %zu): "
                          "utterance too long for one block", k, D, F, bytes(JC, 0, 0), kLdsMax);
     // the assignment's units (frame tile, chunk jc of its centroid tiles [ntc jc / JC, ntc (jc + 1) / JC)) dealt to the waves:
     // largest first, each to the least loaded SIMD (waves w, w + 4, w + 8, w + 12) and there to the least loaded wave with a
@@ -783,7 +772,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
             // tags repeat every 2^15 launches: the words of the last cycle are wiped before they could be taken for new ones
             if ((ctx->feco_epoch & 0x7FFFu) == 1u &&
                 hipMemsetAsync(ctx->feco_xchg, 0, words * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
-                return feco_fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipMemsetAsync failed");
+                return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipMemsetAsync failed");
             pr.on = 1;
             pr.xchg = ctx->feco_xchg;
             pr.flags = ctx->feco_flags;
@@ -832,7 +821,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     const void* fn = dpad == 32 ? reinterpret_cast<const void*>(feco_kmeans_kernel<32>)
                                 : reinterpret_cast<const void*>(feco_kmeans_kernel<64>);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-    if (e != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
     if (dpad == 32)
         hipLaunchKernelGGL(feco_kmeans_kernel<32>, dim3(B, reps, pr.on ? 2 : 1), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F,
                            D, k, max_iter, seeded, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
@@ -840,7 +829,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
         hipLaunchKernelGGL(feco_kmeans_kernel<64>, dim3(B, reps), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F, D, k,
                            max_iter, seeded, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
     e = hipGetLastError();
-    if (e != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
     static const bool tr_on = sg_tune_env("SG_FECO_TRACE") != nullptr;
     if (tr_on) {
         static bool armed[kMaxDevices] = {};  // the switch is a device symbol: one per device
@@ -889,9 +878,9 @@ extern "C" int sg_feco_kmeans_seeded(sg_ctx* ctx, const float* feats_dev, int32_
 extern "C" int sg_feco_kmeans_compress(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                        int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base, int32_t reps,
                                        int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream) {
-    if (!out_dev || !counts_dev) return feco_fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: out and counts are required");
+    if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: out and counts are required");
     if (reps > 1 && !random_init)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: repeats of the evenly started clustering coincide (reps must be 1)");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: repeats of the evenly started clustering coincide (reps must be 1)");
     return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, random_init != 0, seed, index_base, reps, assign_dev, out_dev,
                             counts_dev, stream);
 }
@@ -900,12 +889,12 @@ extern "C" int sg_feco_compress(sg_ctx* ctx, const float* feats_dev, const int32
                                 int32_t D, int32_t k, float* out_dev, int32_t* counts_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!feats_dev || !assign_dev || !out_dev || !counts_dev || B <= 0 || F <= 0 || D <= 0 || k <= 0 || k > F)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_compress: bad arguments");
-    if (hipSetDevice(ctx->device) != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress: hipSetDevice failed");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_compress: bad arguments");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_compress: hipSetDevice failed");
     hipLaunchKernelGGL(feco_compress_kernel, dim3((k * D + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, feats_dev,
                        assign_dev, F, D, k, out_dev, counts_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_compress: %s", hipGetErrorString(e));
     return SG_OK;
 }
 
@@ -914,13 +903,13 @@ extern "C" int sg_feco_compress_backward(sg_ctx* ctx, const float* dout_dev, con
                                          int32_t force, float* dfeats_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!dout_dev || !assign_dev || !counts_dev || !dfeats_dev || B <= 0 || F <= 0 || D <= 0 || k <= 0 || k > F)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_compress_backward: bad arguments");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_compress_backward: bad arguments");
     if (hipSetDevice(ctx->device) != hipSuccess)
-        return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward: hipSetDevice failed");
+        return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward: hipSetDevice failed");
     hipLaunchKernelGGL(feco_compress_bwd_kernel, dim3((F * D + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, dout_dev,
                        assign_dev, counts_dev, F, D, k, force, dfeats_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward: %s", hipGetErrorString(e));
     return SG_OK;
 }
 
@@ -929,12 +918,12 @@ extern "C" int sg_feco_compress_backward_reps(sg_ctx* ctx, const float* dout_dev
                                               int32_t force, int32_t reps, float* dfeats_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!dout_dev || !assign_dev || !counts_dev || !dfeats_dev || B <= 0 || F <= 0 || D <= 0 || k <= 0 || k > F || reps < 1)
-        return feco_fail(ctx, SG_ERR_ARG, "sg_feco_compress_backward_reps: bad arguments");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_compress_backward_reps: bad arguments");
     if (hipSetDevice(ctx->device) != hipSuccess)
-        return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: hipSetDevice failed");
+        return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: hipSetDevice failed");
     hipLaunchKernelGGL(feco_compress_bwd_reps_kernel, dim3((F * D + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, dout_dev,
                        assign_dev, counts_dev, B, F, D, k, force, reps, dfeats_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return feco_fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: %s", hipGetErrorString(e));
     return SG_OK;
 }

@@ -32,7 +32,6 @@
 // The reference moves the means through `.data`, so its autograd sees only the INITIAL segment means: the gradient is
 // sg_feco_compress_backward of the initial segment ids and counts this kernel returns (no kernel of its own).
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <vector>
 
@@ -51,16 +50,6 @@ constexpr size_t kWarpLdsMax = 150 * 1024;
 constexpr int kWarpBadInit = -1;  // sweeps[row]: initial boundaries not strictly increasing from 0
 constexpr int kWarpCapped = -2;   // sweeps[row]: still moving after the cap
 constexpr unsigned long long kWarpRepStride = 0xC2B2AE3D27D4EB4FULL;
-
-int warp_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
 
 __host__ __device__ constexpr int wal4(int n) { return (n + 3) & ~3; }
 
@@ -366,14 +355,14 @@ extern "C" int sg_feco_warped(sg_ctx* ctx, const float* feats_dev, int32_t B, in
                               int32_t* sweeps_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!feats_dev || !boundaries_dev || !init_ids_dev || !init_counts_dev || !out_dev || !sweeps_dev)
-        return warp_fail(ctx, SG_ERR_ARG, "sg_feco_warped: null pointer argument");
+        return fail(ctx, SG_ERR_ARG, "sg_feco_warped: null pointer argument");
     if (B <= 0 || B > 65535 || F <= 0 || F > kWarpMaxF || D <= 0 || D > kWarpMaxD || k < 1 || k > F)
-        return warp_fail(ctx, SG_ERR_ARG, "sg_feco_warped: need 0 < B <= 65535, 0 < F <= %d, 0 < D <= %d, 1 <= k <= F "
+        return fail(ctx, SG_ERR_ARG, "sg_feco_warped: need 0 < B <= 65535, 0 < F <= %d, 0 < D <= %d, 1 <= k <= F "
                          "(got B %d, F %d, D %d, k %d)", kWarpMaxF, kWarpMaxD, B, F, D, k);
     if (init_mode < 0 || init_mode > 2 || rep_rows < 0 || !(delta >= 0.0 && delta <= 1.0))
-        return warp_fail(ctx, SG_ERR_ARG, "sg_feco_warped: need init_mode 0 (ts) / 1 (random) / 2 (given), rep_rows >= 0, "
+        return fail(ctx, SG_ERR_ARG, "sg_feco_warped: need init_mode 0 (ts) / 1 (random) / 2 (given), rep_rows >= 0, "
                          "0 <= delta <= 1");
-    if (hipSetDevice(ctx->device) != hipSuccess) return warp_fail(ctx, SG_ERR_HIP, "sg_feco_warped: hipSetDevice failed");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_warped: hipSetDevice failed");
     auto bytes = [&](int ml, int xl) { return (size_t)warp_layout(F, k, D, ml, xl).total * sizeof(float); };
     const int ml = bytes(1, 0) <= kWarpLdsMax;
     const int xl = ml && bytes(1, 1) <= kWarpLdsMax;
@@ -395,22 +384,22 @@ extern "C" int sg_feco_warped(sg_ctx* ctx, const float* feats_dev, int32_t B, in
         SG_WARP_CASE(true, true, true)
 #undef SG_WARP_CASE
         default:
-            return warp_fail(ctx, SG_ERR_ARG, "sg_feco_warped: no layout for F %d, D %d, k %d", F, D, k);
+            return fail(ctx, SG_ERR_ARG, "sg_feco_warped: no layout for F %d, D %d, k %d", F, D, k);
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return warp_fail(ctx, SG_ERR_HIP, "sg_feco_warped: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_warped: %s", hipGetErrorString(e));
     // the per-row status decides the return code: wait for it
     std::vector<int32_t> st((size_t)B);
     e = hipMemcpyAsync(st.data(), sweeps_dev, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return warp_fail(ctx, SG_ERR_HIP, "sg_feco_warped: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_warped: %s", hipGetErrorString(e));
     for (int b = 0; b < B; ++b) {
         if (st[b] == kWarpBadInit)
-            return warp_fail(ctx, SG_ERR_ARG, "sg_feco_warped: row %d: the initial boundaries do not rise strictly from 0 "
+            return fail(ctx, SG_ERR_ARG, "sg_feco_warped: row %d: the initial boundaries do not rise strictly from 0 "
                              "(%s); the reference would average empty segments (NaN)", b,
                              init_mode == 0 ? "degenerate TS init" : "bad boundaries given");
         if (st[b] == kWarpCapped)
-            return warp_fail(ctx, SG_ERR_STATE, "sg_feco_warped: row %d: boundaries still moving after %d sweeps (cap); "
+            return fail(ctx, SG_ERR_STATE, "sg_feco_warped: row %d: boundaries still moving after %d sweeps (cap); "
                              "its means are those of the last sweep", b, cap);
     }
     return SG_OK;

@@ -36,7 +36,6 @@
 // (consecutive lanes, consecutive slots: conflict-free), and the results go back the same way; clamp and mask happen at the
 // coalesced store.  One barrier per section (the wave totals, double-buffered), three per pass.
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 
 #include "sg_internal.h"
@@ -179,16 +178,6 @@ __global__ __launch_bounds__(kFdThreads) void fd_cascade_kernel(const float* __r
     }
 }
 
-int fd_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
-
 struct Mat2 {
     double m00, m01, m10, m11;
 };
@@ -239,20 +228,20 @@ int fd_tables(const double* sos, int S, FdTables* tab, const char** why) {
 // what a spec alone can get wrong about its sections; builds the kernel's tables on the way
 int fd_check_sections(sg_ctx* ctx, const char* who, const sg_wav_filter* f, FdTables* tab) {
     if (f->n_sections < 1 || f->n_sections > kFdMaxSections)
-        return fd_fail(ctx, SG_ERR_ARG, "%s: 1 .. %d sections are built (%d)", who, kFdMaxSections, f->n_sections);
+        return fail(ctx, SG_ERR_ARG, "%s: 1 .. %d sections are built (%d)", who, kFdMaxSections, f->n_sections);
     const char* why = "";
     const int bad = fd_tables(f->sos, f->n_sections, tab, &why);
-    if (bad) return fd_fail(ctx, SG_ERR_ARG, "%s: section %d of %d: %s", who, bad, f->n_sections, why);
+    if (bad) return fail(ctx, SG_ERR_ARG, "%s: section %d of %d: %s", who, bad, f->n_sections, why);
     return SG_OK;
 }
 
 int fd_check(sg_ctx* ctx, const char* who, const sg_wav_filter* f, const void* a, const void* b, const void* c, int32_t B,
              int32_t T, FdTables* tab) {
     if (!ctx) return SG_ERR_ARG;
-    if (!f || !a || !b || !c || !f->sos) return fd_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || T < 1 || T > kFdMaxT) return fd_fail(ctx, SG_ERR_ARG, "%s: need B >= 1 and 1 <= T <= %d (B %d, T %d)", who, kFdMaxT, B, T);
+    if (!f || !a || !b || !c || !f->sos) return fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    if (B < 1 || T < 1 || T > kFdMaxT) return fail(ctx, SG_ERR_ARG, "%s: need B >= 1 and 1 <= T <= %d (B %d, T %d)", who, kFdMaxT, B, T);
     if (int rc = fd_check_sections(ctx, who, f, tab)) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fd_fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
     return SG_OK;
 }
 
@@ -260,14 +249,14 @@ int fd_check(sg_ctx* ctx, const char* who, const sg_wav_filter* f, const void* a
 int fd_clip(sg_ctx* ctx, const char* who, const sg_wav_filter* f, bool have_scale, float* lo_a, float* hi_a, float* lo_b, float* hi_b) {
     *lo_a = -1.f, *hi_a = 1.f, *lo_b = 0.f, *hi_b = 0.f;
     if (f->clip_mode == SG_FD_CLIP_RANGE) {
-        if (!have_scale) return fd_fail(ctx, SG_ERR_ARG, "%s: SG_FD_CLIP_RANGE needs scale_dev", who);
-        if (f->bits < 2 || f->bits > 24) return fd_fail(ctx, SG_ERR_ARG, "%s: bits must be 2 .. 24 (%d)", who, f->bits);
+        if (!have_scale) return fail(ctx, SG_ERR_ARG, "%s: SG_FD_CLIP_RANGE needs scale_dev", who);
+        if (f->bits < 2 || f->bits > 24) return fail(ctx, SG_ERR_ARG, "%s: bits must be 2 .. 24 (%d)", who, f->bits);
         *lo_b = -(float)(1 << (f->bits - 1)), *hi_b = (float)((1 << (f->bits - 1)) - 1);
     } else if (f->clip_mode == SG_FD_CLIP_GIVEN) {
-        if (!(f->clip_lo <= f->clip_hi)) return fd_fail(ctx, SG_ERR_ARG, "%s: need clip_lo <= clip_hi", who);
+        if (!(f->clip_lo <= f->clip_hi)) return fail(ctx, SG_ERR_ARG, "%s: need clip_lo <= clip_hi", who);
         *lo_a = f->clip_lo, *hi_a = f->clip_hi;
     } else {
-        return fd_fail(ctx, SG_ERR_ARG, "%s: unknown clip_mode %d", who, f->clip_mode);
+        return fail(ctx, SG_ERR_ARG, "%s: unknown clip_mode %d", who, f->clip_mode);
     }
     return SG_OK;
 }
@@ -275,7 +264,7 @@ int fd_clip(sg_ctx* ctx, const char* who, const sg_wav_filter* f, bool have_scal
 }  // namespace
 
 int sg::wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f) {
-    if (!f->sos) return fd_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    if (!f->sos) return fail(ctx, SG_ERR_ARG, "%s: null argument", who);
     FdTables tab;
     if (int rc = fd_check_sections(ctx, who, f, &tab)) return rc;
     float lo_a, hi_a, lo_b, hi_b;
@@ -295,7 +284,7 @@ extern "C" int sg_wav_filter_forward(sg_ctx* ctx, const sg_wav_filter* f, const 
     hipLaunchKernelGGL(fd_cascade_kernel<false>, dim3(B), dim3(kFdThreads), 0, s, x_dev, (const int8_t*)nullptr, out_dev, mask_dev,
                        scale_dev, lo_a, hi_a, lo_b, hi_b, T, f->n_sections, tab);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fd_fail(ctx, SG_ERR_HIP, "sg_wav_filter_forward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_filter_forward: %s", hipGetErrorString(e));
     trace_mark(ctx, SG_STAGE_FD_FWD, s, 1);
     return SG_OK;
 }
@@ -310,7 +299,7 @@ extern "C" int sg_wav_filter_backward(sg_ctx* ctx, const sg_wav_filter* f, const
     hipLaunchKernelGGL(fd_cascade_kernel<true>, dim3(B), dim3(kFdThreads), 0, s, g_dev, mask_dev, gx_dev, (int8_t*)nullptr,
                        (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, T, f->n_sections, tab);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fd_fail(ctx, SG_ERR_HIP, "sg_wav_filter_backward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_filter_backward: %s", hipGetErrorString(e));
     trace_mark(ctx, SG_STAGE_FD_BWD, s, 1);
     return SG_OK;
 }

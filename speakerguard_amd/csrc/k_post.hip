@@ -2,7 +2,6 @@
 // audio with the perturbation metrics the evaluation reads, and the equal-error-rate threshold scan.
 // HBM-bound byte / integer work: one pass for the range decisions, one fused pass for everything else.
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 
 #include "sg_internal.h"
@@ -10,16 +9,6 @@
 using namespace sg;
 
 namespace {
-
-int post_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
 
 template <typename T, typename Op>
 __device__ __forceinline__ T block_reduce(T v, T* scratch, Op op) {
@@ -170,12 +159,12 @@ extern "C" int sg_wav_finalize(sg_ctx* ctx, const float* benign_dev, const float
                                int16_t* pcm_dev, double* metrics_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!adver_dev || B <= 0 || T <= 0 || (!pcm_dev && !metrics_dev) || (metrics_dev && !benign_dev))
-        return post_fail(ctx, SG_ERR_ARG, "sg_wav_finalize: need adver, B > 0, T > 0, an output, and benign for metrics");
-    if (hipSetDevice(ctx->device) != hipSuccess) return post_fail(ctx, SG_ERR_HIP, "sg_wav_finalize: hipSetDevice failed");
+        return fail(ctx, SG_ERR_ARG, "sg_wav_finalize: need adver, B > 0, T > 0, an output, and benign for metrics");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_finalize: hipSetDevice failed");
     hipLaunchKernelGGL(wav_finalize_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, metrics_dev ? benign_dev : nullptr,
                        adver_dev, T, pcm_dev, metrics_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return post_fail(ctx, SG_ERR_HIP, "sg_wav_finalize: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_finalize: %s", hipGetErrorString(e));
     return SG_OK;
 }
 
@@ -183,12 +172,12 @@ extern "C" int sg_eer_threshold(sg_ctx* ctx, const float* target_dev, int32_t n_
                                 int32_t n_untarget, double* out3_dev, void* stream) {
     if (!ctx) return SG_ERR_ARG;
     if (!target_dev || !untarget_dev || !out3_dev || n_target <= 0 || n_untarget <= 0)
-        return post_fail(ctx, SG_ERR_ARG, "sg_eer_threshold: need non-empty target and untarget score lists");
-    if (hipSetDevice(ctx->device) != hipSuccess) return post_fail(ctx, SG_ERR_HIP, "sg_eer_threshold: hipSetDevice failed");
+        return fail(ctx, SG_ERR_ARG, "sg_eer_threshold: need non-empty target and untarget score lists");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_eer_threshold: hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     double* tmp = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)3 * n_target * sizeof(double));
-    if (e != hipSuccess) return post_fail(ctx, SG_ERR_HIP, "sg_eer_threshold: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_eer_threshold: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(eer_count_kernel, dim3((n_target + 255) / 256), dim3(256), 0, s, target_dev, n_target, untarget_dev,
                        n_untarget, tmp, tmp + n_target, tmp + 2 * (size_t)n_target);
     hipLaunchKernelGGL(eer_pick_kernel, dim3(1), dim3(1024), 0, s, target_dev, n_target, tmp, tmp + n_target,
@@ -196,6 +185,6 @@ extern "C" int sg_eer_threshold(sg_ctx* ctx, const float* target_dev, int32_t n_
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
-    if (e != hipSuccess) return post_fail(ctx, SG_ERR_HIP, "sg_eer_threshold: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_eer_threshold: %s", hipGetErrorString(e));
     return SG_OK;
 }

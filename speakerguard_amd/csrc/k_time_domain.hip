@@ -36,7 +36,6 @@
 //            kAtDomain = 0xA7000000 in counter word 1: the dither's counters carry the FRAME there (< 2^31 / 160) and
 //            the NES queries the antithetic pair index, so the three streams never share a counter even under one key.
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 
 #include "philox.h"
@@ -48,16 +47,6 @@
 using namespace sg;
 
 namespace {
-
-int td_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
 
 constexpr int kTdBlock = 256;     // samples (= threads) per block of the elementwise / windowed kernels
 constexpr int kTdMaxK = 31;       // largest window
@@ -255,28 +244,28 @@ int td_window(float param) {
 int td_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d) {
     switch (d->kind) {
     case SG_TD_QT:
-        if (!(d->param > 0.f) || !std::isfinite(d->param)) return td_fail(ctx, SG_ERR_ARG, "%s: QT needs a finite q > 0 (%g)", who, d->param);
+        if (!(d->param > 0.f) || !std::isfinite(d->param)) return fail(ctx, SG_ERR_ARG, "%s: QT needs a finite q > 0 (%g)", who, d->param);
         break;
     case SG_TD_AS:
     case SG_TD_MS:
-        if (!td_window(d->param)) return td_fail(ctx, SG_ERR_ARG, "%s: the window must be odd, 1 <= k <= %d (%g)", who, kTdMaxK, d->param);
+        if (!td_window(d->param)) return fail(ctx, SG_ERR_ARG, "%s: the window must be odd, 1 <= k <= %d (%g)", who, kTdMaxK, d->param);
         break;
     case SG_TD_AT:
-        if (!std::isfinite(d->param)) return td_fail(ctx, SG_ERR_ARG, "%s: AT needs a finite SNR in dB (%g)", who, d->param);
-        if (d->rep_rows < 0 || d->row_base < 0) return td_fail(ctx, SG_ERR_ARG, "%s: row_base and rep_rows must not be negative", who);
+        if (!std::isfinite(d->param)) return fail(ctx, SG_ERR_ARG, "%s: AT needs a finite SNR in dB (%g)", who, d->param);
+        if (d->rep_rows < 0 || d->row_base < 0) return fail(ctx, SG_ERR_ARG, "%s: row_base and rep_rows must not be negative", who);
         break;
     default:
-        return td_fail(ctx, SG_ERR_ARG, "%s: unknown kind %d", who, d->kind);
+        return fail(ctx, SG_ERR_ARG, "%s: unknown kind %d", who, d->kind);
     }
     return SG_OK;
 }
 
 int td_check(sg_ctx* ctx, const char* who, const sg_wav_defense* d, const void* a, const void* b, int32_t B, int32_t T) {
     if (!ctx) return SG_ERR_ARG;
-    if (!d || !a || !b) return td_fail(ctx, SG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || B > 65535 || T < 1) return td_fail(ctx, SG_ERR_ARG, "%s: need 1 <= B <= 65535 and T >= 1 (B %d, T %d)", who, B, T);
+    if (!d || !a || !b) return fail(ctx, SG_ERR_ARG, "%s: null argument", who);
+    if (B < 1 || B > 65535 || T < 1) return fail(ctx, SG_ERR_ARG, "%s: need 1 <= B <= 65535 and T >= 1 (B %d, T %d)", who, B, T);
     if (int rc = td_check_spec(ctx, who, d)) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return td_fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
     return SG_OK;
 }
 
@@ -291,7 +280,7 @@ extern "C" int sg_wav_defense_forward(sg_ctx* ctx, const sg_wav_defense* d, cons
                                       float* out_dev, void* saved_dev, void* stream) {
     int rc = td_check(ctx, "sg_wav_defense_forward", d, x_dev, out_dev, B, T);
     if (rc) return rc;
-    if (d->kind != SG_TD_AS && !saved_dev) return td_fail(ctx, SG_ERR_ARG, "sg_wav_defense_forward: this kind needs saved_dev");
+    if (d->kind != SG_TD_AS && !saved_dev) return fail(ctx, SG_ERR_ARG, "sg_wav_defense_forward: this kind needs saved_dev");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((T + kTdBlock - 1) / kTdBlock, B);
     trace_mark(ctx, SG_STAGE_TD_FWD, s, 0);
@@ -320,7 +309,7 @@ extern "C" int sg_wav_defense_forward(sg_ctx* ctx, const sg_wav_defense* d, cons
     }
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return td_fail(ctx, SG_ERR_HIP, "sg_wav_defense_forward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_defense_forward: %s", hipGetErrorString(e));
     trace_mark(ctx, SG_STAGE_TD_FWD, s, 1);
     return SG_OK;
 }
@@ -330,8 +319,8 @@ extern "C" int sg_wav_defense_backward(sg_ctx* ctx, const sg_wav_defense* d, con
     int rc = td_check(ctx, "sg_wav_defense_backward", d, g_dev, gx_dev, B, T);
     if (rc) return rc;
     if ((d->kind == SG_TD_MS || d->kind == SG_TD_AT) && !saved_dev)
-        return td_fail(ctx, SG_ERR_ARG, "sg_wav_defense_backward: this kind needs the forward's saved_dev");
-    if (d->kind == SG_TD_AT && !x_dev) return td_fail(ctx, SG_ERR_ARG, "sg_wav_defense_backward: AT needs the forward's input");
+        return fail(ctx, SG_ERR_ARG, "sg_wav_defense_backward: this kind needs the forward's saved_dev");
+    if (d->kind == SG_TD_AT && !x_dev) return fail(ctx, SG_ERR_ARG, "sg_wav_defense_backward: AT needs the forward's input");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((T + kTdBlock - 1) / kTdBlock, B);
     trace_mark(ctx, SG_STAGE_TD_BWD, s, 0);
@@ -357,7 +346,7 @@ extern "C" int sg_wav_defense_backward(sg_ctx* ctx, const sg_wav_defense* d, con
     }
     }
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return td_fail(ctx, SG_ERR_HIP, "sg_wav_defense_backward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_wav_defense_backward: %s", hipGetErrorString(e));
     trace_mark(ctx, SG_STAGE_TD_BWD, s, 1);
     return SG_OK;
 }

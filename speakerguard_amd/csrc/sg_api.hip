@@ -2,7 +2,6 @@
 // weight re-layout), workspace, and the kernel sequences of one forward / backward / PGD pass.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,47 +13,6 @@
 using namespace sg;
 
 namespace {
-
-int fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
-
-#define SG_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s failed: %s (%s:%d)", #expr,             \
-                                          hipGetErrorString(e_), __FILE__, __LINE__);                  \
-    } while (0)
-
-#define SG_STAGE(tag, expr)          \
-    do {                             \
-        trace_mark(ctx, (tag), s, 0); \
-        SG_HIP(expr);                \
-        trace_mark(ctx, (tag), s, 1); \
-    } while (0)
-
-template <typename T>
-int dev_alloc(sg_ctx* ctx, std::vector<void*>& pool, T** out, size_t count) {
-    void* p = nullptr;
-    SG_HIP(hipMalloc(&p, count * sizeof(T) + 256));
-    pool.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return SG_OK;
-}
-
-template <typename T>
-int dev_upload(sg_ctx* ctx, std::vector<void*>& pool, T** out, const std::vector<T>& host) {
-    int rc = dev_alloc(ctx, pool, out, host.size());
-    if (rc) return rc;
-    SG_HIP(hipMemcpy(*out, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SG_OK;
-}
 
 // [K][N] row-major -> k4-major [K/4][N][4] (Wq[k/4][n][k%4]): four consecutive k of one column become one
 // 16-byte LDS read in the quad-fed GEMM (k_conv_gemm.hip); K is padded up to a multiple of 4 with zeros.
@@ -476,65 +434,140 @@ int eot_group_size(sg_ctx* ctx, int B, int T, int reps, int* G) {
     return SG_OK;
 }
 
-// per-step records (attack/FGSM.py:50-58: loss averaged, decision voted over ALL EOT repeats of the step): when the
-// repeats of a step run as several passes (G < reps) every pass leaves its rows here and the last one reduces them
-int grow_eot_rows(sg_ctx* ctx, size_t rows, hipStream_t s) {
-    Workspace& w = ctx->ws;
-    if (w.eot_rows_cap >= rows) return SG_OK;
-    // grown: the old pair is released (nothing enqueued still uses it once the stream has drained), not left in the
-    // workspace's pool until sg_destroy
-    if (w.eot_loss_rows || w.eot_dec_rows) {
-        SG_HIP(hipStreamSynchronize(s));
-        for (void* old : {static_cast<void*>(w.eot_loss_rows), static_cast<void*>(w.eot_dec_rows)}) {
-            auto it = std::find(w.allocs.begin(), w.allocs.end(), old);
-            if (it != w.allocs.end()) {
-                (void)hipFree(old);
-                w.allocs.erase(it);
-            }
-        }
-        w.eot_loss_rows = nullptr;
-        w.eot_dec_rows = nullptr;
-        w.eot_rows_cap = 0;
-    }
-    int rc;
-    if ((rc = dev_alloc(ctx, w.allocs, &w.eot_loss_rows, rows))) return rc;
-    if ((rc = dev_alloc(ctx, w.allocs, &w.eot_dec_rows, rows))) return rc;
-    w.eot_rows_cap = rows;
-    return SG_OK;
-}
-
 struct LoopOut {  // a loop's caller buffers: the state at the final pass, and the optional per-step records
     uint8_t* success; int64_t* decisions; float* scores; float* loss; float* loss_trace; int64_t* decision_trace;
 };
-// the tail of the pass of `rows` = Gi * B rows (repeats g0 .. g0 + Gi - 1 of step `it`, nrep repeats in the step, at most G
-// per pass) and the step's records
-int run_loop_tail(sg_ctx* ctx, const sg_loss_spec& loss, const LoopOut& o, int B, int rows, int it, int g0, int Gi, int G, int nrep,
-                  bool last, hipStream_t s) {
+// the tail of pass `ps` of step `it` and the step's records
+int run_loop_tail(sg_ctx* ctx, const sg_loss_spec& loss, const LoopOut& o, int B, int it, const LoopPass& ps, hipStream_t s) {
     Workspace& w = ctx->ws;
-    const bool want_rec = o.loss_trace || o.decision_trace;
     TailArgs t{};
-    t.fc1_part = w.fc1_part; t.nsplit = kFc1SplitK; t.B = rows; t.m = &ctx->xv; t.y = w.y_rep; t.loss = loss;
-    t.want_grad = !last; t.demb = w.demb;
-    t.scores = last ? o.scores : nullptr;
-    t.decisions = last ? o.decisions : nullptr;
-    t.loss_out = last ? o.loss : nullptr;
-    t.success = last ? o.success : nullptr;
-    // per-step records as the reference prints them (attack/FGSM.py:50-58): the loss averaged over the step's EOT
-    // repeats and the decision voted over them (attack/utils.py:118-125).  A pass of several repeats records its
-    // rows into the workspace and a small reduction writes the step's row; with more repeats than one pass holds
-    // (G < reps: activations past 2 GiB, or SG_EOT_MAX_ROWS) the passes of the step collect their rows in repeat
-    // order and the reduction runs after the last one, over all `nrep` repeats.
-    const bool direct = nrep == 1, grouped = nrep > G;
-    float* lrows = grouped ? w.eot_loss_rows + (size_t)g0 * B : w.loss;
-    int64_t* drows = grouped ? w.eot_dec_rows + (size_t)g0 * B : w.decisions;
-    t.loss_trace = !want_rec ? nullptr : (direct && o.loss_trace ? o.loss_trace + (size_t)it * B : lrows);
-    t.decision_trace = !want_rec ? nullptr : (direct && o.decision_trace ? o.decision_trace + (size_t)it * B : drows);
+    t.fc1_part = w.fc1_part; t.nsplit = kFc1SplitK; t.B = ps.rows; t.m = &ctx->xv; t.y = w.y_rep; t.loss = loss;
+    t.want_grad = !ps.last; t.demb = w.demb;
+    t.scores = ps.last ? o.scores : nullptr;
+    t.decisions = ps.last ? o.decisions : nullptr;
+    t.loss_out = ps.last ? o.loss : nullptr;
+    t.success = ps.last ? o.success : nullptr;
+    // per-step records as the reference prints them (LoopPass::Records): the pass scratch is the workspace's loss / decision
+    // rows, the grouped rows are grown before the loop
+    float* lrec = o.loss_trace ? o.loss_trace + (size_t)it * B : nullptr;
+    int64_t* drec = o.decision_trace ? o.decision_trace + (size_t)it * B : nullptr;
+    t.loss_trace = loop_record_rows(ps, lrec, w.loss, w.eot_loss_rows);
+    t.decision_trace = loop_record_rows(ps, drec, w.decisions, w.eot_dec_rows);
     t.coef_rows = B;  // SG_LOSS_LINEAR: the caller's (B, S) table serves every repeat of an utterance
     SG_STAGE(SG_STAGE_TAIL, launch_tail(t, s));
-    if (want_rec && !direct && g0 + Gi >= nrep)
-        SG_HIP(launch_eot_trace_reduce(grouped ? w.eot_loss_rows : w.loss, grouped ? w.eot_dec_rows : w.decisions, nrep, B,
-                                       o.loss_trace ? o.loss_trace + (size_t)it * B : nullptr,
-                                       o.decision_trace ? o.decision_trace + (size_t)it * B : nullptr, s));
+    if (ps.reduce) {
+        const bool grouped = ps.rec == LoopPass::GROUPED;
+        SG_HIP(launch_eot_trace_reduce(grouped ? w.eot_loss_rows : w.loss, grouped ? w.eot_dec_rows : w.decisions, ps.nrep, B, lrec, drec, s));
+    }
+    return SG_OK;
+}
+
+// the loop entry points' own refusal about B / T (loop_check_args)
+const char* xv_loop_shape(int B, int T) {
+    return B < 1 || T < kWin ? "need B >= 1 and a waveform of at least one 25 ms window" : nullptr;
+}
+
+struct XvLoopCall {  // the caller's buffers, as the entry point received them
+    float* x_adv; const int64_t* y; const float* lower; const float* upper;
+    int B, T;
+    const sg_pgd_params* p;
+    LoopOut out;
+};
+
+// The device-resident PGD loop of the x-vector model: sg_xv_pgd_run (n_stages == 0: no chain, `ci` says identity) and
+// sg_xv_pgd_run_defended (the chain and what def_chain_check found), after their argument checks.
+//
+// Expectation over the front-end's random dither and over a randomised stage (adaptive_attack/EOT.py:16-54; the reference
+// hard-codes dither = 1.0 at xv_plda.py:119, so this IS its default behaviour): every gradient step runs eot_size passes
+// with fresh noise, the data gradients are summed in pass order and the sign step is taken on the sum (sign(mean) ==
+// sign(sum); the EOT_batch_size grouping only changes how the reference batches the repeats).  The final pass of the
+// attack is a single forward (FGSM.py:45-47).  Without dither and AT the model is deterministic, every repeat is the same
+// computation and their mean is the single-pass result: one pass.
+//
+// The repeats of a step are independent passes over the same audio: they run as ONE batch of G x B rows (row = repeat * B +
+// utterance), where the contractions are more efficient than at B rows (24.7 k utterance-steps/s at 128 rows, 25.3 k at
+// 256 against 23.2 k at 64).  Per-row arithmetic does not depend on the batch and the repeats are summed in repeat order,
+// so the result is bit for bit that of the repeats run one after the other.  G: as many repeats as one pass may hold
+// (eot_group_size); more run as further groups, the sum handed on through ws.grad.
+//
+// No chain, or one whose backward is the identity (QT / BDR only): the repeats share the (defended) B rows -- the MFCC
+// kernels read them once per repeat and key repeat r's dither by seed + r * kRepKey -- and the overlap-add sums the
+// repeats and takes the step.  Any other chain runs every repeat as its own row through chain, model and both backwards;
+// the sum comes last.
+int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int n_stages, const DefChainInfo& ci, int eot_size,
+                hipStream_t s) {
+    const sg_pgd_params* p = c.p;
+    const int B = c.B, T = c.T;
+    const bool defended = n_stages > 0, per_row = !ci.identity;
+    const int reps = (ci.randomised || p->dither.dither != 0.f) ? eot_size : 1;
+    int rc, G = 1;
+    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
+    const int rows_max = per_row ? B * G : B;  // rows of the chain's largest pass
+    if (defended && rows_max > 65535)
+        return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_defended: %d rows per pass, the stage kernels take at most 65535: split the batch", rows_max);
+    PassDims d;
+    if ((rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d))) return rc;  // workspace for the largest pass
+    if (defended && (rc = ensure_def_workspace(ctx, rows_max, T, n_stages, ci.n_saved, per_row, s))) return rc;
+    Workspace& w = ctx->ws;
+    DefWorkspace& dw = ctx->def_ws;
+    for (int r = 0; r < G; ++r)
+        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, c.y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    const bool want_rec = c.out.loss_trace || c.out.decision_trace;
+    if (want_rec && G < reps) {  // LoopPass::GROUPED: every pass of a step leaves its rows here
+        if ((rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, &w.eot_loss_cap, (size_t)reps * B, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, &w.eot_dec_cap, (size_t)reps * B, s))) return rc;
+    }
+    const size_t n = (size_t)B * T;
+    // the iterate is clamped into [lower, upper] within [-1, 1] at every step: a first stage's own decision is taken once
+    if (defended && (rc = def_chain_first_scale(ctx, chain, c.x_adv, (int64_t)n, s))) return rc;
+
+    for (int it = 0; it <= p->max_iter; ++it) {
+        for (int g0 = 0, more = 1; more; g0 += G) {
+            const LoopPass ps = loop_pass(it, p->max_iter, g0, G, reps, B, want_rec);
+            more = !ps.final_group;
+            const int rows = per_row ? ps.rows : B;  // rows of the chain
+            // ---- chain forward (no stages: the iterate itself)
+            const float* cur = c.x_adv;
+            if (per_row && ps.Gi > 1) {
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
+                for (int r = 0; r < ps.Gi; ++r)
+                    SG_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, c.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
+                cur = dw.x_rep;
+            }
+            DefChainTape tape;  // reused by the backward
+            if ((rc = def_chain_forward(ctx, chain, n_stages, cur, rows, T, ps.pass_key, ps.Gi > 1 ? B : 0, &tape, &cur, s))) return rc;
+            // ---- the model on the (defended) waveform
+            sg_dither dz = p->dither;
+            dz.seed += ps.pass_key;
+            d.B = ps.rows;
+            d.Bu = !per_row && ps.Gi > 1 ? B : 0;
+            if (per_row && ps.Gi > 1) dz.rep_rows = B;  // rows are repeats of B utterances: repeat r keys its dither like d.Bu does
+            // The MFCC's range decision.  No chain: every iterate is clamped into [lower, upper] within [-1, 1], so
+            // check_input_range takes the same branch as for the start point: decide once.  Behind a chain: from the defended
+            // rows of every pass, as a model call takes it.
+            d.keep_scale = !defended && (it > 0 || g0 > 0);
+            if ((rc = run_frontend(ctx, cur, d, SG_FLAG_WAV, &dz, !ps.last, s))) return rc;
+            if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
+            if ((rc = run_loop_tail(ctx, p->loss, c.out, B, it, ps, s))) return rc;
+            if (ps.last) continue;
+            // the repeats' sum: carried to the next group, or turned into the step by the final one
+            const float* carry_in = g0 > 0 ? w.grad : nullptr;
+            float* carry_out = ps.final_group ? nullptr : w.grad;
+            float* x_step = ps.final_group ? c.x_adv : nullptr;
+            if (!per_row) {  // identity backward: d loss / d defended IS d loss / d iterate
+                rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, carry_out, x_step, c.lower, c.upper, p->step_size, p->grad_sign, s, carry_in);
+                if (rc) return rc;
+                continue;
+            }
+            if ((rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, dw.g[0], nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+            // ---- chain backward, last stage first, then the sum over the pass's repeats
+            int gi = 0;
+            if ((rc = def_chain_backward(ctx, chain, n_stages, tape, rows, T, &gi, s))) return rc;
+            SG_STAGE(SG_STAGE_DEF_REP_SUM, launch_wav_rep_sum_update(dw.g[gi], ps.Gi, (int64_t)n, carry_in, carry_out, x_step, c.lower, c.upper,
+                                                                     p->step_size, p->grad_sign, s));
+        }
+    }
     return SG_OK;
 }
 
@@ -1093,161 +1126,29 @@ int sg_fakebob_step(sg_ctx* ctx, float* x_dev, float* grad_dev, const float* pre
 int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
                   int32_t B, int32_t T, const sg_pgd_params* p, uint8_t* success_dev, int64_t* decisions_dev,
                   float* scores_dev, float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev, void* stream) {
-    int rc;
+    int rc, eot_size;
     if (!ctx) return SG_ERR_ARG;
-    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return fail(ctx, SG_ERR_ARG, "NULL argument");
-    if (B < 1 || T < kWin) return fail(ctx, SG_ERR_ARG, "need B >= 1 and a waveform of at least one 25 ms window");
-    if (p->max_iter < 0) return fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
-    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
-    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
-    if (eot_size % eot_bs) return fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
-    // Expectation over the front-end's random dither (adaptive_attack/EOT.py:16-54; the reference hard-codes
-    // dither = 1.0 at xv_plda.py:119, so this IS its default behaviour): every gradient step runs eot_size passes
-    // with fresh noise, the data gradients are summed in pass order and the sign step is taken on the sum
-    // (sign(mean) == sign(sum); the EOT_batch_size grouping only changes how the reference batches the repeats).
-    // The final pass of the attack is a single forward (FGSM.py:45-47).  Without dither the model is
-    // deterministic, every repeat is the same computation and their mean is the single-pass result: one pass.
-    const int reps = p->dither.dither != 0.f ? eot_size : 1;
-    hipStream_t s = (hipStream_t)stream;
-    // The repeats of a step are independent passes over the same audio: they run as ONE batch of G x B rows (row = repeat
-    // * B + utterance; the MFCC kernels read the utterance's waveform for every repeat and key repeat r's dither by
-    // seed + r * 0xC2B2AE3D27D4EB4F), where the contractions are more efficient than at B rows (24.7 k utterance-steps/s
-    // at 128 rows, 25.3 k at 256 against 23.2 k at 64).  Per-row arithmetic does not depend on the batch and the
-    // overlap-add sums the repeats in repeat order, so the result is bit for bit that of the repeats run one after the
-    // other.  G: as many repeats as one pass may hold (activation tensors < 2 GiB); more run as further groups, the sum
-    // handed on through ws.grad.
-    int G = 1;
-    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
-    PassDims d;
-    rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d);  // workspace for the largest pass
-    if (rc) return rc;
-    Workspace& w = ctx->ws;
-    for (int r = 0; r < G; ++r)
-        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    // per-step records (attack/FGSM.py:50-58: loss averaged, decision voted over ALL EOT repeats of the step): when the
-    // repeats of a step run as several passes (G < reps) every pass leaves its rows here and the last one reduces them
-    const bool want_rec = loss_trace_dev || decision_trace_dev;
-    if (want_rec && G < reps && (rc = grow_eot_rows(ctx, (size_t)reps * B, s))) return rc;
-    for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;
-        const int nrep = last ? 1 : reps;
-        for (int g0 = 0; g0 < nrep; g0 += G) {
-            const int Gi = std::min(G, nrep - g0);
-            sg_dither dz = p->dither;
-            dz.seed += (uint64_t)it * 0x9E3779B97F4A7C15ull + (uint64_t)g0 * 0xC2B2AE3D27D4EB4Full;
-            d.B = B * Gi;
-            d.Bu = Gi > 1 ? B : 0;
-            // every iterate is clamped into [lower, upper] within [-1, 1], so check_input_range takes the
-            // same branch as for the start point: decide once
-            d.keep_scale = it > 0 || g0 > 0;
-            if ((rc = run_frontend(ctx, x_adv_dev, d, SG_FLAG_WAV, &dz, !last, s))) return rc;
-            if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
-            const LoopOut out{success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
-            if ((rc = run_loop_tail(ctx, p->loss, out, B, d.B, it, g0, Gi, G, nrep, last, s))) return rc;
-            if (!last) {
-                const bool final_group = g0 + Gi >= nrep;
-                rc = run_backward_to_input(ctx, x_adv_dev, d, SG_FLAG_WAV, &dz, final_group ? nullptr : w.grad,
-                                           final_group ? x_adv_dev : nullptr, lower_dev, upper_dev, p->step_size, p->grad_sign, s,
-                                           g0 > 0 ? w.grad : nullptr);
-                if (rc) return rc;
-            }
-        }
-    }
-    return SG_OK;
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p, xv_loop_shape(B, T), p))) return rc;
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
+    const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
+                       {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
+    return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, (hipStream_t)stream);
 }
 
 int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
                            int32_t B, int32_t T, const sg_pgd_params* p, const sg_wav_stage* chain, int32_t n_stages,
                            uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
                            float* loss_trace_dev, int64_t* decision_trace_dev, void* stream) {
-    static const char* who = "sg_xv_pgd_run_defended";
-    int rc;
+    int rc, eot_size;
     if (!ctx) return SG_ERR_ARG;
-    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return fail(ctx, SG_ERR_ARG, "NULL argument");
-    if (B < 1 || T < kWin) return fail(ctx, SG_ERR_ARG, "need B >= 1 and a waveform of at least one 25 ms window");
-    if (p->max_iter < 0) return fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
-    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
-    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
-    if (eot_size % eot_bs) return fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
-    // ---- the chain: everything a stage call would refuse, before the first launch
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p, xv_loop_shape(B, T), p))) return rc;
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
+    // the chain: everything a stage call would refuse, before the first launch
     DefChainInfo ci;
-    if ((rc = def_chain_check(ctx, who, chain, n_stages, &ci))) return rc;
-    const bool randomised = ci.randomised, identity = ci.identity;
-    const int n_saved = ci.n_saved;
-    // Repeats: a randomised stage (AT) or the dither makes the repeats of a step differ; otherwise one pass stands for all.
-    const int reps = (randomised || p->dither.dither != 0.f) ? eot_size : 1;
-    hipStream_t s = (hipStream_t)stream;
-    int G = 1;
-    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
-    // A chain whose backward is the identity (QT / BDR only) keeps sg_xv_pgd_run's pass: the repeats share the defended
-    // rows (the MFCC kernels read them once per repeat) and the overlap-add sums the repeats and takes the step.  Any
-    // other chain runs every repeat as its own row through chain, model and both backwards; the sum comes last.
-    const bool per_row = !identity;
-    const int rows_max = per_row ? B * G : B;
-    if (rows_max > 65535) return fail(ctx, SG_ERR_ARG, "%s: %d rows per pass, the stage kernels take at most 65535: split the batch", who, rows_max);
-    PassDims d;
-    rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d);  // workspace for the largest pass
-    if (rc) return rc;
-    if ((rc = ensure_def_workspace(ctx, rows_max, T, n_stages, n_saved, per_row, s))) return rc;
-    Workspace& w = ctx->ws;
-    DefWorkspace& dw = ctx->def_ws;
-    for (int r = 0; r < G; ++r)
-        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    const bool want_rec = loss_trace_dev || decision_trace_dev;
-    if (want_rec && G < reps && (rc = grow_eot_rows(ctx, (size_t)reps * B, s))) return rc;
-    const LoopOut out{success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
-    const size_t n = (size_t)B * T;
-    // the iterate is clamped into [lower, upper] within [-1, 1] at every step: its own decision is taken once
-    if ((rc = def_chain_first_scale(ctx, chain, x_adv_dev, (int64_t)n, s))) return rc;
-
-    for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;
-        const int nrep = last ? 1 : reps;
-        for (int g0 = 0; g0 < nrep; g0 += G) {
-            const int Gi = std::min(G, nrep - g0);
-            const int rows = per_row ? B * Gi : B;
-            const uint64_t pass_key = (uint64_t)it * 0x9E3779B97F4A7C15ull + (uint64_t)g0 * 0xC2B2AE3D27D4EB4Full;
-            // ---- chain forward
-            const float* cur = x_adv_dev;
-            if (per_row && Gi > 1) {
-                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
-                for (int r = 0; r < Gi; ++r)
-                    SG_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, x_adv_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
-                cur = dw.x_rep;
-            }
-            DefChainTape tape;  // reused by the backward
-            if ((rc = def_chain_forward(ctx, chain, n_stages, cur, rows, T, pass_key, Gi > 1 ? B : 0, &tape, &cur, s))) return rc;
-            // ---- the model on the defended waveform
-            sg_dither dz = p->dither;
-            dz.seed += pass_key;
-            d.B = B * Gi;
-            d.Bu = !per_row && Gi > 1 ? B : 0;
-            if (per_row && Gi > 1) dz.rep_rows = B;  // rows are repeats of B utterances: repeat r keys its dither like d.Bu does
-            d.keep_scale = false;  // the MFCC's decision: from the defended rows of every pass, as a model call takes it
-            if ((rc = run_frontend(ctx, cur, d, SG_FLAG_WAV, &dz, !last, s))) return rc;
-            if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
-            if ((rc = run_loop_tail(ctx, p->loss, out, B, d.B, it, g0, Gi, G, nrep, last, s))) return rc;
-            if (last) continue;
-            const bool final_group = g0 + Gi >= nrep;
-            if (!per_row) {  // identity backward: d loss / d defended IS d loss / d iterate
-                rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, final_group ? nullptr : w.grad,
-                                           final_group ? x_adv_dev : nullptr, lower_dev, upper_dev, p->step_size, p->grad_sign, s,
-                                           g0 > 0 ? w.grad : nullptr);
-                if (rc) return rc;
-                continue;
-            }
-            if ((rc = run_backward_to_input(ctx, cur, d, SG_FLAG_WAV, &dz, dw.g[0], nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
-            // ---- chain backward, last stage first
-            int gi = 0;
-            if ((rc = def_chain_backward(ctx, chain, n_stages, tape, rows, T, &gi, s))) return rc;
-            // ---- the repeats' sum, carried to the next group or turned into the step
-            SG_STAGE(SG_STAGE_DEF_REP_SUM,
-                     launch_wav_rep_sum_update(dw.g[gi], Gi, (int64_t)n, g0 > 0 ? w.grad : nullptr, final_group ? nullptr : w.grad,
-                                               final_group ? x_adv_dev : nullptr, lower_dev, upper_dev, p->step_size, p->grad_sign, s));
-        }
-    }
-    return SG_OK;
+    if ((rc = def_chain_check(ctx, "sg_xv_pgd_run_defended", chain, n_stages, &ci))) return rc;
+    const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
+                       {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
+    return xv_pgd_loop(ctx, c, chain, n_stages, ci, eot_size, (hipStream_t)stream);
 }
 
 int sg_wav_rep_sum_update(sg_ctx* ctx, const float* planes_dev, int32_t G, int64_t n, const float* carry_dev, float* sum_out_dev,

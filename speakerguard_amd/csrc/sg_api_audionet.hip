@@ -2,7 +2,6 @@
 // model load (BatchNorm folding), workspace, forward / backward / PGD kernel sequences.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 
@@ -11,46 +10,6 @@
 using namespace sg;
 
 namespace {
-
-int an_fail(sg_ctx* ctx, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    return code;
-}
-
-#define AN_HIP(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return an_fail(ctx, SG_ERR_HIP, "%s failed: %s (%s:%d)", #expr,         \
-                                             hipGetErrorString(e_), __FILE__, __LINE__);              \
-    } while (0)
-
-#define AN_STAGE(tag, expr)           \
-    do {                              \
-        trace_mark(ctx, (tag), s, 0); \
-        AN_HIP(expr);                 \
-        trace_mark(ctx, (tag), s, 1); \
-    } while (0)
-
-template <typename T>
-int an_alloc(sg_ctx* ctx, std::vector<void*>& pool, T** out, size_t count) {
-    void* p = nullptr;
-    AN_HIP(hipMalloc(&p, count * sizeof(T) + 256));
-    pool.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return SG_OK;
-}
-template <typename T>
-int an_upload(sg_ctx* ctx, std::vector<void*>& pool, T** out, const std::vector<T>& host) {
-    int rc = an_alloc(ctx, pool, out, host.size());
-    if (rc) return rc;
-    AN_HIP(hipMemcpy(*out, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SG_OK;
-}
 
 // ---- front-end tables: periodic hann(800), librosa-0.8.0 slaney mel basis (Preprocessor.py:57-60) ----
 double hz_to_mel(double f) {
@@ -102,7 +61,7 @@ int an_build_tables(sg_ctx* ctx) {
                     ++cnt;
                 }
             if (cnt > 2 || (cnt == 2 && melw[(size_t)(first + 1) * kAnBins + k] <= 0.f))
-                return an_fail(ctx, SG_ERR_STATE, "mel filterbank is not a two-overlap triangular bank");
+                return fail(ctx, SG_ERR_STATE, "mel filterbank is not a two-overlap triangular bank");
             m0[k] = first;
             if (first >= 0) {
                 w0[k] = melw[(size_t)first * kAnBins + k];
@@ -120,10 +79,10 @@ int an_build_tables(sg_ctx* ctx) {
     AnTables& t = ctx->an_tab;
     std::vector<void*>& pool = ctx->model_allocs;
     int rc = 0;
-    rc |= an_upload(ctx, pool, &t.window, window);
-    rc |= an_upload(ctx, pool, &t.mel_w, melw);
-    rc |= an_upload(ctx, pool, &t.mel_lo, lo);
-    rc |= an_upload(ctx, pool, &t.mel_hi, hi);
+    rc |= dev_upload(ctx, pool, &t.window, window);
+    rc |= dev_upload(ctx, pool, &t.mel_w, melw);
+    rc |= dev_upload(ctx, pool, &t.mel_lo, lo);
+    rc |= dev_upload(ctx, pool, &t.mel_hi, hi);
     {   // the per-lane views of window and filterbank the front-end kernels keep in LDS (k_audionet.hip, AnLaneTab)
         // mel: every filter is cut into ceil(width / 20) runs of consecutive bins of (nearly) equal length, one lane per run
         // (971 filter taps over 63 lanes, <= 20 each; the two-lanes-per-filter split of rounds 3-4 was bound by its widest
@@ -140,7 +99,7 @@ int an_build_tables(sg_ctx* ctx) {
         int lanes = 0;
         for (int m = 0; m < kAnMel; ++m) {
             const int w = hi[m] - lo[m], runs = w > 0 ? (w + kLaneBins - 1) / kLaneBins : 1;
-            if (lanes + runs > 64 || runs > 5) return an_fail(ctx, SG_ERR_STATE, "mel filterbank needs more than 64 runs of %d bins", kLaneBins);
+            if (lanes + runs > 64 || runs > 5) return fail(ctx, SG_ERR_STATE, "mel filterbank needs more than 64 runs of %d bins", kLaneBins);
             seg[m] = lanes | (runs << 8);
             for (int i = 0; i < runs; ++i, ++lanes) {
                 const int k0 = lo[m] + (int)((long long)w * i / runs), k1 = lo[m] + (int)((long long)w * (i + 1) / runs);
@@ -148,10 +107,10 @@ int an_build_tables(sg_ctx* ctx) {
                 for (int j = 0; j < k1 - k0; ++j) lmelw[(size_t)j * 64 + lanes] = melw[(size_t)m * kAnBins + k0 + j];
             }
         }
-        rc |= an_upload(ctx, pool, &t.mel_seg, seg);
-        rc |= an_upload(ctx, pool, &t.lane_win, lwin);
-        rc |= an_upload(ctx, pool, &t.lane_melw, lmelw);
-        rc |= an_upload(ctx, pool, &t.lane_k0, lk0);
+        rc |= dev_upload(ctx, pool, &t.mel_seg, seg);
+        rc |= dev_upload(ctx, pool, &t.lane_win, lwin);
+        rc |= dev_upload(ctx, pool, &t.lane_melw, lmelw);
+        rc |= dev_upload(ctx, pool, &t.lane_k0, lk0);
     }
     {   // twiddle tables of the 512-point complex transform (W512^m = W1024^(2 m)), as fft512_fill_tables lays them out
         auto w512 = [&](int m) {
@@ -167,17 +126,17 @@ int an_build_tables(sg_ctx* ctx) {
         }
         for (int i = 0; i < 7 * 64; ++i) t1f[i] = make_float2((float)t1[i].x, (float)t1[i].y);
         for (int i = 0; i < 72; ++i) t2f[i] = make_float2((float)t2[i].x, (float)t2[i].y);
-        rc |= an_upload(ctx, pool, &t.tw1d, t1);
-        rc |= an_upload(ctx, pool, &t.tw2d, t2);
-        rc |= an_upload(ctx, pool, &t.tw1f, t1f);
-        rc |= an_upload(ctx, pool, &t.tw2f, t2f);
+        rc |= dev_upload(ctx, pool, &t.tw1d, t1);
+        rc |= dev_upload(ctx, pool, &t.tw2d, t2);
+        rc |= dev_upload(ctx, pool, &t.tw1f, t1f);
+        rc |= dev_upload(ctx, pool, &t.tw2f, t2f);
     }
-    rc |= an_upload(ctx, pool, &t.bin_m0, m0);
-    rc |= an_upload(ctx, pool, &t.bin_w0, w0);
-    rc |= an_upload(ctx, pool, &t.bin_w1, w1);
-    rc |= an_upload(ctx, pool, &t.twiddle, tw);
-    rc |= an_upload(ctx, pool, &t.bitrev, br);
-    if (!ctx->range_scratch) rc |= an_alloc(ctx, pool, &ctx->range_scratch, 512);
+    rc |= dev_upload(ctx, pool, &t.bin_m0, m0);
+    rc |= dev_upload(ctx, pool, &t.bin_w0, w0);
+    rc |= dev_upload(ctx, pool, &t.bin_w1, w1);
+    rc |= dev_upload(ctx, pool, &t.twiddle, tw);
+    rc |= dev_upload(ctx, pool, &t.bitrev, br);
+    if (!ctx->range_scratch) rc |= dev_alloc(ctx, pool, &ctx->range_scratch, 512);
     if (rc) return SG_ERR_HIP;
     ctx->an_tables_ready = true;
     return SG_OK;
@@ -195,27 +154,27 @@ int an_ensure_workspace(sg_ctx* ctx, int B, int T, int F) {
     an_layer_frames(cf, Tin, Tout);
     const size_t b = (size_t)cb;
     int rc = 0;
-    rc |= an_alloc(ctx, w.allocs, &w.scale, 4);
-    rc |= an_alloc(ctx, w.allocs, &w.feats, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.pre, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.dpre, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.dfeats, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.dframes, b * cf * kAnWin);
-    rc |= an_alloc(ctx, w.allocs, &w.mel_cache, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.feco_ids, b * cf);
-    rc |= an_alloc(ctx, w.allocs, &w.feco_cnt, b * cf);
-    rc |= an_alloc(ctx, w.allocs, &w.feco_out, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.dfeco, b * cf * kAnMel);
-    rc |= an_alloc(ctx, w.allocs, &w.y_rep, b);
-    rc |= an_alloc(ctx, w.allocs, &w.trace_l, b);
-    rc |= an_alloc(ctx, w.allocs, &w.trace_d, b);
+    rc |= dev_alloc(ctx, w.allocs, &w.scale, 4);
+    rc |= dev_alloc(ctx, w.allocs, &w.feats, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.pre, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.dpre, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.dfeats, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.dframes, b * cf * kAnWin);
+    rc |= dev_alloc(ctx, w.allocs, &w.mel_cache, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.feco_ids, b * cf);
+    rc |= dev_alloc(ctx, w.allocs, &w.feco_cnt, b * cf);
+    rc |= dev_alloc(ctx, w.allocs, &w.feco_out, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.dfeco, b * cf * kAnMel);
+    rc |= dev_alloc(ctx, w.allocs, &w.y_rep, b);
+    rc |= dev_alloc(ctx, w.allocs, &w.trace_l, b);
+    rc |= dev_alloc(ctx, w.allocs, &w.trace_d, b);
     for (int l = 0; l < kAnConv; ++l) {
         const size_t n = b * (size_t)(Tout[l] > 0 ? Tout[l] : 1) * kAnCout[l];
-        rc |= an_alloc(ctx, w.allocs, &w.act[l], n);
-        rc |= an_alloc(ctx, w.allocs, &w.dact[l], n);
+        rc |= dev_alloc(ctx, w.allocs, &w.act[l], n);
+        rc |= dev_alloc(ctx, w.allocs, &w.dact[l], n);
         if (kAnPool[l]) {
-            rc |= an_alloc(ctx, w.allocs, &w.pool[l], n / 2 + kAnCout[l]);
-            rc |= an_alloc(ctx, w.allocs, &w.dpool[l], n / 2 + kAnCout[l]);
+            rc |= dev_alloc(ctx, w.allocs, &w.pool[l], n / 2 + kAnCout[l]);
+            rc |= dev_alloc(ctx, w.allocs, &w.dpool[l], n / 2 + kAnCout[l]);
         }
     }
     if (rc) {
@@ -233,13 +192,13 @@ struct AnDims {
 
 int an_check(sg_ctx* ctx, int B, int TF, int flag, AnDims* d) {
     if (!ctx) return SG_ERR_ARG;
-    if (!ctx->an.loaded) return an_fail(ctx, SG_ERR_STATE, "no AudioNet model loaded (call sg_an_load)");
-    AN_HIP(hipSetDevice(ctx->device));
-    if (B < 1) return an_fail(ctx, SG_ERR_ARG, "B must be >= 1");
-    if (flag != 0 && flag != 1) return an_fail(ctx, SG_ERR_ARG, "flag must be 0 (wav) or 1 (log-mel feat)");
+    if (!ctx->an.loaded) return fail(ctx, SG_ERR_STATE, "no AudioNet model loaded (call sg_an_load)");
+    SG_HIP(hipSetDevice(ctx->device));
+    if (B < 1) return fail(ctx, SG_ERR_ARG, "B must be >= 1");
+    if (flag != 0 && flag != 1) return fail(ctx, SG_ERR_ARG, "flag must be 0 (wav) or 1 (log-mel feat)");
     d->B = B;
     if (flag == 0) {
-        if (TF < kAnFft) return an_fail(ctx, SG_ERR_ARG, "waveform shorter than one 1024-sample STFT frame");
+        if (TF < kAnFft) return fail(ctx, SG_ERR_ARG, "waveform shorter than one 1024-sample STFT frame");
         d->T = TF;
         d->F = an_num_frames(TF);
     } else {
@@ -248,16 +207,16 @@ int an_check(sg_ctx* ctx, int B, int TF, int flag, AnDims* d) {
     }
     int Tin[kAnConv], Tout[kAnConv];
     if (!an_layer_frames(d->F, Tin, Tout))
-        return an_fail(ctx, SG_ERR_ARG, "%d frames are too few for the AudioNet stack (need >= 3 frames at conv8)", d->F);
+        return fail(ctx, SG_ERR_ARG, "%d frames are too few for the AudioNet stack (need >= 3 frames at conv8)", d->F);
     // 32-bit buffer offsets in the contraction kernels (k_conv_gemm.hip): every activation tensor < 2 GiB
     for (int l = 0; l < kAnConv; ++l)
         if ((size_t)B * Tout[l] * kAnCout[l] * sizeof(float) >= 0x80000000ull || (size_t)B * d->F * 32 * sizeof(float) >= 0x80000000ull)
-            return an_fail(ctx, SG_ERR_ARG, "batch of %d x %d frames exceeds the 2 GiB per-tensor limit of one pass: split the batch",
+            return fail(ctx, SG_ERR_ARG, "batch of %d x %d frames exceeds the 2 GiB per-tensor limit of one pass: split the batch",
                            B, d->F);
     int rc = an_build_tables(ctx);
     if (rc) return rc;
     rc = an_ensure_workspace(ctx, d->B, d->T, d->F);
-    if (rc) return an_fail(ctx, rc, "workspace allocation failed: %s", ctx->err.c_str());
+    if (rc) return fail(ctx, rc, "workspace allocation failed: %s", ctx->err.c_str());
     return SG_OK;
 }
 
@@ -279,7 +238,7 @@ static bool an_use_spec_cache(const sg_ctx* ctx, int B, int F) {
 // waveform -> log-mel features in ws.feats (the backward of the same pass starts from the stored mel energies)
 int an_frontend_forward(sg_ctx* ctx, const float* x, const AnDims& d, hipStream_t s) {
     AnWorkspace& w = ctx->an_ws;
-    if (!d.keep_scale) AN_HIP(launch_input_scale(x, (int64_t)d.B * d.T, ctx->range_scratch, w.scale, 1, s));
+    if (!d.keep_scale) SG_HIP(launch_input_scale(x, (int64_t)d.B * d.T, ctx->range_scratch, w.scale, 1, s));
     AnTables tab = ctx->an_tab;
     tab.mel_cache = w.mel_cache;
     if (an_use_spec_cache(ctx, d.B, d.F)) {
@@ -290,7 +249,7 @@ int an_frontend_forward(sg_ctx* ctx, const float* x, const AnDims& d, hipStream_
             void* p = nullptr;
             if (hipMalloc(&p, need) == hipSuccess) {
                 if (w.spec_cache) {
-                    AN_HIP(hipStreamSynchronize(s));  // (an earlier pass may still read the old buffer)
+                    SG_HIP(hipStreamSynchronize(s));  // (an earlier pass may still read the old buffer)
                     (void)hipFree(w.spec_cache);
                     w.allocs.erase(std::remove(w.allocs.begin(), w.allocs.end(), static_cast<void*>(w.spec_cache)), w.allocs.end());
                 }
@@ -306,7 +265,7 @@ int an_frontend_forward(sg_ctx* ctx, const float* x, const AnDims& d, hipStream_
         if (need <= w.spec_cache_bytes) tab.spec_cache = w.spec_cache;
     }
     w.cache_x = x; w.cache_B = d.B; w.cache_T = d.T; w.cache_spec = tab.spec_cache != nullptr;
-    AN_STAGE(SG_STAGE_AN_LOGMEL_FWD, launch_an_logmel_fwd(tab, x, d.B, d.T, d.F, w.scale, w.feats, ctx->an_cfg.fft32, s));
+    SG_STAGE(SG_STAGE_AN_LOGMEL_FWD, launch_an_logmel_fwd(tab, x, d.B, d.T, d.F, w.scale, w.feats, ctx->an_cfg.fft32, s));
     return SG_OK;
 }
 
@@ -374,10 +333,10 @@ int an_net_forward(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int B, h
         AnFusedArgs a = an_fused_args(ctx, p);
         a.feats = feats;
         for (int l = 0; l < kAnConv; ++l) a.wq[l] = m.wfq[l];
-        AN_STAGE(SG_STAGE_AN_FUSED_FWD, launch_an_cnn_fused(a, p, B, false, s));
+        SG_STAGE(SG_STAGE_AN_FUSED_FWD, launch_an_cnn_fused(a, p, B, false, s));
         return SG_OK;
     }
-    AN_STAGE(SG_STAGE_AN_PREFILTER_FWD, launch_an_prefilter(feats, w.pre, B, p.Fnet, m.w25, m.pre_bias, 0, s));
+    SG_STAGE(SG_STAGE_AN_PREFILTER_FWD, launch_an_prefilter(feats, w.pre, B, p.Fnet, m.w25, m.pre_bias, 0, s));
     for (int l = 0; l < kAnConv; ++l) {
         ConvGemmArgs a{};
         a.A = an_layer_input(w, l);
@@ -398,8 +357,8 @@ int an_net_forward(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int B, h
         a.total_chunks = 3 * (a.Kc / 32);
         a.chunks_per_split = a.total_chunks;
         a.Wq = a.N % 128 == 0 ? m.wfq[l] : nullptr;
-        AN_STAGE(SG_STAGE_AN_CONV_FWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, EPI_BIAS_RELU, 1, s));
-        if (kAnPool[l]) AN_STAGE(SG_STAGE_AN_POOL_FWD, launch_an_pool_fwd(w.act[l], w.pool[l], B, p.Tout[l], kAnCout[l], s));
+        SG_STAGE(SG_STAGE_AN_CONV_FWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, EPI_BIAS_RELU, 1, s));
+        if (kAnPool[l]) SG_STAGE(SG_STAGE_AN_POOL_FWD, launch_an_pool_fwd(w.act[l], w.pool[l], B, p.Tout[l], kAnCout[l], s));
     }
     return SG_OK;
 }
@@ -414,11 +373,11 @@ int an_net_backward(sg_ctx* ctx, const AnNetPlan& p, int B, const AnHeadArgs* he
         a.dfeats = dfeats_out;
         if (head) a.head = *head;
         for (int l = 0; l < kAnConv; ++l) a.wq[l] = m.wbq[l];
-        AN_STAGE(SG_STAGE_AN_FUSED_BWD, launch_an_cnn_fused(a, p, B, true, s));
+        SG_STAGE(SG_STAGE_AN_FUSED_BWD, launch_an_cnn_fused(a, p, B, true, s));
         return SG_OK;
     }
     // (the plan puts the head into a launch only in a fused form: nobody would have written dact[6])
-    if (head) return an_fail(ctx, SG_ERR_STATE, "AudioNet: the per-layer backward cannot run the head");
+    if (head) return fail(ctx, SG_ERR_STATE, "AudioNet: the per-layer backward cannot run the head");
     for (int l = kAnConv - 1; l >= 0; --l) {
         // data gradient of conv l: reads dact[l] (B, Tout, Cout), writes the gradient of its input
         const bool in_pooled = l > 0 && kAnPool[l - 1];
@@ -441,11 +400,11 @@ int an_net_backward(sg_ctx* ctx, const AnNetPlan& p, int B, const AnHeadArgs* he
         a.total_chunks = 3 * (a.Kc / 32);
         a.chunks_per_split = a.total_chunks;
         a.Wq = a.N % 128 == 0 ? m.wbq[l] : nullptr;
-        AN_STAGE(SG_STAGE_AN_CONV_BWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, a.mask ? EPI_RELU_MASK : EPI_NONE, 1, s));
+        SG_STAGE(SG_STAGE_AN_CONV_BWD + l, launch_conv_gemm(a, a.N % 128 == 0 ? 2 : 1, a.mask ? EPI_RELU_MASK : EPI_NONE, 1, s));
         if (in_pooled)
-            AN_STAGE(SG_STAGE_AN_POOL_BWD, launch_an_pool_bwd(w.act[l - 1], w.dpool[l - 1], w.dact[l - 1], B, p.Tout[l - 1], kAnCout[l - 1], s));
+            SG_STAGE(SG_STAGE_AN_POOL_BWD, launch_an_pool_bwd(w.act[l - 1], w.dpool[l - 1], w.dact[l - 1], B, p.Tout[l - 1], kAnCout[l - 1], s));
     }
-    AN_STAGE(SG_STAGE_AN_PREFILTER_BWD, launch_an_prefilter(w.dpre, dfeats_out, B, p.Fnet, m.w25, 0.f, 1, s));
+    SG_STAGE(SG_STAGE_AN_PREFILTER_BWD, launch_an_prefilter(w.dpre, dfeats_out, B, p.Fnet, m.w25, 0.f, 1, s));
     return SG_OK;
 }
 
@@ -464,7 +423,7 @@ int an_net_step(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int rows, c
     const AnModel& m = ctx->an;
     const int L = kAnConv - 1;
     const bool head_inside = p.form == AN_FUSED_HEAD || p.form == AN_ONE_LAUNCH;
-    if (head_inside && !dfeats_out) return an_fail(ctx, SG_ERR_STATE, "AudioNet: a plan with the head inside the backward needs a gradient target");
+    if (head_inside && !dfeats_out) return fail(ctx, SG_ERR_STATE, "AudioNet: a plan with the head inside the backward needs a gradient target");
     std::copy(p.Tin, p.Tin + kAnConv, w.Tin);
     std::copy(p.Tout, p.Tout + kAnConv, w.Tout);
     int rc;
@@ -477,18 +436,18 @@ int an_net_step(sg_ctx* ctx, const AnNetPlan& p, const float* feats, int rows, c
             a.wq[l] = m.wfq[l];
             a.wq_bwd[l] = m.wbq[l];
         }
-        AN_STAGE(SG_STAGE_AN_FUSED_FWDBWD, launch_an_cnn_fwdbwd(a, p, rows, s));
+        SG_STAGE(SG_STAGE_AN_FUSED_FWDBWD, launch_an_cnn_fwdbwd(a, p, rows, s));
     } else {
         if ((rc = an_net_forward(ctx, p, feats, rows, s))) return rc;
         if (head_inside) {
             if ((rc = an_net_backward(ctx, p, rows, &head, dfeats_out, s))) return rc;
         } else {
-            AN_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], rows, p.Tout[L], head.fc_w, head.fc_b, head.S, head.threshold, head.y, head.ls,
+            SG_STAGE(SG_STAGE_AN_TAIL, launch_an_tail(w.act[L], rows, p.Tout[L], head.fc_w, head.fc_b, head.S, head.threshold, head.y, head.ls,
                                                       dfeats_out != nullptr, head.emb_out, head.scores_out, head.dec_out, head.loss_out, w.dact[L],
                                                       head.loss_trace, head.dec_trace, head.success, s, head.coef_rows));
         }
     }
-    if (eot) AN_HIP(launch_eot_trace_reduce(head.loss_trace, head.dec_trace, eot->R, eot->B, eot->loss_out, eot->dec_out, s));
+    if (eot) SG_HIP(launch_eot_trace_reduce(head.loss_trace, head.dec_trace, eot->R, eot->B, eot->loss_out, eot->dec_out, s));
     if (dfeats_out && !head_inside) return an_net_backward(ctx, p, rows, nullptr, dfeats_out, s);
     return SG_OK;
 }
@@ -514,13 +473,13 @@ int an_frontend_backward(sg_ctx* ctx, const float* x, const AnDims& d, const flo
         a.x = x; a.dfeats = dfeats; a.dframes = w.dframes; a.grad_out = grad_out;
         a.x_in = x_update; a.x_out = x_update ? x_next : nullptr; a.lower = lower; a.upper = upper; a.scale_p = w.scale;
         a.step = step; a.grad_sign = grad_sign; a.B = d.B; a.T = d.T; a.F = d.F;
-        AN_STAGE(SG_STAGE_AN_LOGMEL_BWD, launch_an_logmel_bwd_ola(tab, a, ctx->an_cfg.fft32, ctx->num_cus, s));
+        SG_STAGE(SG_STAGE_AN_LOGMEL_BWD, launch_an_logmel_bwd_ola(tab, a, ctx->an_cfg.fft32, ctx->num_cus, s));
         return SG_OK;
     }
-    AN_STAGE(SG_STAGE_AN_LOGMEL_BWD, launch_an_logmel_bwd(tab, x, d.B, d.T, d.F, w.scale, dfeats, w.dframes, ctx->an_cfg.fft32, s));
-    AN_STAGE(SG_STAGE_AN_OVERLAP_ADD, launch_an_frames_to_wave(w.dframes, d.B, d.T, d.F, w.scale, grad_out, x_update, lower, upper, step, grad_sign, s));
+    SG_STAGE(SG_STAGE_AN_LOGMEL_BWD, launch_an_logmel_bwd(tab, x, d.B, d.T, d.F, w.scale, dfeats, w.dframes, ctx->an_cfg.fft32, s));
+    SG_STAGE(SG_STAGE_AN_OVERLAP_ADD, launch_an_frames_to_wave(w.dframes, d.B, d.T, d.F, w.scale, grad_out, x_update, lower, upper, step, grad_sign, s));
     if (x_update && x_next != x_update)
-        AN_HIP(hipMemcpyAsync(x_next, x_update, (size_t)d.B * d.T * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SG_HIP(hipMemcpyAsync(x_next, x_update, (size_t)d.B * d.T * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SG_OK;
 }
 
@@ -537,165 +496,119 @@ float* an_step_target(sg_ctx* ctx, const AnDims& d) {
     return w.x_alt;
 }
 
-// ---- the defended loops (sg_an_pgd_run_defended)
-struct AnDefCall {  // the caller's buffers and the chain, as the entry point received them
-    float* x_adv; const int64_t* y; const float* lower; const float* upper;
+// ---- the device-resident PGD loop (sg_an_pgd_run, sg_an_pgd_run_feco, sg_an_pgd_run_defended)
+struct AnLoopCall {  // the caller's buffers, the chain and the feature-level defense, as the entry point received them
+    float* x_adv;
+    const int64_t* y; int coef_rows;  // the labels the head reads: the caller's B (coef_rows 0), or ws.y_rep, once per repeat (coef_rows B)
+    const float* lower; const float* upper;
     int B, T;
     const sg_pgd_params* p;
-    const sg_wav_stage* chain; int n_stages;
-    const sg_feco_params* feco;
+    const sg_wav_stage* chain; int n_stages;  // n_stages 0: no chain
+    const sg_feco_params* feco;               // null: no FeCo between front-end and network
     uint8_t* success; int64_t* decisions; float* scores; float* loss; float* loss_trace; int64_t* decision_trace;
 };
 
-// an on-demand workspace buffer of at least `need` elements (grown before a loop: the stream drains first)
-template <typename T>
-int an_grow(sg_ctx* ctx, T** buf, size_t* cap, size_t need, hipStream_t s) {
-    AnWorkspace& w = ctx->an_ws;
-    if (*buf && *cap >= need) return SG_OK;
-    if (*buf) {
-        AN_HIP(hipStreamSynchronize(s));
-        (void)hipFree(*buf);
-        w.allocs.erase(std::remove(w.allocs.begin(), w.allocs.end(), static_cast<void*>(*buf)), w.allocs.end());
-        *buf = nullptr;
-        *cap = 0;
-    }
-    int rc = an_alloc(ctx, w.allocs, buf, need);
-    if (rc) return rc;
-    *cap = need;
+// FeCo inside a loop: 1 <= k <= F cluster frames, enough of them for the stack
+int an_feco_check(sg_ctx* ctx, const sg_feco_params* f, int B, int F) {
+    const bool k_ok = f->k >= 1 && f->k <= F && f->max_iter >= 1;
+    if (!an_plan(ctx, an_knobs(), B, k_ok ? f->k : 0, false).frames_ok)
+        return fail(ctx, SG_ERR_ARG, "FeCo: need 1 <= k <= %d frames, enough of them for the AudioNet stack, max_iter >= 1", F);
     return SG_OK;
 }
 
-// Chains with a backward of their own, no feature-level stage: every EOT repeat is a row of its own through chain, model and
-// both backwards (G repeats per pass); the repeats' cotangents are summed after the chain's backward, in repeat order.
-int an_def_loop_rows(sg_ctx* ctx, const AnDefCall& c, AnDims d, int reps, int G, hipStream_t s) {
-    AnWorkspace& w = ctx->an_ws;
-    DefWorkspace& dw = ctx->def_ws;
-    const sg_pgd_params* p = c.p;
-    const int B = c.B, T = c.T, F = d.F;
-    const size_t n = (size_t)B * T;
-    const AnKnobs knobs = an_knobs();
-    const int tail = reps % G;  // repeats of a last, smaller group
-    const AnNetPlan full_plan = an_plan(ctx, knobs, B * G, F, true), tail_plan = an_plan(ctx, knobs, B * (tail ? tail : G), F, true),
-                    final_plan = an_plan(ctx, knobs, B, F, false);
-    const bool want_rec = c.loss_trace || c.decision_trace;
-    int rc;
-    for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;  // the final pass is one forward repeat, chain included
-        const int nrep = last ? 1 : reps;
-        float* lrec = c.loss_trace ? c.loss_trace + (size_t)it * B : nullptr;
-        int64_t* drec = c.decision_trace ? c.decision_trace + (size_t)it * B : nullptr;
-        for (int g0 = 0; g0 < nrep; g0 += G) {
-            const int Gi = std::min(G, nrep - g0), rows = B * Gi;
-            const bool final_group = g0 + Gi >= nrep;
-            const uint64_t pass_key = (uint64_t)it * 0x9E3779B97F4A7C15ull + (uint64_t)g0 * 0xC2B2AE3D27D4EB4Full;
-            const float* cur = c.x_adv;
-            if (Gi > 1) {
-                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
-                for (int r = 0; r < Gi; ++r)
-                    AN_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, c.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
-                cur = dw.x_rep;
-            }
-            DefChainTape tape;
-            if ((rc = def_chain_forward(ctx, c.chain, c.n_stages, cur, rows, T, pass_key, Gi > 1 ? B : 0, &tape, &cur, s))) return rc;
-            d.B = rows;
-            d.keep_scale = false;  // the model's range decision: from the defended rows of every pass, as a model call takes it
-            if ((rc = an_frontend_forward(ctx, cur, d, s))) return rc;
-            // per-step records (attack/FGSM.py:50-58): loss averaged, decision voted over ALL repeats of the step.  One pass of
-            // several repeats records its rows and reduces them right after the head; when the repeats run as several passes
-            // (G < reps) every pass leaves its rows in repeat order and the last one reduces them.
-            const bool direct = nrep == 1, grouped = nrep > G;
-            float* lrows = grouped ? w.eot_loss_rows + (size_t)g0 * B : w.trace_l;
-            int64_t* drows = grouped ? w.eot_dec_rows + (size_t)g0 * B : w.trace_d;
-            float* ltr = !want_rec ? nullptr : (direct && lrec ? lrec : lrows);
-            int64_t* dtr = !want_rec ? nullptr : (direct && drec ? drec : drows);
-            const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? c.scores : nullptr, last ? c.decisions : nullptr,
-                                                 last ? c.loss : nullptr, ltr, dtr, last ? c.success : nullptr);
-            const AnEotRecords reduce = {nrep, B, lrec, drec};
-            const AnNetPlan& plan = last ? final_plan : (Gi == G ? full_plan : tail_plan);
-            rc = an_net_step(ctx, plan, w.feats, rows, head, want_rec && !direct && !grouped ? &reduce : nullptr, last ? nullptr : w.dfeats, s);
-            if (rc) return rc;
-            if (want_rec && grouped && final_group)
-                AN_HIP(launch_eot_trace_reduce(w.eot_loss_rows, w.eot_dec_rows, nrep, B, lrec, drec, s));
-            if (last) continue;
-            if ((rc = an_frontend_backward(ctx, cur, d, w.dfeats, dw.g[0], nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
-            int gi = 0;
-            if ((rc = def_chain_backward(ctx, c.chain, c.n_stages, tape, rows, T, &gi, s))) return rc;
-            // the repeats' sum, carried to the next group or turned into the step
-            AN_STAGE(SG_STAGE_DEF_REP_SUM,
-                     launch_wav_rep_sum_update(dw.g[gi], Gi, (int64_t)n, g0 > 0 ? w.grad_carry : nullptr, final_group ? nullptr : w.grad_carry,
-                                               final_group ? c.x_adv : nullptr, c.lower, c.upper, p->step_size, p->grad_sign, s));
-        }
-    }
-    return SG_OK;
-}
-
-// One pass of B defended rows per step: a QT / BDR-only chain (identity backward) in front of the model, and any
-// deterministic chain in front of FeCo (R clusterings per step, their gradients summed at the feature level).  With an
-// identity backward the log-mel adjoint steps the iterate directly (sg_an_pgd_run's waveform ping-pong); otherwise it
-// writes a plane, the chain's backward follows and the repeat-sum kernel over that one plane is the update.
-int an_def_loop_single(sg_ctx* ctx, const AnDefCall& c, AnDims d, bool identity, int R, hipStream_t s) {
+// One loop for every entry point.  A step's repeats are either `reps` repeats of the chain (AT: every repeat a row of its own
+// through chain, model and both backwards, G per pass, the cotangents summed after the chain's backward in repeat order and
+// carried from group to group), or R clusterings of FeCo behind ONE chain and front-end pass (their gradients summed at the
+// feature level); never both (reps == 1 or R == 1).  identity: no chain, or one whose backward is the identity (QT / BDR only):
+// d loss / d defended IS d loss / d iterate, and the log-mel adjoint steps the iterate directly -- the fused overlap-add from
+// one waveform buffer into another, so the iterate alternates between the caller's buffer and a workspace twin and is copied
+// home once if the attack ends on the twin.  Otherwise the adjoint writes a plane, the chain's backward follows and the
+// repeat-sum kernel is the update, in place.
+int an_pgd_loop(sg_ctx* ctx, const AnLoopCall& c, AnDims d, bool identity, int reps, int G, int R, hipStream_t s) {
     AnWorkspace& w = ctx->an_ws;
     DefWorkspace& dw = ctx->def_ws;
     const sg_pgd_params* p = c.p;
     const sg_feco_params* f = c.feco;
-    const int B = c.B, T = c.T, F = d.F, Fnet = f ? f->k : F;
+    const int B = c.B, T = c.T, F = d.F, Fnet = f ? f->k : F;  // Fnet: the frames the network sees in every pass
     const size_t n = (size_t)B * T;
+    const int step_reps = reps * R, cap = G * R;  // repeats of a step at either level, and how many of them a pass holds
     const AnKnobs knobs = an_knobs();
-    const AnNetPlan step_plan = an_plan(ctx, knobs, B * R, Fnet, true), final_plan = an_plan(ctx, knobs, B, Fnet, false);
+    const int tail = step_reps % cap;  // repeats of a last, smaller group
+    const AnNetPlan full_plan = an_plan(ctx, knobs, B * cap, Fnet, true), tail_plan = an_plan(ctx, knobs, B * (tail ? tail : cap), Fnet, true),
+                    final_plan = an_plan(ctx, knobs, B, Fnet, false);
+    const bool want_rec = c.loss_trace || c.decision_trace;
     d.B = B;
-    float* xc = c.x_adv;  // waveform ping-pong of the fused overlap-add (sg_an_pgd_run); a chain with a backward steps in place
+    float* xc = c.x_adv;
     float* xn = identity ? an_step_target(ctx, d) : nullptr;
     if (!xn) xn = c.x_adv;
     int rc;
     for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;
-        const int Ri = last ? 1 : R, rows = B * Ri;
-        const float* cur = xc;
-        DefChainTape tape;
-        if ((rc = def_chain_forward(ctx, c.chain, c.n_stages, cur, B, T, 0, 0, &tape, &cur, s))) return rc;
-        d.keep_scale = false;  // the model's range decision: from the defended rows of every pass
-        if ((rc = an_frontend_forward(ctx, cur, d, s))) return rc;
-        const float* net_in = w.feats;
-        if (f) {
-            const uint64_t key = f->seed + (uint64_t)it * 0x9E3779B97F4A7C15ull;  // repeat r: + r * 0xC2B2AE3D27D4EB4F
-            trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 0);
-            rc = sg_feco_kmeans_compress(ctx, w.feats, B, F, kAnMel, f->k, f->max_iter, f->random_init, key, f->index_base, Ri,
-                                         w.feco_ids, w.feco_out, w.feco_cnt, s);
-            if (rc) return rc;
-            trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 1);
-            net_in = w.feco_out;
-        }
         float* lrec = c.loss_trace ? c.loss_trace + (size_t)it * B : nullptr;
         int64_t* drec = c.decision_trace ? c.decision_trace + (size_t)it * B : nullptr;
-        const bool direct = Ri == 1, rec = lrec || drec;
-        float* ltr = !rec ? nullptr : (direct && lrec ? lrec : w.trace_l);
-        int64_t* dtr = !rec ? nullptr : (direct && drec ? drec : w.trace_d);
-        const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? c.scores : nullptr, last ? c.decisions : nullptr,
-                                             last ? c.loss : nullptr, ltr, dtr, last ? c.success : nullptr);
-        const AnEotRecords reduce = {Ri, B, lrec, drec};
-        rc = an_net_step(ctx, last ? final_plan : step_plan, net_in, rows, head, rec && !direct ? &reduce : nullptr,
-                         last ? nullptr : (f ? w.dfeco : w.dfeats), s);
-        if (rc) return rc;
-        if (last) break;
-        if (f) {
-            trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 0);
-            if ((rc = sg_feco_compress_backward_reps(ctx, w.dfeco, w.feco_ids, w.feco_cnt, B, F, kAnMel, f->k, 1, Ri, w.dfeats, s))) return rc;
-            trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 1);
-        }
-        if (identity) {  // d loss / d defended IS d loss / d iterate: straight into the update
-            rc = an_frontend_backward(ctx, cur, d, w.dfeats, nullptr, xc, xn, c.lower, c.upper, p->step_size, p->grad_sign, s);
+        for (int g0 = 0, more = 1; more; g0 += cap) {
+            const LoopPass ps = loop_pass(it, p->max_iter, g0, cap, step_reps, B, want_rec);  // the final pass: one forward repeat
+            more = !ps.final_group;
+            const int Gc = f ? 1 : ps.Gi, Ri = f ? ps.Gi : 1;  // repeats in front of the log-mel front-end / clusterings behind it
+            const int rows = B * Gc;
+            const float* cur = xc;
+            if (Gc > 1) {
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 0);
+                for (int r = 0; r < Gc; ++r)
+                    SG_HIP(hipMemcpyAsync(dw.x_rep + (size_t)r * n, xc, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                trace_mark(ctx, SG_STAGE_DEF_REPLICATE, s, 1);
+                cur = dw.x_rep;
+            }
+            DefChainTape tape;  // (no stages: cur stays the iterate)
+            if ((rc = def_chain_forward(ctx, c.chain, c.n_stages, cur, rows, T, ps.pass_key, Gc > 1 ? B : 0, &tape, &cur, s))) return rc;
+            d.B = rows;
+            // the model's range decision: iterates stay in [-1, 1], one decision serves; behind a chain it is taken from the
+            // defended rows of every pass, as a model call takes it
+            d.keep_scale = c.n_stages == 0 && it > 0;
+            if ((rc = an_frontend_forward(ctx, cur, d, s))) return rc;
+            const float* net_in = w.feats;
+            float* dnet = w.dfeats;
+            if (f) {
+                trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 0);
+                rc = sg_feco_kmeans_compress(ctx, w.feats, B, F, kAnMel, f->k, f->max_iter, f->random_init, f->seed + ps.pass_key /* repeat r: + r * kRepKey */,
+                                             f->index_base, Ri, w.feco_ids, w.feco_out, w.feco_cnt, s);
+                if (rc) return rc;
+                trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 1);
+                net_in = w.feco_out;
+                dnet = w.dfeco;
+            }
+            // per-step records (LoopPass::Records): a pass of several repeats reduces its rows right after the head, the groups of
+            // a step after the last one
+            const AnHeadArgs head = an_head_args(ctx, c.y, p->loss, c.coef_rows, nullptr, ps.last ? c.scores : nullptr, ps.last ? c.decisions : nullptr,
+                                                 ps.last ? c.loss : nullptr, loop_record_rows(ps, lrec, w.trace_l, w.eot_loss_rows),
+                                                 loop_record_rows(ps, drec, w.trace_d, w.eot_dec_rows), ps.last ? c.success : nullptr);
+            const AnEotRecords reduce = {ps.nrep, B, lrec, drec};
+            const AnNetPlan& plan = ps.last ? final_plan : (ps.Gi == cap ? full_plan : tail_plan);
+            rc = an_net_step(ctx, plan, net_in, ps.rows, head, ps.rec == LoopPass::PASS ? &reduce : nullptr, ps.last ? nullptr : dnet, s);
             if (rc) return rc;
-            if (xn != xc) std::swap(xc, xn);
-            continue;
+            if (ps.rec == LoopPass::GROUPED && ps.reduce)
+                SG_HIP(launch_eot_trace_reduce(w.eot_loss_rows, w.eot_dec_rows, ps.nrep, B, lrec, drec, s));
+            if (ps.last) continue;
+            if (f) {
+                trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 0);
+                if ((rc = sg_feco_compress_backward_reps(ctx, w.dfeco, w.feco_ids, w.feco_cnt, B, F, kAnMel, f->k, 1, Ri, w.dfeats, s))) return rc;
+                trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 1);
+            }
+            if (identity) {  // straight into the update (one pass per step: Gc == 1)
+                rc = an_frontend_backward(ctx, cur, d, w.dfeats, nullptr, xc, xn, c.lower, c.upper, p->step_size, p->grad_sign, s);
+                if (rc) return rc;
+                if (xn != xc) std::swap(xc, xn);
+                continue;
+            }
+            if ((rc = an_frontend_backward(ctx, cur, d, w.dfeats, dw.g[0], nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+            int gi = 0;
+            if ((rc = def_chain_backward(ctx, c.chain, c.n_stages, tape, rows, T, &gi, s))) return rc;
+            // the repeats' sum, carried to the next group or turned into the step
+            SG_STAGE(SG_STAGE_DEF_REP_SUM,
+                     launch_wav_rep_sum_update(dw.g[gi], Gc, (int64_t)n, g0 > 0 ? w.grad_carry : nullptr, ps.final_group ? nullptr : w.grad_carry,
+                                               ps.final_group ? xc : nullptr, c.lower, c.upper, p->step_size, p->grad_sign, s));
         }
-        if ((rc = an_frontend_backward(ctx, cur, d, w.dfeats, dw.g[0], nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
-        int gi = 0;
-        if ((rc = def_chain_backward(ctx, c.chain, c.n_stages, tape, B, T, &gi, s))) return rc;
-        AN_STAGE(SG_STAGE_DEF_REP_SUM, launch_wav_rep_sum_update(dw.g[gi], 1, (int64_t)n, nullptr, nullptr, xc, c.lower, c.upper, p->step_size,
-                                                                 p->grad_sign, s));
     }
-    if (xc != c.x_adv) AN_HIP(hipMemcpyAsync(c.x_adv, xc, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (xc != c.x_adv) SG_HIP(hipMemcpyAsync(c.x_adv, xc, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SG_OK;
 }
 
@@ -707,14 +620,14 @@ int32_t sg_an_num_frames(int32_t T) { return an_num_frames(T); }
 
 int sg_an_load(sg_ctx* ctx, const sg_an_weights* w) {
     if (!ctx || !w) return SG_ERR_ARG;
-    if (w->num_class < 1 || w->num_class > 1024) return an_fail(ctx, SG_ERR_ARG, "num_class must be 1..1024");
-    if (!w->conv1_weight || !w->conv1_bias || !w->fc_weight || !w->fc_bias) return an_fail(ctx, SG_ERR_ARG, "missing tensor");
+    if (w->num_class < 1 || w->num_class > 1024) return fail(ctx, SG_ERR_ARG, "num_class must be 1..1024");
+    if (!w->conv1_weight || !w->conv1_bias || !w->fc_weight || !w->fc_bias) return fail(ctx, SG_ERR_ARG, "missing tensor");
     for (int i = 0; i < 4; ++i)
-        if (!w->bn1[i]) return an_fail(ctx, SG_ERR_ARG, "missing conv1 BatchNorm tensor");
+        if (!w->bn1[i]) return fail(ctx, SG_ERR_ARG, "missing conv1 BatchNorm tensor");
     for (int l = 0; l < kAnConv; ++l)
         if (!w->conv_weight[l] || !w->conv_bias[l] || !w->bn_weight[l] || !w->bn_bias[l] || !w->bn_mean[l] || !w->bn_var[l])
-            return an_fail(ctx, SG_ERR_ARG, "missing tensor for conv%d", l + 2);
-    AN_HIP(hipSetDevice(ctx->device));
+            return fail(ctx, SG_ERR_ARG, "missing tensor for conv%d", l + 2);
+    SG_HIP(hipSetDevice(ctx->device));
     int rc = an_build_tables(ctx);
     if (rc) return rc;
     const double eps = w->bn_eps > 0.f ? w->bn_eps : 1e-5;
@@ -729,7 +642,7 @@ int sg_an_load(sg_ctx* ctx, const sg_an_weights* w) {
         std::vector<float> w25(25);
         for (int i = 0; i < 25; ++i) w25[i] = (float)(w->conv1_weight[i] * sc);  // [mel offset][time offset]
         m.pre_bias = (float)((w->conv1_bias[0] - mean) * sc + beta);
-        rc |= an_upload(ctx, pool, &m.w25, w25);
+        rc |= dev_upload(ctx, pool, &m.w25, w25);
     }
     for (int l = 0; l < kAnConv; ++l) {
         const int cin = kAnCin[l], cout = kAnCout[l];
@@ -744,8 +657,8 @@ int sg_an_load(sg_ctx* ctx, const sg_an_weights* w) {
                     wb[((size_t)j * cout + co) * cin + ci] = v;
                 }
         }
-        rc |= an_upload(ctx, pool, &m.wf[l], wf);
-        rc |= an_upload(ctx, pool, &m.wb[l], wb);
+        rc |= dev_upload(ctx, pool, &m.wf[l], wf);
+        rc |= dev_upload(ctx, pool, &m.wb[l], wb);
         auto packed = [](const std::vector<float>& w, int K, int N) {  // [K][N] -> k4-major [K/4][N][4]
             std::vector<float> q((size_t)K * N);
             for (int k = 0; k < K; ++k)
@@ -754,20 +667,20 @@ int sg_an_load(sg_ctx* ctx, const sg_an_weights* w) {
         };
         // (every layer: the fused CNN kernels take all their weights k4-packed; the per-layer sequence uses the packed copy
         // where its quad-fed tile kernel applies, N % 128 == 0)
-        rc |= an_upload(ctx, pool, &m.wfq[l], packed(wf, 3 * cin, cout));
-        rc |= an_upload(ctx, pool, &m.wbq[l], packed(wb, 3 * cout, cin));
-        rc |= an_upload(ctx, pool, &m.bias[l], bias);
+        rc |= dev_upload(ctx, pool, &m.wfq[l], packed(wf, 3 * cin, cout));
+        rc |= dev_upload(ctx, pool, &m.wbq[l], packed(wb, 3 * cout, cin));
+        rc |= dev_upload(ctx, pool, &m.bias[l], bias);
     }
-    rc |= an_upload(ctx, pool, &m.fc_w, std::vector<float>(w->fc_weight, w->fc_weight + (size_t)w->num_class * 32));
-    rc |= an_upload(ctx, pool, &m.fc_b, std::vector<float>(w->fc_bias, w->fc_bias + w->num_class));
-    if (rc) return an_fail(ctx, SG_ERR_HIP, "model upload failed: %s", ctx->err.c_str());
+    rc |= dev_upload(ctx, pool, &m.fc_w, std::vector<float>(w->fc_weight, w->fc_weight + (size_t)w->num_class * 32));
+    rc |= dev_upload(ctx, pool, &m.fc_b, std::vector<float>(w->fc_bias, w->fc_bias + w->num_class));
+    if (rc) return fail(ctx, SG_ERR_HIP, "model upload failed: %s", ctx->err.c_str());
     m.S = w->num_class;
     m.loaded = true;
     return SG_OK;
 }
 
 int sg_an_logmel(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, float* feats_dev, void* stream) {
-    if (!ctx || !x_dev || !feats_dev || B < 1 || T < kAnFft) return an_fail(ctx, SG_ERR_ARG, "bad argument");
+    if (!ctx || !x_dev || !feats_dev || B < 1 || T < kAnFft) return fail(ctx, SG_ERR_ARG, "bad argument");
     int rc = an_build_tables(ctx);
     if (rc) return rc;
     float* scale = nullptr;
@@ -786,14 +699,14 @@ int sg_an_logmel(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, float* f
         if (rc) return rc;
     }
     scale = ctx->an_ws.scale;
-    AN_HIP(launch_input_scale(x_dev, (int64_t)B * T, ctx->range_scratch, scale, 1, s));
-    AN_HIP(launch_an_logmel_fwd(tab, x_dev, B, T, an_num_frames(T), scale, feats_dev, ctx->an_cfg.fft32, s));
+    SG_HIP(launch_input_scale(x_dev, (int64_t)B * T, ctx->range_scratch, scale, 1, s));
+    SG_HIP(launch_an_logmel_fwd(tab, x_dev, B, T, an_num_frames(T), scale, feats_dev, ctx->an_cfg.fft32, s));
     return SG_OK;
 }
 
 int sg_an_logmel_backward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, const float* dfeats_dev, float* grad_dev,
                           int32_t reuse_forward, void* stream) {
-    if (!x_dev || !dfeats_dev || !grad_dev) return an_fail(ctx, SG_ERR_ARG, "bad argument");
+    if (!x_dev || !dfeats_dev || !grad_dev) return fail(ctx, SG_ERR_ARG, "bad argument");
     AnDims d;
     int rc = an_check(ctx, B, T, 0, &d);  // sizes the per-frame gradient scratch
     if (rc) return rc;
@@ -804,22 +717,22 @@ int sg_an_logmel_backward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T,
         tab.mel_cache = w.mel_cache;
         tab.spec_cache = w.cache_spec ? w.spec_cache : nullptr;
     }
-    AN_HIP(launch_input_scale(x_dev, (int64_t)B * T, ctx->range_scratch, w.scale, 1, s));
+    SG_HIP(launch_input_scale(x_dev, (int64_t)B * T, ctx->range_scratch, w.scale, 1, s));
     if (tab.mel_cache && an_use_ola(ctx, d.B, d.F)) {  // the attack loops' form of the adjoint (same sums in the same order as the pair below)
         AnOlaArgs a{};
         a.x = x_dev; a.dfeats = dfeats_dev; a.dframes = w.dframes; a.grad_out = grad_dev; a.scale_p = w.scale;
         a.B = d.B; a.T = d.T; a.F = d.F;
-        AN_HIP(launch_an_logmel_bwd_ola(tab, a, ctx->an_cfg.fft32, ctx->num_cus, s));
+        SG_HIP(launch_an_logmel_bwd_ola(tab, a, ctx->an_cfg.fft32, ctx->num_cus, s));
         return SG_OK;
     }
-    AN_HIP(launch_an_logmel_bwd(tab, x_dev, d.B, d.T, d.F, w.scale, dfeats_dev, w.dframes, ctx->an_cfg.fft32, s));
-    AN_HIP(launch_an_frames_to_wave(w.dframes, d.B, d.T, d.F, w.scale, grad_dev, nullptr, nullptr, nullptr, 0.f, 1, s));
+    SG_HIP(launch_an_logmel_bwd(tab, x_dev, d.B, d.T, d.F, w.scale, dfeats_dev, w.dframes, ctx->an_cfg.fft32, s));
+    SG_HIP(launch_an_frames_to_wave(w.dframes, d.B, d.T, d.F, w.scale, grad_dev, nullptr, nullptr, nullptr, 0.f, 1, s));
     return SG_OK;
 }
 
 int sg_an_configure(sg_ctx* ctx, int32_t fft_bits, int32_t spectrum_cache, int32_t fused_overlap_add) {
     if (!ctx) return SG_ERR_ARG;
-    if (fft_bits != 32 && fft_bits != 64) return an_fail(ctx, SG_ERR_ARG, "fft_bits must be 32 or 64");
+    if (fft_bits != 32 && fft_bits != 64) return fail(ctx, SG_ERR_ARG, "fft_bits must be 32 or 64");
     ctx->an_cfg.fft32 = fft_bits == 32;
     ctx->an_cfg.spec_cache = spectrum_cache < 0 ? -1 : (spectrum_cache != 0);
     ctx->an_cfg.ola = fused_overlap_add < 0 ? -1 : (fused_overlap_add != 0);
@@ -833,7 +746,7 @@ int sg_an_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, in
     AnDims d;
     int rc = an_check(ctx, B, T_or_F, flag, &d);
     if (rc) return rc;
-    if (!x_dev) return an_fail(ctx, SG_ERR_ARG, "x is NULL");
+    if (!x_dev) return fail(ctx, SG_ERR_ARG, "x is NULL");
     hipStream_t s = (hipStream_t)stream;
     const AnNetPlan plan = an_plan(ctx, an_knobs(), B, d.F, false);
     const float* feats = x_dev;
@@ -847,7 +760,7 @@ int sg_an_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, in
 
 int sg_an_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t capacity_floats, int32_t* rows_per_utt,
                            int32_t* channels, void* stream) {
-    if (!ctx || layer < 1 || layer > kAnConv + 1 || !ctx->an_ws.scale) return an_fail(ctx, SG_ERR_ARG, "bad layer or no pass run");
+    if (!ctx || layer < 1 || layer > kAnConv + 1 || !ctx->an_ws.scale) return fail(ctx, SG_ERR_ARG, "bad layer or no pass run");
     const AnWorkspace& w = ctx->an_ws;
     const float* src;
     int rows, ch;
@@ -861,10 +774,10 @@ int sg_an_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t c
     if (rows_per_utt) *rows_per_utt = rows;
     if (channels) *channels = ch;
     if (out_dev) {
-        if (capacity_floats <= 0) return an_fail(ctx, SG_ERR_ARG, "capacity must be positive");
+        if (capacity_floats <= 0) return fail(ctx, SG_ERR_ARG, "capacity must be positive");
         const size_t held = (size_t)w.B * (size_t)(rows > 0 ? rows : 1) * ch;  // never read past what the workspace holds
         const size_t n = (size_t)capacity_floats < held ? (size_t)capacity_floats : held;
-        AN_HIP(hipMemcpyAsync(out_dev, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        SG_HIP(hipMemcpyAsync(out_dev, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return SG_OK;
 }
@@ -875,8 +788,8 @@ int sg_an_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
     AnDims d;
     int rc = an_check(ctx, B, T_or_F, flag, &d);
     if (rc) return rc;
-    if (!x_dev || !y_dev || !loss) return an_fail(ctx, SG_ERR_ARG, "x, y and loss are required");
-    if (loss->loss == SG_LOSS_LINEAR && !loss->coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
+    if (!x_dev || !y_dev || !loss) return fail(ctx, SG_ERR_ARG, "x, y and loss are required");
+    if (loss->loss == SG_LOSS_LINEAR && !loss->coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
     hipStream_t s = (hipStream_t)stream;
     AnWorkspace& w = ctx->an_ws;
     const AnNetPlan plan = an_plan(ctx, an_knobs(), B, d.F, grad_dev != nullptr);
@@ -897,48 +810,24 @@ int sg_an_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     AnDims d;
     int rc = an_check(ctx, B, T, 0, &d);
     if (rc) return rc;
-    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return an_fail(ctx, SG_ERR_ARG, "NULL argument");
-    if (p->max_iter < 0) return an_fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
-    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
-    hipStream_t s = (hipStream_t)stream;
-    AnWorkspace& w = ctx->an_ws;
-    const AnKnobs knobs = an_knobs();
-    const AnNetPlan step_plan = an_plan(ctx, knobs, B, d.F, true), final_plan = an_plan(ctx, knobs, B, d.F, false);
-    // the fused overlap-add steps from one waveform buffer into another: the iterate alternates between the caller's
-    // buffer and a workspace twin and is copied home once if the attack ends on the twin
-    float* xc = x_adv_dev;
-    float* xn = an_step_target(ctx, d);
-    if (!xn) xn = x_adv_dev;
-    for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;  // the final pass is a single forward
-        d.keep_scale = it > 0;  // iterates stay in [-1, 1]
-        if ((rc = an_frontend_forward(ctx, xc, d, s))) return rc;
-        const AnHeadArgs head = an_head_args(ctx, y_dev, p->loss, 0, nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr,
-                                             last ? loss_dev : nullptr, loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr,
-                                             decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr, last ? success_dev : nullptr);
-        if ((rc = an_net_step(ctx, last ? final_plan : step_plan, w.feats, B, head, nullptr, last ? nullptr : w.dfeats, s))) return rc;
-        if (last) break;
-        rc = an_frontend_backward(ctx, xc, d, w.dfeats, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s);
-        if (rc) return rc;
-        if (xn != xc) std::swap(xc, xn);
-    }
-    if (xc != x_adv_dev) AN_HIP(hipMemcpyAsync(x_adv_dev, xc, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return SG_OK;
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p, nullptr, p))) return rc;
+    // the model is deterministic: one pass stands for every EOT repeat, and the final pass is a single forward
+    const AnLoopCall c{x_adv_dev, y_dev, 0, lower_dev, upper_dev, B, T, p, nullptr, 0, nullptr,
+                       success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+    return an_pgd_loop(ctx, c, d, true, 1, 1, 1, (hipStream_t)stream);
 }
 
 int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
                        int32_t B, int32_t T, const sg_pgd_params* p, const sg_feco_params* f, uint8_t* success_dev,
                        int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* loss_trace_dev,
                        int64_t* decision_trace_dev, void* stream) {
+    int rc, eot_size;
     if (!ctx) return SG_ERR_ARG;
-    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p || !f) return an_fail(ctx, SG_ERR_ARG, "NULL argument");
-    if (p->max_iter < 0) return an_fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
-    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p || !f, nullptr, p))) return rc;
     // defense/feature_level.py:33: with a single utterance the reference DROPS empty clusters (variable frame count);
     // that case stays on the host-chained path (model/defended_model.py)
-    if (B < 2) return an_fail(ctx, SG_ERR_ARG, "the fused FeCo loop needs a batch of at least 2 utterances");
-    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
-    if (eot_size % eot_bs) return an_fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
+    if (B < 2) return fail(ctx, SG_ERR_ARG, "the fused FeCo loop needs a batch of at least 2 utterances");
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
     // Expectation over the defense's randomness (adaptive_attack/EOT.py:16-54): eot_size clusterings per gradient step,
     // each started from fresh random frames.  The reference repeats the batch (x_batch.repeat, EOT.py:24) and runs the
     // whole model on the copies; only the DEFENSE is random here, so the log-mel front-end runs once per step, the R
@@ -947,58 +836,17 @@ int sg_an_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
     // sum to the waveform: sign(sum) == sign(mean).  (EOT_batch_size only says how the reference cuts the repeats into
     // model calls.)  The evenly started clustering is a deterministic function of its input: every repeat is the same
     // computation, one stands for all.  The final pass is a single forward.
-    const int reps = f->random_init ? eot_size : 1;
+    const int R = f->random_init ? eot_size : 1;
     AnDims d;
-    int rc = an_check(ctx, B * reps, T, 0, &d);  // workspace for the batch of R x B rows
-    if (rc) return rc;
-    d.B = B;
-    const int k = f->k;
-    // the network sees k frames in every pass, the first one included: R x B rows at a gradient step, B at the final forward
-    const AnKnobs knobs = an_knobs();
-    const bool k_ok = k >= 1 && k <= d.F && f->max_iter >= 1;
-    const AnNetPlan step_plan = an_plan(ctx, knobs, B * reps, k_ok ? k : 0, true), final_plan = an_plan(ctx, knobs, B, k_ok ? k : 0, false);
-    if (!final_plan.frames_ok)
-        return an_fail(ctx, SG_ERR_ARG, "FeCo: need 1 <= k <= %d frames, enough of them for the AudioNet stack, max_iter >= 1", d.F);
+    if ((rc = an_check(ctx, B * R, T, 0, &d))) return rc;  // workspace for the batch of R x B rows
+    if ((rc = an_feco_check(ctx, f, B, d.F))) return rc;
     hipStream_t s = (hipStream_t)stream;
     AnWorkspace& w = ctx->an_ws;
-    for (int r = 0; r < reps; ++r)
-        AN_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    float* xc = x_adv_dev;  // waveform ping-pong of the fused overlap-add (sg_an_pgd_run)
-    float* xn = an_step_target(ctx, d);
-    if (!xn) xn = x_adv_dev;
-    for (int it = 0; it <= p->max_iter; ++it) {
-        const bool last = it == p->max_iter;
-        const int R = last ? 1 : reps, rows = B * R;
-        d.keep_scale = it > 0;  // iterates stay in [-1, 1]
-        if ((rc = an_frontend_forward(ctx, xc, d, s))) return rc;
-        const uint64_t key = f->seed + (uint64_t)it * 0x9E3779B97F4A7C15ull;  // repeat r: + r * 0xC2B2AE3D27D4EB4F
-        trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 0);
-        rc = sg_feco_kmeans_compress(ctx, w.feats, B, d.F, kAnMel, k, f->max_iter, f->random_init, key, f->index_base, R,
-                                     w.feco_ids, w.feco_out, w.feco_cnt, s);
-        if (rc) return rc;
-        trace_mark(ctx, SG_STAGE_AN_FECO_FWD, s, 1);
-        // per-step records as the reference prints them (attack/FGSM.py:50-58): the loss averaged over the step's EOT
-        // repeats, the decision voted over them
-        float* lrec = loss_trace_dev ? loss_trace_dev + (size_t)it * B : nullptr;
-        int64_t* drec = decision_trace_dev ? decision_trace_dev + (size_t)it * B : nullptr;
-        const bool direct = R == 1, rec = lrec || drec;
-        float* ltr = !rec ? nullptr : (direct && lrec ? lrec : w.trace_l);
-        int64_t* dtr = !rec ? nullptr : (direct && drec ? drec : w.trace_d);
-        const AnHeadArgs head = an_head_args(ctx, w.y_rep, p->loss, B, nullptr, last ? scores_dev : nullptr, last ? decisions_dev : nullptr,
-                                             last ? loss_dev : nullptr, ltr, dtr, last ? success_dev : nullptr);
-        const AnEotRecords reduce = {R, B, lrec, drec};
-        rc = an_net_step(ctx, last ? final_plan : step_plan, w.feco_out, rows, head, rec && !direct ? &reduce : nullptr, last ? nullptr : w.dfeco, s);
-        if (rc) return rc;
-        if (last) break;
-        trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 0);
-        if ((rc = sg_feco_compress_backward_reps(ctx, w.dfeco, w.feco_ids, w.feco_cnt, B, d.F, kAnMel, k, 1, R, w.dfeats, s))) return rc;
-        trace_mark(ctx, SG_STAGE_AN_FECO_BWD, s, 1);
-        rc = an_frontend_backward(ctx, xc, d, w.dfeats, nullptr, xc, xn, lower_dev, upper_dev, p->step_size, p->grad_sign, s);
-        if (rc) return rc;
-        if (xn != xc) std::swap(xc, xn);
-    }
-    if (xc != x_adv_dev) AN_HIP(hipMemcpyAsync(x_adv_dev, xc, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return SG_OK;
+    for (int r = 0; r < R; ++r)
+        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    const AnLoopCall c{x_adv_dev, w.y_rep, B, lower_dev, upper_dev, B, T, p, nullptr, 0, f,
+                       success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+    return an_pgd_loop(ctx, c, d, true, 1, 1, R, s);
 }
 
 int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
@@ -1006,22 +854,19 @@ int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
                            const sg_feco_params* feco, uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev,
                            float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev, void* stream) {
     static const char* who = "sg_an_pgd_run_defended";
-    int rc;
+    int rc, eot_size;
     if (!ctx) return SG_ERR_ARG;
-    if (!x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p) return an_fail(ctx, SG_ERR_ARG, "NULL argument");
-    if (B < 1 || T < kAnFft) return an_fail(ctx, SG_ERR_ARG, "need B >= 1 and a waveform of at least one 1024-sample STFT frame");
-    if (p->max_iter < 0) return an_fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
-    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return an_fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
-    const int eot_size = p->eot_size > 0 ? p->eot_size : 1, eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
-    if (eot_size % eot_bs) return an_fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
+    const char* shape = B < 1 || T < kAnFft ? "need B >= 1 and a waveform of at least one 1024-sample STFT frame" : nullptr;
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p, shape, p))) return rc;
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
     // ---- the chain: everything a stage call would refuse, before the first launch
     DefChainInfo ci;
     if ((rc = def_chain_check(ctx, who, chain, n_stages, &ci))) return rc;
     if (feco) {
         // (one utterance: the reference drops empty clusters, sg_an_pgd_run_feco)
-        if (B < 2) return an_fail(ctx, SG_ERR_ARG, "%s: the FeCo loop needs a batch of at least 2 utterances", who);
+        if (B < 2) return fail(ctx, SG_ERR_ARG, "%s: the FeCo loop needs a batch of at least 2 utterances", who);
         // the clusterings' gradients are summed at the feature level, behind ONE chain pass: that pass must not be random
-        if (ci.randomised) return an_fail(ctx, SG_ERR_ARG, "%s: a randomised stage (AT) in front of FeCo is not supported in the loop", who);
+        if (ci.randomised) return fail(ctx, SG_ERR_ARG, "%s: a randomised stage (AT) in front of FeCo is not supported in the loop", who);
     }
     // Repeats: AT makes the repeats of a step differ (AudioNet has no dither); otherwise one pass stands for all.  With FeCo
     // only the clustering is repeated (R times, behind one chain and front-end pass).
@@ -1032,33 +877,27 @@ int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
     const int G = (int)std::min<long>(reps, std::max<long>(1, cap / B));
     const bool per_row = !ci.identity;  // the chain has a backward of its own: cotangent planes are needed
     const int chain_rows = B * G;
-    if (chain_rows > 65535) return an_fail(ctx, SG_ERR_ARG, "%s: %d rows per pass, the stage kernels take at most 65535: split the batch", who, chain_rows);
+    if (chain_rows > 65535) return fail(ctx, SG_ERR_ARG, "%s: %d rows per pass, the stage kernels take at most 65535: split the batch", who, chain_rows);
     AnDims d;
     if ((rc = an_check(ctx, feco ? B * R : chain_rows, T, 0, &d))) return rc;  // workspace for the largest pass
-    if (feco) {
-        const bool k_ok = feco->k >= 1 && feco->k <= d.F && feco->max_iter >= 1;
-        if (!an_plan(ctx, an_knobs(), B, k_ok ? feco->k : 0, false).frames_ok)
-            return an_fail(ctx, SG_ERR_ARG, "FeCo: need 1 <= k <= %d frames, enough of them for the AudioNet stack, max_iter >= 1", d.F);
-    }
+    if (feco && (rc = an_feco_check(ctx, feco, B, d.F))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = ensure_def_workspace(ctx, chain_rows, T, n_stages, ci.n_saved, per_row, s)))
-        return an_fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
+        return fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
     AnWorkspace& w = ctx->an_ws;
-    const bool want_rec = loss_trace_dev || decision_trace_dev;
-    if (G < reps) {  // the repeats of a step run as several passes
-        if ((rc = an_grow(ctx, &w.grad_carry, &w.grad_carry_cap, (size_t)B * T, s))) return rc;
-        size_t cap_rows = w.eot_rows_cap;
-        if (want_rec && (rc = an_grow(ctx, &w.eot_loss_rows, &cap_rows, (size_t)reps * B, s))) return rc;
-        if (want_rec && (rc = an_grow(ctx, &w.eot_dec_rows, &w.eot_rows_cap, (size_t)reps * B, s))) return rc;
+    if (G < reps) {  // the repeats of a step run as several passes: the carried sum, and the rows of LoopPass::GROUPED
+        const bool want_rec = loss_trace_dev || decision_trace_dev;
+        if ((rc = dev_grow(ctx, w.allocs, &w.grad_carry, &w.grad_carry_cap, (size_t)B * T, s))) return rc;
+        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, &w.eot_loss_cap, (size_t)reps * B, s))) return rc;
+        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, &w.eot_dec_cap, (size_t)reps * B, s))) return rc;
     }
     for (int r = 0; r < (feco ? R : G); ++r)
-        AN_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     // the iterate is clamped into [lower, upper] within [-1, 1] at every step: a first stage's decision is taken once
-    if ((rc = def_chain_first_scale(ctx, chain, x_adv_dev, (int64_t)B * T, s))) return an_fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
-    const AnDefCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p, chain, n_stages, feco,
-                      success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
-    if (feco || ci.identity) return an_def_loop_single(ctx, c, d, ci.identity, R, s);
-    return an_def_loop_rows(ctx, c, d, reps, G, s);
+    if ((rc = def_chain_first_scale(ctx, chain, x_adv_dev, (int64_t)B * T, s))) return fail(ctx, rc, "%s: %s", who, ctx->err.c_str());
+    const AnLoopCall c{x_adv_dev, w.y_rep, B, lower_dev, upper_dev, B, T, p, chain, n_stages, feco,
+                       success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev};
+    return an_pgd_loop(ctx, c, d, ci.identity, reps, G, R, s);
 }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
 // Internal declarations shared by the HIP translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
 #include <stdint.h>
 #include <string>
@@ -159,8 +162,9 @@ struct AnWorkspace {
     float* grad_carry = nullptr;     // (n) floats, n = utterances x T of the call
     size_t grad_carry_cap = 0;
     float* eot_loss_rows = nullptr;  // (reps * utterances)
+    size_t eot_loss_cap = 0;
     int64_t* eot_dec_rows = nullptr;
-    size_t eot_rows_cap = 0;
+    size_t eot_dec_cap = 0;
     // which input the mel cache belongs to (sg_an_logmel_backward(reuse_forward) checks pointer and shape, not contents)
     const float* cache_x = nullptr;
     int cache_B = 0, cache_T = 0;
@@ -259,8 +263,9 @@ struct Workspace {
     float* grad = nullptr;             // [B][T]
     int64_t* y_rep = nullptr;          // [B] labels repeated for EOT repeats batched into one pass
     float* eot_loss_rows = nullptr;    // [reps * B] per-repeat records of a step whose repeats run as several passes
+    size_t eot_loss_cap = 0;
     int64_t* eot_dec_rows = nullptr;
-    size_t eot_rows_cap = 0;
+    size_t eot_dec_cap = 0;
     std::vector<void*> allocs;
 };
 
@@ -343,6 +348,128 @@ inline void trace_mark(sg_ctx* ctx, int tag, hipStream_t s, int after) {
         if (hipEventRecord(ctx->trace_ev[2 * ctx->trace_used + 1], s) == hipSuccess) ++ctx->trace_used;
         else ++ctx->trace_dropped;
     }
+}
+
+// ---------------------------------------------------------------- host helpers of the entry points
+// a refusal or failure: the text goes to the context (sg_last_error), the code back to the caller
+inline int fail(sg_ctx* ctx, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (ctx) ctx->err = buf;
+    return code;
+}
+
+// inside a function with `ctx` (and, for SG_STAGE, the stream `s`) in scope
+#define SG_HIP(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return sg::fail(ctx, SG_ERR_HIP, "%s failed: %s (%s:%d)", #expr,         \
+                                              hipGetErrorString(e_), __FILE__, __LINE__);              \
+    } while (0)
+
+#define SG_STAGE(tag, expr)               \
+    do {                                  \
+        sg::trace_mark(ctx, (tag), s, 0); \
+        SG_HIP(expr);                     \
+        sg::trace_mark(ctx, (tag), s, 1); \
+    } while (0)
+
+// device memory owned by `pool` (a model's or a workspace's list: freed with it)
+template <typename T>
+int dev_alloc(sg_ctx* ctx, std::vector<void*>& pool, T** out, size_t count) {
+    void* p = nullptr;
+    SG_HIP(hipMalloc(&p, count * sizeof(T) + 256));
+    pool.push_back(p);
+    *out = reinterpret_cast<T*>(p);
+    return SG_OK;
+}
+template <typename T>
+int dev_upload(sg_ctx* ctx, std::vector<void*>& pool, T** out, const std::vector<T>& host) {
+    int rc = dev_alloc(ctx, pool, out, host.size());
+    if (rc) return rc;
+    SG_HIP(hipMemcpy(*out, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SG_OK;
+}
+// an on-demand workspace buffer of at least `need` elements, grown before a loop: the old one is released once the stream
+// has drained (nothing enqueued still uses it), not left in the pool until sg_destroy
+template <typename T>
+int dev_grow(sg_ctx* ctx, std::vector<void*>& pool, T** buf, size_t* cap, size_t need, hipStream_t s) {
+    if (*buf && *cap >= need) return SG_OK;
+    if (*buf) {
+        SG_HIP(hipStreamSynchronize(s));
+        (void)hipFree(*buf);
+        pool.erase(std::remove(pool.begin(), pool.end(), static_cast<void*>(*buf)), pool.end());
+        *buf = nullptr;
+        *cap = 0;
+    }
+    int rc = dev_alloc(ctx, pool, buf, need);
+    if (rc) return rc;
+    *cap = need;
+    return SG_OK;
+}
+
+// ---------------------------------------------------------------- one pass of a device-resident PGD loop
+// Step `it` of a loop runs its `reps` EOT repeats as passes of at most G repeats (rows = repeat * B + utterance), the last
+// step (it == max_iter) one forward repeat.  What the pass that starts at repeat g0 is: a pure function of its arguments (no HIP
+// call, no context), shared by the x-vector and the AudioNet loop.
+constexpr uint64_t kStepKey = 0x9E3779B97F4A7C15ull;  // key stride from one PGD step to the next
+constexpr uint64_t kRepKey = 0xC2B2AE3D27D4EB4Full;   // ... from one EOT repeat to the next (the kernels' stride for the rows of a pass)
+struct LoopPass {
+    bool last;          // the final pass: the caller's outputs, no gradient
+    int nrep;           // repeats of this step
+    int Gi;             // repeats of this pass
+    int rows;           // Gi * B
+    bool final_group;   // the step's last pass takes the step; earlier ones carry their sum
+    uint64_t pass_key;  // added to every seed of the pass (dither, AT, FeCo)
+    // Per-step records (attack/FGSM.py:50-58: loss averaged, decision voted over ALL repeats of the step): where the head
+    // writes its rows.  DIRECT: one repeat, row `it` of the caller's trace.  PASS: several repeats in one pass, the pass
+    // scratch, reduced right after the head.  GROUPED: more repeats than a pass holds, the grouped rows at rec_offset in repeat
+    // order, reduced after the last group.
+    enum Records { NONE, DIRECT, PASS, GROUPED } rec;
+    size_t rec_offset;
+    bool reduce;        // the reduction over the step's nrep repeats follows this pass
+};
+inline LoopPass loop_pass(int it, int max_iter, int g0, int G, int reps, int B, bool want_rec) {
+    LoopPass p;
+    p.last = it == max_iter;
+    p.nrep = p.last ? 1 : reps;
+    p.Gi = std::min(G, p.nrep - g0);
+    p.rows = B * p.Gi;
+    p.final_group = g0 + p.Gi >= p.nrep;
+    p.pass_key = (uint64_t)it * kStepKey + (uint64_t)g0 * kRepKey;
+    p.rec = !want_rec ? LoopPass::NONE : p.nrep == 1 ? LoopPass::DIRECT : p.nrep > G ? LoopPass::GROUPED : LoopPass::PASS;
+    p.rec_offset = (size_t)g0 * B;
+    p.reduce = p.rec == LoopPass::PASS || (p.rec == LoopPass::GROUPED && p.final_group);
+    return p;
+}
+// the head's record pointer of the pass: trace_row = row `it` of the caller's trace (null: that record is not wanted)
+template <typename T>
+T* loop_record_rows(const LoopPass& p, T* trace_row, T* pass_scratch, T* grouped) {
+    switch (p.rec) {
+        case LoopPass::DIRECT: return trace_row;
+        case LoopPass::PASS: return pass_scratch;
+        case LoopPass::GROUPED: return grouped + p.rec_offset;
+        default: return nullptr;
+    }
+}
+// What every loop entry point refuses about its arguments, after its own NULL test (any_null) and with its own refusal about
+// B / T (shape: the text, or null) in their place between the shared ones.
+inline int loop_check_args(sg_ctx* ctx, bool any_null, const char* shape, const sg_pgd_params* p) {
+    if (any_null) return fail(ctx, SG_ERR_ARG, "NULL argument");
+    if (shape) return fail(ctx, SG_ERR_ARG, "%s", shape);
+    if (p->max_iter < 0) return fail(ctx, SG_ERR_ARG, "max_iter must be >= 0");
+    if (p->loss.loss == SG_LOSS_LINEAR && !p->loss.coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
+    return SG_OK;
+}
+// ... and, where the entry point takes EOT repeats: eot_size, or SG_ERR_ARG
+inline int loop_eot_size(sg_ctx* ctx, const sg_pgd_params* p, int* eot_size) {
+    const int eot_bs = p->eot_batch_size > 0 ? p->eot_batch_size : 1;
+    *eot_size = p->eot_size > 0 ? p->eot_size : 1;
+    if (*eot_size % eot_bs) return fail(ctx, SG_ERR_ARG, "EOT size should be divisible by EOT batch size");
+    return SG_OK;
 }
 
 

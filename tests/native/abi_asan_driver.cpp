@@ -14,6 +14,11 @@
 // AudioNet entry points (sg_api_audionet.hip) and prints one line per launch of ANY kernel, in order, plus the planned
 // fields of AnFusedArgs for the fused CNN kernels -- the four launch forms of the CNN give the same bits too.  Recorded in
 // tests/native/an_launch_sequence.expected (tests/test_an_launch_sequence.py).
+//
+// `abi_asan_driver --loop-sequence` is the fourth: the same lines for the device-resident PGD loops -- sg_xv_pgd_run with and
+// without dither, EOT repeats as one pass, as full groups and with a tail group, sg_xv_pgd_run_defended and
+// sg_an_pgd_run_defended over identity, per-row, randomised and FeCo chains.  Every launch form of a loop gives the same bits
+// too.  Recorded in tests/native/loop_launch_sequence.expected (tests/test_loop_launch_sequence.py).
 #include <cxxabi.h>
 
 #include <algorithm>
@@ -340,9 +345,123 @@ static int an_sequence(bool configure) {
     return 0;
 }
 
+// ---- the device loops' launch sequence ----------------------------------------------------------------------------
+static sg_wav_stage td(int kind, float param) {
+    sg_wav_stage st{};
+    st.tag = SG_WAV_STAGE_DEFENSE;
+    st.u.defense.kind = kind;
+    st.u.defense.param = param;
+    st.u.defense.seed = 17;
+    return st;
+}
+
+// SG_EOT_MAX_ROWS is read at every call (behind SG_TUNE=1): 0 = unset
+static void eot_max_rows(int rows) {
+    if (rows > 0) setenv("SG_EOT_MAX_ROWS", std::to_string(rows).c_str(), 1);
+    else unsetenv("SG_EOT_MAX_ROWS");
+}
+
+static int loop_sequence() {
+    setenv("SG_TUNE", "1", 1);
+    unsetenv("SG_EOT_MAX_ROWS");
+    hipdouble_set_launch_hook(record_an_launch);
+    const int K = 2;
+    const double sos[2][6] = {{0.2, 0.4, 0.2, 1.0, -0.3, 0.1}, {1.0, 2.0, 1.0, 1.0, -0.2, 0.3}};
+    sg_wav_stage lpf{};
+    lpf.tag = SG_WAV_STAGE_FILTER;
+    lpf.u.filter.n_sections = 2; lpf.u.filter.sos = &sos[0][0]; lpf.u.filter.clip_mode = SG_FD_CLIP_RANGE; lpf.u.filter.bits = 16;
+    const sg_wav_stage qt = td(SG_TD_QT, 512.f), bdr = td(SG_TD_QT, 256.f) /* BDR to 8 of 16 bits */, ms = td(SG_TD_MS, 3.f), at = td(SG_TD_AT, 25.f);
+    const sg_wav_stage qt_bdr[2] = {qt, bdr}, qt_ms_lpf[3] = {qt, ms, lpf}, lpf_qt[2] = {lpf, qt};
+    const sg_wav_stage eight[SG_WAV_CHAIN_MAX] = {td(SG_TD_MS, 5.f), td(SG_TD_AS, 31.f), td(SG_TD_QT, 256.f), lpf, at, td(SG_TD_QT, 128.f), ms, lpf};
+    sg_pgd_params base{};
+    base.step_size = 4e-4f; base.max_iter = K; base.grad_sign = 1; base.eot_size = 1; base.eot_batch_size = 1;
+    {   // ---- x-vector, the shape of defended_asan_driver.cpp
+        const int B = 3, T = 5043, S = 4;
+        sg_ctx* ctx = nullptr;
+        XvModel xv(24, S);
+        if (sg_create(0, &ctx) != SG_OK || sg_xv_load(ctx, &xv.desc) != SG_OK) return 1;
+        std::vector<float> x = rnd((size_t)B * T, 200, 0.3f), lower = x, upper = x, scores((size_t)B * S), loss(B), ltr((size_t)(K + 1) * B);
+        std::vector<int64_t> y(B, 1), dec(B), dtr((size_t)(K + 1) * B);
+        std::vector<uint8_t> succ(B);
+        const std::string at_shape = " B=" + std::to_string(B) + " T=" + std::to_string(T);
+        // dither: 0 = none, 1 = dither 1 with eot_size 4; eot: eot_size without dither (AT's repeats)
+        auto params = [&](bool dither, int eot, int max_iter) {
+            sg_pgd_params pp = base;
+            pp.max_iter = max_iter;
+            pp.eot_size = dither ? 4 : eot;
+            if (dither) { pp.dither.dither = 1.0f; pp.dither.seed = 99; pp.dither.index_base = 5; }
+            return pp;
+        };
+        auto run = [&](const std::string& label, const sg_pgd_params& pp, bool trace, int max_rows) {
+            eot_max_rows(max_rows);
+            AN_CASE("xv_pgd_run" + at_shape + " " + label,
+                    sg_xv_pgd_run(ctx, x.data(), y.data(), lower.data(), upper.data(), B, T, &pp, succ.data(), dec.data(), scores.data(), loss.data(),
+                                  trace ? ltr.data() : nullptr, trace ? dtr.data() : nullptr, nullptr));
+        };
+        auto run_def = [&](const std::string& label, const sg_wav_stage* chain, int n, const sg_pgd_params& pp, int max_rows) {
+            eot_max_rows(max_rows);
+            AN_CASE("xv_pgd_run_defended" + at_shape + " " + label,
+                    sg_xv_pgd_run_defended(ctx, x.data(), y.data(), lower.data(), upper.data(), B, T, &pp, chain, n, succ.data(), dec.data(),
+                                           scores.data(), loss.data(), ltr.data(), dtr.data(), nullptr));
+        };
+        run("no dither trace", params(false, 1, K), true, 0);
+        run("no dither", params(false, 1, K), false, 0);
+        run("dither eot=4 G=4", params(true, 4, K), true, 0);
+        run("dither eot=4 max_rows=6 G=2", params(true, 4, K), true, 6);
+        run("dither eot=4 max_rows=9 G=3 tail", params(true, 4, K), true, 9);
+        run("max_iter=0", params(false, 1, 0), true, 0);
+        run_def("QT", &qt, 1, params(false, 1, K), 0);
+        run_def("QT,BDR", qt_bdr, 2, params(false, 1, K), 0);
+        run_def("QT,BDR dither eot=4", qt_bdr, 2, params(true, 4, K), 0);
+        run_def("MS", &ms, 1, params(false, 1, K), 0);
+        run_def("LPF clip=range", &lpf, 1, params(false, 1, K), 0);
+        run_def("QT,MS,LPF dither eot=4", qt_ms_lpf, 3, params(true, 4, K), 0);
+        run_def("AT eot=4", &at, 1, params(false, 4, K), 0);
+        run_def("AT eot=4 max_rows=9", &at, 1, params(false, 4, K), 9);
+        run_def("8 stages eot=4", eight, SG_WAV_CHAIN_MAX, params(false, 4, K), 0);
+        run_def("MS max_iter=0", &ms, 1, params(false, 1, 0), 0);
+        eot_max_rows(0);
+        sg_destroy(ctx);
+    }
+    {   // ---- AudioNet: 64 log-mel frames, so that FeCo's k = 32 passes the stack
+        const int B = 4, T = 10081, Sa = 5;
+        sg_ctx* ctx = nullptr;
+        AnModel an(Sa);
+        if (sg_create(0, &ctx) != SG_OK || sg_an_load(ctx, &an.desc) != SG_OK) return 1;
+        AnBuffers b(B, T, Sa, K);
+        const std::string at_shape = " B=" + std::to_string(B) + " T=" + std::to_string(T);
+        auto run = [&](const std::string& label, const sg_wav_stage* chain, int n, const sg_feco_params* f, int eot, int max_iter, bool trace, int max_rows) {
+            sg_pgd_params pp = base;
+            pp.max_iter = max_iter;
+            pp.eot_size = eot;
+            eot_max_rows(max_rows);
+            AN_CASE("an_pgd_run_defended" + at_shape + " " + label,
+                    sg_an_pgd_run_defended(ctx, b.x.data(), b.y.data(), b.x.data(), b.x.data(), B, T, &pp, chain, n, f, b.succ.data(), b.dec.data(),
+                                           b.sc.data(), b.loss.data(), trace ? b.ltr.data() : nullptr, trace ? b.dtr.data() : nullptr, nullptr));
+        };
+        sg_feco_params even{}, random{};
+        even.k = 32; even.max_iter = 3; even.random_init = 0; even.seed = 5;
+        random = even;
+        random.random_init = 1;
+        run("QT", &qt, 1, nullptr, 1, K, true, 0);
+        run("MS", &ms, 1, nullptr, 1, K, true, 0);
+        run("LPF,QT", lpf_qt, 2, nullptr, 1, K, true, 0);
+        run("AT eot=4", &at, 1, nullptr, 4, K, true, 0);
+        run("AT eot=4 max_rows=12 G=3 tail", &at, 1, nullptr, 4, K, true, 12);
+        run("QT feco k=32 even", &qt, 1, &even, 1, K, true, 0);
+        run("MS feco k=32 random eot=2 trace", &ms, 1, &random, 2, K, true, 0);
+        run("MS feco k=32 random eot=2", &ms, 1, &random, 2, K, false, 0);
+        run("MS max_iter=0", &ms, 1, nullptr, 1, 0, true, 0);
+        eot_max_rows(0);
+        sg_destroy(ctx);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && std::string(argv[1]) == "--launch-table") return launch_table(argv[2]);
     if (argc == 3 && std::string(argv[1]) == "--an-sequence") return an_sequence(std::string(argv[2]) == "all");
+    if (argc == 2 && std::string(argv[1]) == "--loop-sequence") return loop_sequence();
     setenv("SG_TUNE", "1", 1);  // the knobs this walk sets (SG_EOT_MAX_ROWS, SG_AN_SLICES, SG_AN_FUSED) count only behind it
     // ---- no context ------------------------------------------------------------------------------------------
     EXPECT(sg_version() == 100);
