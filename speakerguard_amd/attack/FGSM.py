@@ -5,9 +5,10 @@ and nothing between attack and model needs Python (no defense wrapper), the whol
 over the front-end's random dither included -- max_iter x (forward, hand-coded backward, sign step,
 projection) + the final forward-only pass -- is ONE C-ABI call (``model.pgd_run``).  A wrapper that
 carries only native waveform-level defenses in sequential order runs the same way, the chain inside
-the loop (``model.pgd_run_defended``), and so does such a chain in front of one FeCoDefense on AudioNet
-(``model.pgd_run_defended_feco``).  Otherwise the same loop runs step by step over ``model.loss_grad`` /
-``model.pgd_update``.
+the loop (``model.pgd_run_defended``), and so do one FeCoDefense on AudioNet (``model.pgd_run_feco``) and
+such a chain in front of it (``model.pgd_run_defended_feco``).  ``_device_route`` is the one place that
+decides this, once per batch, from one reading of the model; ``attack_batch`` makes the one call it
+names.  Otherwise the same loop runs step by step over ``model.loss_grad`` / ``model.pgd_update``.
 """
 import numpy as np
 import torch
@@ -47,102 +48,59 @@ class FGSM(Attack):
                                                  task=self.task, threshold=self.threshold, clip_max=False)
         self.EOT_wrapper = EOT(self.model, self.loss, self.EOT_size, self.EOT_batch_size, True)
 
-    # ---- fused device loop -----------------------------------------------------------------
-    def _fused_feco(self, n_audios):
-        """The FeCoDefense of ``defended_model(base, [(1, FeCoDefense)])`` when the base model runs the defended loop on
-        the device (BASELINE.json configs[3]: audionet_csine.pgd_run_feco), else None."""
-        m = self.model
-        defense = getattr(m, 'defense', None)
-        base = getattr(m, 'base_model', None)
-        if not self.fuse_defended or defense is None or base is None or not hasattr(base, 'pgd_run_feco') or n_audios < 2:
-            return None  # one utterance: the reference drops empty clusters (variable frame count) -> host path
-        if getattr(m, 'order', None) != 'sequential' or len(defense) != 1:
-            return None
-        flag, d = defense[0]
-        from ..defense.feature_level import FeCoDefense
-        return d if flag == 1 and isinstance(d, FeCoDefense) else None
-
-    def _fused_input_chain(self):
-        """The defense objects of ``defended_model(base, [(0, d1), (0, d2), ...])`` in chain order when the base model runs
-        that loop on the device (xv_plda / audionet_csine ``pgd_run_defended``): sequential order, every defense at the waveform level and a
-        native waveform defense object (defense.time_domain / defense.frequency_domain) as it stands -- no BPDA wrapper,
-        no Python callable, no explicit noise.  Else None: the step loop below."""
-        m = self.model
-        defense = getattr(m, 'defense', None)
-        base = getattr(m, 'base_model', None)
-        if not self.fuse_input_defenses or not defense or base is None or not hasattr(base, 'pgd_run_defended'):
-            return None
-        if getattr(m, 'order', None) != 'sequential':
-            return None
-        from ..defense.time_domain import _WavDefense
-        if not all(flag == 0 and isinstance(d, _WavDefense) for flag, d in defense):
-            return None
-        chain = m.flag2defense.get(0, [])  # what process_sequential applies, in its order
-        if len(chain) != len(defense) or not 1 <= len(chain) <= 8:
-            return None
-        # A randomised stage (AT) draws DIFFERENT noise on the two routes for the same seed: the device loop keys a pass by
-        # (step, repeat), the step loop by the defense's call number.  An attack's result must not change under its user, so
-        # such a chain keeps the step loop unless the caller asks for the device loop's schedule.
-        if any(getattr(d, 'randomised', False) for d in chain) and not self.fuse_randomised_input_defenses:
-            return None
-        return chain
-
-    def _fused_chain_feco(self, n_audios):
-        """(chain, feco) of ``defended_model(base, [(0, d1), ..., (1, FeCoDefense)])`` when the base model runs that loop on the
-        device (audionet_csine.pgd_run_defended_feco): sequential order, every level-0 defense a native waveform defense object
-        as it stands and not randomised (the clusterings' gradients are summed behind ONE chain pass), exactly one level-1
-        defense and that a FeCoDefense, nothing at any other level, at least two utterances (``_fused_feco``), both fuse flags
-        on.  Else None: the step loop below."""
-        m = self.model
-        defense = getattr(m, 'defense', None)
-        base = getattr(m, 'base_model', None)
-        if not (self.fuse_defended and self.fuse_input_defenses) or not defense or base is None or n_audios < 2:
-            return None
-        if not hasattr(base, 'pgd_run_defended_feco') or getattr(m, 'order', None) != 'sequential':
-            return None
-        from ..defense.feature_level import FeCoDefense
-        from ..defense.time_domain import _WavDefense
-        chain = [d for flag, d in defense if flag == 0]
-        rest = [(flag, d) for flag, d in defense if flag != 0]
-        if len(rest) != 1 or rest[0][0] != 1 or not isinstance(rest[0][1], FeCoDefense):
-            return None
-        if not 1 <= len(chain) <= 8 or chain != m.flag2defense.get(0, []) or m.flag2defense.get(1, []) != [rest[0][1]]:
-            return None
-        if not all(isinstance(d, _WavDefense) and not getattr(d, 'randomised', False) for d in chain):
-            return None
-        return chain, rest[0][1]
-
-    def _can_fuse(self):
-        m = self.model
-        if getattr(m, 'defense', None) is not None:
-            return False
-        base = getattr(m, 'base_model', m)
-        # EOT repeats of a deterministic model are identical (one pass stands for all of them); with random dither
-        # the engine runs the repeats itself and sums their gradients on the device
-        return hasattr(base, 'pgd_run')
-
+    # ---- device-resident loop ---------------------------------------------------------------
     fuse_defended = True  # False: PGD against a FeCo-defended model runs the host-chained loop (tests compare the two)
     fuse_input_defenses = True  # False: ... against native input-level defenses likewise (tests, tools/defended_loop_time.py)
     fuse_randomised_input_defenses = False  # True: chains holding AT run on the device too, with the device loop's noise keys
 
-    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, feco=None, chain=None):
+    def _device_route(self, n_audios):
+        """Which device-resident loop of the base model runs ``attack_batch`` for a batch of `n_audios`: None for the step loop
+        below, else ``(method name, extra arguments)`` -- ``('pgd_run', ())`` for a model without defenses, ``('pgd_run_feco',
+        (feco,))``, ``('pgd_run_defended', (chain,))`` or ``('pgd_run_defended_feco', (chain, feco))`` for a ``defended_model`` in
+        sequential order whose defenses are
+
+          * chain: 1 .. 8 native waveform defense objects (defense.time_domain / defense.frequency_domain) as they stand -- no
+            BPDA wrapper, no Python callable -- and exactly what the model applies at level 0 (``flag2defense[0]``);
+          * feco: the one entry that is not at level 0, a FeCoDefense at level 1; needs ``fuse_defended`` and two utterances
+            (one: the reference drops empty clusters, the frame count varies -> host path).
+
+        A randomised stage (AT) draws DIFFERENT noise on the two routes for the same seed: the device loop keys a pass by
+        (step, repeat), the step loop by the defense's call number.  An attack's result must not change under its user, so such
+        a chain keeps the step loop unless ``fuse_randomised_input_defenses`` asks for the device loop's schedule, and always
+        in front of FeCo (the clusterings' gradients are summed behind ONE chain pass).  The base model says what it offers by
+        having the method."""
+        m = self.model
+        defense = getattr(m, 'defense', None)
+        base = getattr(m, 'base_model', m if defense is None else None)
+        route = None
+        if defense is None:
+            # EOT repeats of a deterministic model are identical (one pass stands for all of them); with random dither
+            # the engine runs the repeats itself and sums their gradients on the device
+            route = 'pgd_run', ()
+        elif getattr(m, 'order', None) == 'sequential':
+            from ..defense.feature_level import FeCoDefense
+            from ..defense.time_domain import _WavDefense
+            chain = [d for flag, d in defense if flag == 0]
+            rest = [(flag, d) for flag, d in defense if flag != 0]
+            chain_ok = (self.fuse_input_defenses and 1 <= len(chain) <= 8 and all(isinstance(d, _WavDefense) for d in chain)
+                        and chain == m.flag2defense.get(0, []))  # (what process_sequential applies, in its order)
+            randomised = any(getattr(d, 'randomised', False) for d in chain)
+            if not rest:
+                if chain_ok and (self.fuse_randomised_input_defenses or not randomised):
+                    route = 'pgd_run_defended', (chain,)
+            elif len(rest) == 1 and rest[0][0] == 1 and isinstance(rest[0][1], FeCoDefense) and self.fuse_defended and n_audios >= 2:
+                feco = rest[0][1]
+                if not chain:
+                    route = 'pgd_run_feco', (feco,)
+                elif chain_ok and not randomised and m.flag2defense.get(1, []) == [feco]:
+                    route = 'pgd_run_defended_feco', (chain, feco)
+        return route if route is not None and hasattr(base, route[0]) else None
+
+    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, name, extra):
         base = getattr(self.model, 'base_model', self.model)
-        if chain is not None and feco is not None:
-            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_defended_feco(
-                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, chain, feco,
-                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
-        elif chain is not None:
-            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_defended(
-                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, chain,
-                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
-        elif feco is not None:
-            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run_feco(
-                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, feco,
-                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
-        else:
-            x_adv, success, dec, scores, loss, ltr, dtr = base.pgd_run(
-                x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign,
-                self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
+        x_adv, success, dec, scores, loss, ltr, dtr = getattr(base, name)(
+            x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, *extra,
+            self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
         if self.verbose:
             ltr, dtr = ltr.cpu().numpy(), dtr.cpu().numpy()
             target = y_batch.detach().cpu().numpy()
@@ -152,17 +110,9 @@ class FGSM(Attack):
 
     # ---- step-by-step loop (FGSM.py:38-70) ---------------------------------------------------
     def attack_batch(self, x_batch, y_batch, lower, upper, batch_id):
-        if self._can_fuse():
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id)
-        feco = self._fused_feco(x_batch.shape[0])
-        if feco is not None:
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, feco=feco)
-        chain = self._fused_input_chain()
-        if chain is not None:
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, chain=chain)
-        both = self._fused_chain_feco(x_batch.shape[0])
-        if both is not None:
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, feco=both[1], chain=both[0])
+        route = self._device_route(x_batch.shape[0])
+        if route is not None:
+            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, *route)
         x_batch = x_batch.clone()
         lower = lower.expand_as(x_batch).contiguous()
         upper = upper.expand_as(x_batch).contiguous()

@@ -24,6 +24,7 @@ import torch
 
 from .. import _native as N
 from ..metric.metric import _context
+from ..model._engine_ops import REP_KEY_STRIDE
 
 
 class FeCoDefense:
@@ -53,7 +54,7 @@ class FeCoDefense:
         """feat (B,F,D) -> (compressed (B,k,D) [or (1,k',D) with empty clusters dropped when B == 1], saved).
         `seed`: explicit generator key for this call of the randomised defense (tests replay the fused loop's keys).
         `row_keys` = (index_base, row_base, rep_rows) as in sg_dither (speakerguard_hip.h): which global utterance and
-        which EOT repeat every row of `feat` is -- repeat r draws from key + r * 0xC2B2AE3D27D4EB4F, like repeat r of the
+        which EOT repeat every row of `feat` is -- repeat r draws from key + r * REP_KEY_STRIDE, like repeat r of the
         device loop (sg_an_pgd_run_feco); default: row b is utterance ``self.index_base + b``.
         `ids` (B,F) int32: cluster ids from elsewhere -- only the reference's step after the clustering runs
         (feature_level.py:204-216; tests/golden/feco_ref.npz pins it against the reference's own code)."""
@@ -86,7 +87,7 @@ class FeCoDefense:
                 nb = min(B - b0, rep_rows - u) if rep_rows > 0 else B
                 sl = slice(b0, b0 + nb)
                 ctx.call("sg_feco_kmeans_compress", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, int(self.init == 'random'),
-                         C.c_uint64((key + rep * 0xC2B2AE3D27D4EB4F) & 0xFFFFFFFFFFFFFFFF), int(index_base + u), 1,
+                         C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF), int(index_base + u), 1,
                          N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
                 b0 += nb
         force = B > 1  # :33 force=feat.shape[0] > 1
@@ -177,7 +178,7 @@ class WarpedFeCoDefense:
                         rep = g // rep_rows if rep_rows > 0 else 0
                         u = g - rep * rep_rows
                         nb = min(B - b0, rep_rows - u) if rep_rows > 0 else B
-                        chunks.append((b0, nb, 1, (key + rep * 0xC2B2AE3D27D4EB4F) & 0xFFFFFFFFFFFFFFFF, index_base + u, 0))
+                        chunks.append((b0, nb, 1, (key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF, index_base + u, 0))
                         b0 += nb
             else:
                 chunks = [(0, B, 0, 0, 0, 0)]

@@ -22,9 +22,10 @@ import torch
 
 from .. import _native as N
 from ..metric.metric import _context
+from ..model._engine_ops import REP_KEY_STRIDE
 
 _MASK64 = 0xFFFFFFFFFFFFFFFF
-_REPEAT_STRIDE = 0xC2B2AE3D27D4EB4F  # key offset of EOT repeat r (sg_dither)
+_REPEAT_STRIDE = REP_KEY_STRIDE  # key offset of EOT repeat r (sg_dither)
 
 
 class _WavDefense:

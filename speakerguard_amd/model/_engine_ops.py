@@ -1,14 +1,20 @@
-"""Native attack-state updates shared by every engine-backed model (C-ABI: sg_pgd_update, sg_cw2_step,
-sg_nes_queries, sg_nes_grad, sg_fakebob_step).  The attack classes call these through the model so
-that the only implementation in the product is the HIP one (tests substitute a CPU double)."""
+"""What every engine-backed model shares: the native attack-state updates (C-ABI: sg_pgd_update, sg_cw2_step,
+sg_nes_queries, sg_nes_grad, sg_fakebob_step), which the attack classes call through the model so
+that the only implementation in the product is the HIP one (tests substitute a CPU double), the noise
+bookkeeping, and the ONE marshalling path from a model's ``pgd_run*`` methods to its device-resident PGD
+loops (``_pgd_loop``)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from .. import _native as N
 
 
 _MASK64 = (1 << 64) - 1
+# the key strides of the device-resident PGD loops (kStepKey / kRepKey of csrc/sg_internal.h)
+STEP_KEY_STRIDE = 0x9E3779B97F4A7C15  # from one PGD step to the next
+REP_KEY_STRIDE = 0xC2B2AE3D27D4EB4F   # from one EOT repeat to the next (the kernels' stride for the rows of a pass, sg_dither)
 
 
 def mix64(*vals):
@@ -20,8 +26,21 @@ def mix64(*vals):
     return h
 
 
+def fused_pass_seed(base_seed, it, r=0):
+    """Generator key of step `it`, EOT repeat `r` of a device-resident PGD loop whose call drew `base_seed` (the dither's,
+    a randomised stage's or FeCo's: ``last_fused_seed`` / ``last_fused_defense_seeds``)."""
+    return (int(base_seed) + it * STEP_KEY_STRIDE + r * REP_KEY_STRIDE) & _MASK64
+
+
+def _f32(a):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+
+
 class EngineOps:
-    """Mixin: expects ``self.ctx`` (N.Context) and ``self.device``.
+    """Mixin: ``_open`` sets ``self.ctx`` (N.Context) and ``self.device``; the model names its feature width
+    (``_feat_width``) and its debug-activation entry (``_debug_activation``) and has ``num_spks`` / ``allowed_flags``.
 
     Noise bookkeeping (dither of the MFCC front-end, NES queries, FeCo's random start): the reference draws from the
     process-global torch RNG, which makes an utterance's noise depend on everything that ran before it.  Here every
@@ -87,6 +106,133 @@ class EngineOps:
 
     def _stream(self):
         return N.current_stream_ptr(self.device)
+
+    def _open(self, device):
+        """Bind the model to the GPU `device` and create its engine context.  Returns ``hp``: host array -> pointer to its
+        float32 copy for a weight struct; the copies live as long as ``hp`` (they must outlive the load call)."""
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise N.NativeError("%s runs on the HIP engine only; device must be a GPU (got %s)" % (type(self).__name__, device))
+        self.device = torch.device("cuda", self.device.index if self.device.index is not None else 0)
+        self.ctx = N.Context(self.device.index)
+        keep = []
+
+        def hp(a):
+            a = _f32(a)
+            keep.append(a)
+            return a.ctypes.data_as(C.c_void_p)
+        return hp
+
+    def _prep(self, x, flag):
+        assert flag in self.allowed_flags
+        x = x.to(self.device, torch.float32).contiguous()
+        if flag == 0:
+            assert x.dim() == 3 and x.shape[1] == 1, "wav input must be (B, 1, T)"
+            return x, x.shape[0], x.shape[2]
+        assert x.dim() == 3 and x.shape[2] == self._feat_width, "feature input must be (B, F, %d)" % self._feat_width
+        return x, x.shape[0], x.shape[1]
+
+    def activation_shape(self, layer):
+        """(rows, channels) per utterance of layer `layer`'s activation in the last pass"""
+        rows, ch = C.c_int32(), C.c_int32()
+        self.ctx.call(self._debug_activation, layer, None, 0, C.byref(rows), C.byref(ch), self._stream())
+        return rows.value, ch.value
+
+    def read_activation(self, layer, B):
+        rows, ch = self.activation_shape(layer)
+        out = torch.empty(B, rows, ch, device=self.device, dtype=torch.float32)
+        self.ctx.call(self._debug_activation, layer, N._ptr(out), out.numel(), None, None, self._stream())
+        return out
+
+    def _loss_grad_args(self, x, y, loss_spec, flag, want_grad):
+        """what every ``loss_grad`` starts with -> (x, y, B, T or F, (decisions, scores, loss, grad or None))"""
+        x, B, TF = self._prep(x, flag)
+        self.check_labels(y, loss_spec)
+        y = y.to(self.device, torch.int64).contiguous()
+        dec = torch.empty(B, device=self.device, dtype=torch.int64)
+        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
+        loss = torch.empty(B, device=self.device, dtype=torch.float32)
+        grad = torch.empty_like(x) if want_grad else None
+        if hasattr(loss_spec, 'check'):
+            loss_spec.check(B, self.num_spks)
+        return x, y, B, TF, (dec, scores, loss, grad)
+
+    # ---- the device-resident PGD loops ------------------------------------------------------------------------------
+    fused_pass_seed = staticmethod(fused_pass_seed)
+
+    def _pgd_dither(self, p):
+        """hook: the front-end dither of one device loop call, into ``p.dither`` (none: the block stays zero)"""
+
+    def _pgd_args(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace):
+        """the tensors and the parameter block the device loops share -> (x_adv, y, lower, upper, B, T, params, outputs)"""
+        x, B, T = self._prep(x, 0)
+        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
+        x_adv = x.clone()
+        y = y.to(self.device, torch.int64).contiguous()
+        lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()
+        upper = upper.to(self.device, torch.float32).expand_as(x).contiguous()
+        if hasattr(loss_spec, "check"):
+            loss_spec.check(B, self.num_spks)  # ScoreVJP: one (B, S) table, shared by the EOT repeats of an utterance
+        p = N.PgdParams()
+        p.loss = loss_spec.native()
+        p.step_size, p.max_iter, p.grad_sign = float(step_size), int(max_iter), int(grad_sign)
+        p.eot_size, p.eot_batch_size = int(eot_size), int(eot_batch_size)
+        self._pgd_dither(p)
+        success = torch.empty(B, device=self.device, dtype=torch.uint8)
+        dec = torch.empty(B, device=self.device, dtype=torch.int64)
+        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
+        loss = torch.empty(B, device=self.device, dtype=torch.float32)
+        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
+        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
+        return x_adv, y, lower, upper, B, T, p, (success, dec, scores, loss, ltr, dtr)
+
+    @staticmethod
+    def _checked_chain(chain, randomised_ok):
+        """the host's refusals of a chain, asked before anything is drawn or cloned -> the chain as a list"""
+        chain = list(chain)
+        if not randomised_ok and any(getattr(d, 'randomised', False) for d in chain):
+            raise ValueError("a randomised input-level defense in front of FeCo keeps the step loop")
+        if not 1 <= len(chain) <= N.SG_WAV_CHAIN_MAX:
+            raise ValueError("a chain of 1 .. %d input-level defenses runs on the device, got %d" % (N.SG_WAV_CHAIN_MAX, len(chain)))
+        return chain
+
+    def _wav_stages(self, chain):
+        """the (checked) chain as a sg_wav_stage array.  Every randomised stage (AT) gets one base key, drawn in chain order
+        like ``defended_model._fwd`` draws them; ``last_fused_defense_seeds`` keeps them (None for a deterministic stage)."""
+        stages = (N.WavStage * len(chain))()
+        keep, keys = [], []
+        index_base, row_base, _ = self.row_keys()
+        for i, d in enumerate(chain):
+            st = d.stage()
+            keep.append(st)  # (a filter's stage keeps its sections alive)
+            key = None
+            if getattr(d, 'randomised', False):
+                key = self.defense_seed(d.seed, d.seed_tag)
+                st.u.defense.seed, st.u.defense.index_base, st.u.defense.row_base = key, index_base, row_base
+            keys.append(key)
+            stages[i] = st
+        self.last_fused_defense_seeds = keys
+        return stages, keep
+
+    def _pgd_loop(self, entry, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace,
+                  chain=None, feco=None, feco_slot=False):
+        """One device-resident PGD loop call: C entry `entry` over the common arguments, then the stage array and its length
+        if a `chain` is given, then the FeCo block if `feco` is given (`feco_slot`: the entry takes that pointer anyway,
+        NULL without a defense), then the outputs and the stream.  Keys are drawn in this order: the front-end's dither
+        (``_pgd_dither``), the chain's randomised stages in chain order, FeCo's (``_feco_params``)."""
+        if chain is not None:
+            chain = self._checked_chain(chain, feco is None)
+        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
+                                                               eot_size, eot_batch_size, trace)
+        extras = []
+        if chain is not None:
+            stages, keep = self._wav_stages(chain)
+            extras += [stages, len(stages)]
+        if feco is not None or feco_slot:
+            extras.append(None if feco is None else C.byref(self._feco_params(feco, T)))
+        self.ctx.call(entry, N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p), *extras,
+                      *[N._ptr(t) for t in outs], self._stream())
+        return (x_adv,) + outs
 
     def check_health(self):
         """Raise NativeError if a kernel of an earlier launch flagged its own result as invalid (sg_health: a

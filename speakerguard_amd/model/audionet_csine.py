@@ -11,21 +11,17 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from ._engine_ops import EngineOps
+from ._engine_ops import EngineOps, _f32
 
 BITS = 16
 _CONVS = ("conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv8")
 
 
-def _f32(a):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
-
-
 class audionet_csine(EngineOps):
     allowed_flags = [0, 1]  # 0: wav; 1: raw (log-mel) feat -- audionet_csine.py:127-129
     range_type = "scale"
+    _feat_width = 32
+    _debug_activation = "sg_an_debug_activation"
 
     def __init__(self, extractor_file=None, num_class=None, label_encoder=None, device="cuda:0"):
         if extractor_file is None:
@@ -42,18 +38,7 @@ class audionet_csine(EngineOps):
         return self
 
     def _init(self, sd, label_encoder, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise N.NativeError("audionet_csine runs on the HIP engine only; device must be a GPU (got %s)" % device)
-        idx = self.device.index if self.device.index is not None else 0
-        self.device = torch.device("cuda", idx)
-        keep = []
-
-        def hp(a):
-            a = _f32(a)
-            keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
+        hp = self._open(device)  # host arrays must outlive sg_an_load
         w = N.AnWeights()
         w.conv1_weight, w.conv1_bias = hp(sd["conv1.0.weight"]), hp(sd["conv1.0.bias"])
         for i, k in enumerate(("weight", "bias", "running_mean", "running_var")):
@@ -65,7 +50,6 @@ class audionet_csine(EngineOps):
         w.fc_weight, w.fc_bias = hp(sd["fc.weight"]), hp(sd["fc.bias"])
         self.num_spks = int(_f32(sd["fc.bias"]).shape[0])
         w.num_class, w.bn_eps = self.num_spks, 1e-5
-        self.ctx = N.Context(idx)
         self.ctx.call("sg_an_load", C.byref(w))
         self.threshold = -np.inf  # CSI-NE: never rejects (audionet_csine.py:126)
         if label_encoder is not None:  # id <-> label table, audionet_csine.py:36-46
@@ -88,15 +72,6 @@ class audionet_csine(EngineOps):
         cache = -1 if spectrum_cache is None else int(bool(spectrum_cache))
         self.ctx.call("sg_an_configure", int(fft_bits), cache, ola)
         return self
-
-    def _prep(self, x, flag):
-        assert flag in self.allowed_flags
-        x = x.to(self.device, torch.float32).contiguous()
-        if flag == 0:
-            assert x.dim() == 3 and x.shape[1] == 1, "wav input must be (B, 1, T)"
-            return x, x.shape[0], x.shape[2]
-        assert x.dim() == 3 and x.shape[2] == 32, "feature input must be (B, F, 32)"
-        return x, x.shape[0], x.shape[1]
 
     def compute_feat(self, x, flag=1):
         """wav (B,1,T) -> log-mel (B,F,32); audionet_csine.py:133-146."""
@@ -150,55 +125,13 @@ class audionet_csine(EngineOps):
         dec, scores, _ = self._forward(x, flag)
         return dec, scores
 
-    def read_activation(self, layer, B):
-        rows, ch = C.c_int32(), C.c_int32()
-        self.ctx.call("sg_an_debug_activation", layer, None, 0, C.byref(rows), C.byref(ch), self._stream())
-        out = torch.empty(B, rows.value, ch.value, device=self.device, dtype=torch.float32)
-        self.ctx.call("sg_an_debug_activation", layer, N._ptr(out), out.numel(), None, None, self._stream())
-        return out
-
     # ---- engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True):
-        x, B, TF = self._prep(x, flag)
-        self.check_labels(y, loss_spec)
-        y = y.to(self.device, torch.int64).contiguous()
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        grad = torch.empty_like(x) if want_grad else None
-        if hasattr(loss_spec, 'check'):
-            loss_spec.check(B, self.num_spks)
+        x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)
         spec = loss_spec.native()
-        self.ctx.call("sg_an_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), N._ptr(dec), N._ptr(scores),
-                      N._ptr(loss), N._ptr(grad), self._stream())
-        return dec, scores, loss, grad
-
-    # per-pass generator keys of the fused FeCo loop (sg_an_pgd_run_feco): step `it`, EOT repeat `r`
-    @staticmethod
-    def fused_pass_seed(base_seed, it, r=0):
-        return (int(base_seed) + it * 0x9E3779B97F4A7C15 + r * 0xC2B2AE3D27D4EB4F) & 0xFFFFFFFFFFFFFFFF
-
-    def _pgd_args(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace):
-        """the tensors and the parameter block the device loops share -> (x_adv, y, lower, upper, B, T, params, outputs)"""
-        x, B, T = self._prep(x, 0)
-        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
-        x_adv = x.clone()
-        y = y.to(self.device, torch.int64).contiguous()
-        lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()
-        upper = upper.to(self.device, torch.float32).expand_as(x).contiguous()
-        if hasattr(loss_spec, "check"):
-            loss_spec.check(B, self.num_spks)  # ScoreVJP: one (B, S) table, shared by the EOT repeats of an utterance
-        p = N.PgdParams()
-        p.loss = loss_spec.native()
-        p.step_size, p.max_iter, p.grad_sign = float(step_size), int(max_iter), int(grad_sign)
-        p.eot_size, p.eot_batch_size = int(eot_size), int(eot_batch_size)
-        success = torch.empty(B, device=self.device, dtype=torch.uint8)
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
-        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
-        return x_adv, y, lower, upper, B, T, p, (success, dec, scores, loss, ltr, dtr)
+        self.ctx.call("sg_an_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), *[N._ptr(t) for t in outs],
+                      self._stream())
+        return outs
 
     def _feco_params(self, feco, T):
         """sg_feco_params of one fused call: one key per call, from the model's noise bookkeeping (attack call, restart, call
@@ -213,71 +146,33 @@ class audionet_csine(EngineOps):
         f.index_base = int(feco.index_base) + self.row_keys()[0]
         return f
 
-    def _wav_stages(self, chain):
-        """the chain as a sg_wav_stage array.  Every randomised stage (AT) gets one base key, drawn in chain order like
-        ``defended_model._fwd`` draws them; ``last_fused_defense_seeds`` keeps them (None for a deterministic stage)."""
-        chain = list(chain)
-        if not 1 <= len(chain) <= N.SG_WAV_CHAIN_MAX:
-            raise ValueError("a chain of 1 .. %d input-level defenses runs on the device, got %d" % (N.SG_WAV_CHAIN_MAX, len(chain)))
-        stages = (N.WavStage * len(chain))()
-        keep, keys = [], []
-        index_base, row_base, _ = self.row_keys()
-        for i, d in enumerate(chain):
-            st = d.stage()
-            keep.append(st)  # (a filter's stage keeps its sections alive)
-            key = None
-            if getattr(d, 'randomised', False):
-                key = self.defense_seed(d.seed, d.seed_tag)
-                st.u.defense.seed, st.u.defense.index_base, st.u.defense.row_base = key, index_base, row_base
-            keys.append(key)
-            stages[i] = st
-        self.last_fused_defense_seeds = keys
-        return stages, keep
-
+    # the device loops: which C entry each takes and whether that entry has a FeCo pointer (``EngineOps._pgd_loop`` marshals)
     def pgd_run_defended(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, eot_size=1,
                          eot_batch_size=1, trace=False):
         """``pgd_run`` against this model behind a chain of native waveform-level defenses (defense.time_domain /
         defense.frequency_domain objects, applied in order before the log-mel front-end): the step loop of ``attack_batch`` over
         ``defended_model._loss_grad_through_defenses`` as ONE device-resident call (sg_an_pgd_run_defended).  The loop derives
         AT's key of step ``it``, repeat ``r`` from the stage's base key as ``fused_pass_seed(key, it, r)``."""
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        stages, keep = self._wav_stages(chain)
-        self.ctx.call("sg_an_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      stages, len(stages), None, *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_an_pgd_run_defended", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace, chain=chain, feco_slot=True)
 
     def pgd_run_defended_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, feco, eot_size=1,
                               eot_batch_size=1, trace=False):
         """``pgd_run_feco`` with a chain of native, deterministic waveform-level defenses in front of the log-mel front-end:
         ``defended_model(self, [(0, d1), ..., (1, feco)])`` as ONE device-resident call (sg_an_pgd_run_defended with feco).
         Keys and ``feco.calls`` bookkeeping as ``pgd_run_feco``."""
-        if any(getattr(d, 'randomised', False) for d in chain):
-            raise ValueError("a randomised input-level defense in front of FeCo keeps the step loop")
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        stages, keep = self._wav_stages(chain)
-        f = self._feco_params(feco, T)
-        self.ctx.call("sg_an_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      stages, len(stages), C.byref(f), *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_an_pgd_run_defended", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace, chain=chain, feco=feco)
 
     def pgd_run_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, feco, eot_size=1, eot_batch_size=1,
                      trace=False):
         """attack/FGSM.py:38-70 attack_batch against defended_model(self, [(1, feco)]) (BASELINE.json configs[3]) as one
         device-resident loop: log-mel -> FeCo -> CNN forward, hand-chained backward, EOT repeats over the defense's
         random initial frames (``feco.init == 'random'``) summed on the device.  `feco`: a FeCoDefense."""
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        f = self._feco_params(feco, T)
-        self.ctx.call("sg_an_pgd_run_feco", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      C.byref(f), *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_an_pgd_run_feco", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace, feco=feco)
 
     def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
                 trace=False):
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        self.ctx.call("sg_an_pgd_run", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_an_pgd_run", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace)

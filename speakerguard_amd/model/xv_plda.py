@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from ._engine_ops import EngineOps
+from ._engine_ops import EngineOps, _f32
 
 BITS = 16
 _TDNN = ("tdnn1", "tdnn2", "tdnn3", "tdnn4", "tdnn5")
@@ -74,15 +74,11 @@ def parse_enroll_model_file(path):
     return spk_ids, z_means, z_stds, np.concatenate(embs, 0)
 
 
-def _f32(a):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
-
-
 class xv_plda(EngineOps):
     allowed_flags = [0, 1, 2]  # 0: wav; 1: raw feat; 2: cmvn feat (xv_plda.py:45-47)
     range_type = "origin"
+    _feat_width = 30
+    _debug_activation = "sg_xv_debug_activation"
 
     def __init__(self, extractor_file, plda_file, mean_file, transform_mat_file, model_file=None,
                  threshold=None, device="cuda:0", dither=1.0, dither_seed=0):
@@ -104,23 +100,12 @@ class xv_plda(EngineOps):
         return self
 
     def _init(self, weights, threshold, device, dither, dither_seed, spk_ids):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise N.NativeError("xv_plda runs on the HIP engine only; device must be a GPU (got %s)" % device)
-        idx = self.device.index if self.device.index is not None else 0
-        self.device = torch.device("cuda", idx)
+        hp = self._open(device)  # host arrays must outlive sg_xv_load
         self.threshold = threshold if threshold else -np.inf  # xv_plda.py:41
         self.dither = float(dither)
         self.dither_seed = int(dither_seed)
         self._draw = 0
         sd = weights["state_dict"]
-        keep = []  # host arrays must outlive sg_xv_load
-
-        def hp(a):
-            a = _f32(a)
-            keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
         w = N.XvWeights()
         for l, name in enumerate(_TDNN):
             w.tdnn_weight[l] = hp(sd[name + ".weight"])
@@ -144,7 +129,6 @@ class xv_plda(EngineOps):
         w.enroll = hp(enroll)
         w.D, w.S, w.bn_eps = D, enroll.shape[0], 1e-5
         w.threshold = float(self.threshold) if np.isfinite(self.threshold) else -math.inf
-        self.ctx = N.Context(idx)
         self.ctx.call("sg_xv_load", C.byref(w))
         self.dim = D
         self.num_spks = enroll.shape[0]
@@ -187,20 +171,6 @@ class xv_plda(EngineOps):
         d.seed = self.noise_seed(self.dither_seed, self._draw)
         self._draw += 1  # every forward draws fresh noise, like the reference's global RNG
         return d
-
-    # per-pass generator keys of the fused loop (sg_xv_pgd_run): step `it`, EOT repeat `r`
-    @staticmethod
-    def fused_pass_seed(base_seed, it, r=0):
-        return (int(base_seed) + it * 0x9E3779B97F4A7C15 + r * 0xC2B2AE3D27D4EB4F) & 0xFFFFFFFFFFFFFFFF
-
-    def _prep(self, x, flag):
-        assert flag in self.allowed_flags
-        x = x.to(self.device, torch.float32).contiguous()
-        if flag == 0:
-            assert x.dim() == 3 and x.shape[1] == 1, "wav input must be (B, 1, T)"
-            return x, x.shape[0], x.shape[2]
-        assert x.dim() == 3 and x.shape[2] == 30, "feature input must be (B, F, 30)"
-        return x, x.shape[0], x.shape[1]
 
     def set_enroll(self, enroll_embs=None, threshold=None):
         """Replace the enrolled speakers and/or the decision threshold on the device."""
@@ -322,15 +292,7 @@ class xv_plda(EngineOps):
 
     def tdnn_activation(self, layer):
         """ReLU output of TDNN layer 1..5 from the last pass, (B, F_l, C_l) channel-last (parity tests)."""
-        rows, ch = C.c_int32(), C.c_int32()
-        self.ctx.call("sg_xv_debug_activation", layer, None, 0, C.byref(rows), C.byref(ch), self._stream())
-        return rows.value, ch.value
-
-    def read_activation(self, layer, B):
-        rows, ch = self.tdnn_activation(layer)
-        out = torch.empty(B, rows, ch, device=self.device, dtype=torch.float32)
-        self.ctx.call("sg_xv_debug_activation", layer, N._ptr(out), out.numel(), None, None, self._stream())
-        return out
+        return self.activation_shape(layer)
 
     # ------------------------------------------------------------------ engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):
@@ -338,55 +300,25 @@ class xv_plda(EngineOps):
 
         Returns (decisions, scores, loss, grad) with grad shaped like x (None if want_grad=False).
         """
-        x, B, TF = self._prep(x, flag)
-        self.check_labels(y, loss_spec)
-        y = y.to(self.device, torch.int64).contiguous()
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        grad = torch.empty_like(x) if want_grad else None
+        x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)
         dz = self._dither(dither_noise, dither_seed)
-        if hasattr(loss_spec, 'check'):
-            loss_spec.check(B, self.num_spks)
         spec = loss_spec.native()
-        self.ctx.call("sg_xv_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), C.byref(dz), N._ptr(dec),
-                      N._ptr(scores), N._ptr(loss), N._ptr(grad), self._stream())
-        return dec, scores, loss, grad
+        self.ctx.call("sg_xv_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), C.byref(dz),
+                      *[N._ptr(t) for t in outs], self._stream())
+        return outs
 
-    def _pgd_args(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace):
-        """the tensors and the parameter block the device loops share -> (x_adv, y, lower, upper, B, T, params, outputs)"""
-        x, B, T = self._prep(x, 0)
-        self.check_labels(y, loss_spec)  # once per call: the device loop runs max_iter steps on these labels
-        x_adv = x.clone()
-        y = y.to(self.device, torch.int64).contiguous()
-        lower = lower.to(self.device, torch.float32).expand_as(x).contiguous()
-        upper = upper.to(self.device, torch.float32).expand_as(x).contiguous()
-        if hasattr(loss_spec, "check"):
-            loss_spec.check(B, self.num_spks)  # ScoreVJP: one (B, S) table, shared by the EOT repeats of an utterance
-        p = N.PgdParams()
-        p.loss = loss_spec.native()
-        p.step_size, p.max_iter, p.grad_sign = float(step_size), int(max_iter), int(grad_sign)
-        p.eot_size, p.eot_batch_size = int(eot_size), int(eot_batch_size)
+    def _pgd_dither(self, p):
         p.dither = self._dither()
         self.last_fused_seed = int(p.dither.seed)
-        success = torch.empty(B, device=self.device, dtype=torch.uint8)
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, self.num_spks, device=self.device, dtype=torch.float32)
-        loss = torch.empty(B, device=self.device, dtype=torch.float32)
-        ltr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.float32) if trace else None
-        dtr = torch.empty(max_iter + 1, B, device=self.device, dtype=torch.int64) if trace else None
-        return x_adv, y, lower, upper, B, T, p, (success, dec, scores, loss, ltr, dtr)
 
+    # the device loops: which C entry each takes (``EngineOps._pgd_loop`` marshals; neither takes a FeCo block)
     def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
                 trace=False):
         """attack/FGSM.py:38-70 attack_batch as one device-resident loop, including EOT over the front-end's random
         dither (eot_size fresh-noise passes per gradient step, gradients summed on the device; the traces record each
         step's loss averaged and decision voted over its repeats, like the reference's verbose print)."""
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        self.ctx.call("sg_xv_pgd_run", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_xv_pgd_run", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace)
 
     def pgd_run_defended(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, chain, eot_size=1,
                          eot_batch_size=1, trace=False):
@@ -396,27 +328,8 @@ class xv_plda(EngineOps):
         stage (AT) gets one base key, drawn in chain order like ``defended_model._fwd`` draws them; the loop derives the
         key of step ``it``, repeat ``r`` from it as ``fused_pass_seed(key, it, r)``.  ``last_fused_seed`` (the dither's base
         key) and ``last_fused_defense_seeds`` (one entry per stage, None for a deterministic one) let tests replay."""
-        chain = list(chain)
-        if not 1 <= len(chain) <= N.SG_WAV_CHAIN_MAX:
-            raise ValueError("a chain of 1 .. %d input-level defenses runs on the device, got %d" % (N.SG_WAV_CHAIN_MAX, len(chain)))
-        x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
-                                                               eot_size, eot_batch_size, trace)
-        stages = (N.WavStage * len(chain))()
-        keep, keys = [], []
-        index_base, row_base, _ = self.row_keys()
-        for i, d in enumerate(chain):
-            st = d.stage()
-            keep.append(st)  # (a filter's stage keeps its sections alive)
-            key = None
-            if getattr(d, 'randomised', False):
-                key = self.defense_seed(d.seed, d.seed_tag)
-                st.u.defense.seed, st.u.defense.index_base, st.u.defense.row_base = key, index_base, row_base
-            keys.append(key)
-            stages[i] = st
-        self.last_fused_defense_seeds = keys
-        self.ctx.call("sg_xv_pgd_run_defended", N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p),
-                      stages, len(chain), *[N._ptr(t) for t in outs], self._stream())
-        return (x_adv,) + outs
+        return self._pgd_loop("sg_xv_pgd_run_defended", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                              eot_batch_size, trace, chain=chain)
 
     def time_layer(self, layer, B, T, iters=20):
         ms, fl, rows = C.c_float(), C.c_double(), C.c_int32()

@@ -10,10 +10,63 @@ from conftest import ROOT
 from speakerguard_amd import _native
 
 
-def header_functions():
+def header_text():
+    """include/speakerguard_hip.h without its comments"""
     text = open(os.path.join(ROOT, "include", "speakerguard_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sg_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def header_functions():
+    return sorted(set(re.findall(r"\b(sg_[a-z0-9_]+)\s*\(", header_text())))
+
+
+# ---------------------------------------------------------------- the prototypes against the ctypes mirror (_native.load's table)
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+_STRUCTS = {"sg_loss_spec": _native.LossSpec, "sg_dither": _native.Dither, "sg_pgd_params": _native.PgdParams,
+            "sg_xv_weights": _native.XvWeights, "sg_an_weights": _native.AnWeights, "sg_feco_params": _native.FecoParams,
+            "sg_wav_defense": _native.WavDefense, "sg_wav_filter": _native.WavFilter, "sg_wav_stage": _native.WavStage}
+# what a typed pointer of the mirror may point to, by the C type behind the `*` (anything else: c_void_p only)
+_POINTEES = dict(_SCALARS, **_STRUCTS, **{"sg_ctx*": ctypes.c_void_p})
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": ctypes.c_char_p})
+
+
+def declared(name):
+    """(return type, [parameter types]) of `name` as the header spells them: ``const`` kept on the return type only, the
+    parameters' names and ``const`` dropped, ``*`` attached to the type"""
+    m = re.search(r"^\s*([A-Za-z_][\w \t\*]*?)\s*\b%s\s*\(([^)]*)\)\s*;" % name, header_text(), flags=re.M)
+    assert m, "%s is not declared" % name
+    params = []
+    for param in m.group(2).split(","):
+        param = " ".join(param.replace("*", " * ").split())
+        if param in ("", "void"):
+            continue
+        words = [w for w in param.split()[:-1] if w != "const"]  # drop the parameter's name
+        params.append(words[0] + "".join(words[1:]))
+        assert set(words[1:]) <= {"*"} and re.fullmatch(r"\w+", param.split()[-1]), param
+    return " ".join(m.group(1).replace("*", " * ").split()).replace(" *", "*"), params
+
+
+def declared_argtypes(name):
+    """the mirror `name`'s prototype asks for, with every struct pointer typed and every other pointer a ``c_void_p``"""
+    return [_SCALARS[t] if t in _SCALARS else ctypes.POINTER(_STRUCTS[t[:-1]]) if t[:-1] in _STRUCTS else ctypes.c_void_p
+            for t in declared(name)[1] if t in _SCALARS or t.endswith("*")]
+
+
+@pytest.mark.parametrize("name", _native.EXPORTS)
+def test_binding_mirrors_the_prototype(name):
+    """arity; every scalar exactly; a pointer as ``c_void_p`` or as ``POINTER`` of the mirrored struct / scalar it points to;
+    the return type"""
+    ret, params = declared(name)
+    fn = getattr(_native.load(), name)
+    assert fn.restype is _RETURNS[ret], (name, ret, fn.restype)
+    assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, len(fn.argtypes or ()), params)
+    for i, (have, want) in enumerate(zip(fn.argtypes, params)):
+        if want.endswith("*"):
+            typed = _POINTEES.get(want[:-1])
+            assert have is ctypes.c_void_p or (typed is not None and have is ctypes.POINTER(typed)), (name, i, want, have)
+        else:
+            assert have is _SCALARS[want], (name, i, want, have)  # (a type this table does not know is a KeyError: add it)
 
 
 def test_library_exports_every_declared_symbol():
@@ -38,8 +91,8 @@ def test_struct_layouts_match_header(tmp_path):
     """sizeof of every struct that crosses the boundary, as gcc lays out the header's definition (x86-64 SysV), against
     the ctypes mirror: catches field-order / padding drift."""
     import subprocess
-    pairs = [("sg_loss_spec", _native.LossSpec), ("sg_dither", _native.Dither), ("sg_pgd_params", _native.PgdParams),
-             ("sg_xv_weights", _native.XvWeights), ("sg_feco_params", _native.FecoParams)]
+    pairs = sorted(_STRUCTS.items())
+    assert len(pairs) == 9
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include "speakerguard_hip.h"\nint main(void) {\n' +
                    "".join('    printf("%%zu\\n", sizeof(%s));\n' % c for c, _ in pairs) + "    return 0;\n}\n")

@@ -13,7 +13,8 @@ from speakerguard_amd.attack.PGD import PGD
 from speakerguard_amd.defense import AS, AT, BDR, LPF, MS, QT
 from speakerguard_amd.defense.feature_level import FeCoDefense, WarpedFeCoDefense
 from speakerguard_amd.model.defended_model import defended_model
-from test_defended_loop_host import B, S, T, _FusedBase, _header, _on_cpu, _StepBase
+from test_abi import declared_argtypes
+from test_defended_loop_host import B, S, T, _FusedBase, _header, _on_cpu, _step_loop, _StepBase
 
 
 class _AnStepBase(_StepBase):
@@ -69,9 +70,8 @@ def test_chain_in_front_of_feco_takes_its_own_loop():
     assert adv.shape == (4, 1, T) and success == [True] * 4
     # the input-chain route does not claim the mixed model, the FeCo-only route neither
     atk = PGD(defended_model(base, [(0, AS(3)), (1, FeCoDefense(0.5))]), verbose=0)
-    assert atk._fused_input_chain() is None and atk._fused_feco(2) is None
-    chain, feco = atk._fused_chain_feco(2)
-    assert [type(d).__name__ for d in chain] == ["AS"] and isinstance(feco, FeCoDefense)
+    name, (chain, feco) = atk._device_route(2)
+    assert name == "pgd_run_defended_feco" and [type(d).__name__ for d in chain] == ["AS"] and isinstance(feco, FeCoDefense)
 
 
 def _feco_fallbacks():
@@ -104,47 +104,31 @@ def test_average_order_keeps_the_step_loop():
     """'average' has no device loop (its step loop needs a native base, so the routing decision is asked directly)"""
     base = _AnBase()
     defense = [(0, AS(3)), (1, FeCoDefense(0.5))]
-    assert PGD(defended_model(base, defense), verbose=0)._fused_chain_feco(2) is not None
+    name, (chain, feco) = PGD(defended_model(base, defense), verbose=0)._device_route(2)
+    assert name == "pgd_run_defended_feco" and chain == [defense[0][1]] and feco is defense[1][1]
     avg = PGD(defended_model(base, defense, order='average'), verbose=0)
-    assert avg._fused_chain_feco(2) is None and avg._fused_input_chain() is None and not avg._can_fuse()
+    assert _step_loop(avg)
     # and the other refusals at the same level
-    assert PGD(defended_model(base, defense), verbose=0)._fused_chain_feco(1) is None
-    assert PGD(defended_model(_AnStepBase(), defense), verbose=0)._fused_chain_feco(2) is None
-    assert PGD(defended_model(base, [(0, AS(3))] * 9 + [(1, FeCoDefense(0.5))]), verbose=0)._fused_chain_feco(2) is None  # past the cap
-    assert PGD(defended_model(base, [(1, FeCoDefense(0.5))]), verbose=0)._fused_chain_feco(2) is None  # no chain: _fused_feco's
+    assert PGD(defended_model(base, defense), verbose=0)._device_route(1) is None
+    assert _step_loop(PGD(defended_model(_AnStepBase(), defense), verbose=0))
+    assert _step_loop(PGD(defended_model(base, [(0, AS(3))] * 9 + [(1, FeCoDefense(0.5))]), verbose=0))  # past the cap
+    # no chain: pgd_run_feco's model, never pgd_run_defended_feco's -- and this double has no pgd_run_feco
+    assert _step_loop(PGD(defended_model(base, [(1, FeCoDefense(0.5))]), verbose=0))
     from speakerguard_amd.adaptive_attack.BPDA import BPDA
-    assert PGD(defended_model(base, [(0, BPDA(AS(3))), (1, FeCoDefense(0.5))]), verbose=0)._fused_chain_feco(2) is None
+    assert _step_loop(PGD(defended_model(base, [(0, BPDA(AS(3))), (1, FeCoDefense(0.5))]), verbose=0))
     from speakerguard_amd.attack.CWinf import CWinf
-    assert CWinf(defended_model(base, defense), verbose=0)._fused_chain_feco(2) is None  # CWinf's opt-out applies unchanged
+    assert _step_loop(CWinf(defended_model(base, defense), verbose=0))  # CWinf's opt-out applies unchanged
 
 
 # ---------------------------------------------------------------- header, library and ctypes mirror
-_C2CTYPES = {
-    "sg_ctx*": ctypes.c_void_p, "float*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "const int64_t*": ctypes.c_void_p,
-    "int64_t*": ctypes.c_void_p, "uint8_t*": ctypes.c_void_p, "void*": ctypes.c_void_p, "int32_t": ctypes.c_int32,
-    "const sg_pgd_params*": ctypes.POINTER(_native.PgdParams), "const sg_wav_stage*": ctypes.POINTER(_native.WavStage),
-    "const sg_feco_params*": ctypes.POINTER(_native.FecoParams),
-}
-
-
-def _declared_argtypes(name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-    assert m, "%s is not declared" % name
-    types = []
-    for param in m.group(1).split(","):
-        ctype = " ".join(param.split()[:-1])  # drop the parameter's name
-        types.append(_C2CTYPES[ctype])
-    return types
-
-
 def test_header_library_and_binding_agree_on_the_call():
     name = "sg_an_pgd_run_defended"
     assert name in set(re.findall(r"\b(sg_[a-z0-9_]+)\s*\(", _header())) and name in _native.EXPORTS
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
     fn = getattr(_native.load(), name)
-    assert fn.restype is ctypes.c_int and list(fn.argtypes) == _declared_argtypes(name)
+    assert fn.restype is ctypes.c_int and list(fn.argtypes) == declared_argtypes(name)
     # the x-vector call differs by the FeCo argument only, and the comparison sees that
-    xv = _declared_argtypes("sg_xv_pgd_run_defended")
+    xv = declared_argtypes("sg_xv_pgd_run_defended")
     assert list(_native.load().sg_xv_pgd_run_defended.argtypes) == xv
     an = list(fn.argtypes)
     assert an[:10] == xv[:10] and an[10] is ctypes.POINTER(_native.FecoParams) and an[11:] == xv[10:]

@@ -114,26 +114,33 @@ def test_everything_else_keeps_the_step_loop(case):
     assert base.calls.count("loss_grad") == 2 * 3 and base.calls.count("pgd_update") == 2 * 2  # 2 batches x (2 steps + final pass)
 
 
+def _step_loop(atk):
+    """the route is the step loop whatever the batch size"""
+    return atk._device_route(1) is None and atk._device_route(2) is None
+
+
 def test_average_order_keeps_the_step_loop():
     """'average' has no device loop: the route must not take it (the step loop then needs a native base, so the attack is
     not run here: the routing decision is asked directly)"""
     base = _FusedBase()
     seq = PGD(defended_model(base, [(0, AS(3))]), verbose=0)
     avg = PGD(defended_model(base, [(0, AS(3))], order='average'), verbose=0)
-    assert [type(d).__name__ for d in seq._fused_input_chain()] == ["AS"]
-    assert avg._fused_input_chain() is None and not avg._can_fuse()
+    name, (chain,) = seq._device_route(B)
+    assert name == "pgd_run_defended" and [type(d).__name__ for d in chain] == ["AS"]
+    assert _step_loop(avg)
     # and the other refusals at the same level
-    assert PGD(defended_model(base, [(0, AS(3)), (1, FeCoDefense(0.5))]), verbose=0)._fused_input_chain() is None
-    assert PGD(defended_model(base, [(0, BPDA(AS(3)))]), verbose=0)._fused_input_chain() is None
-    assert PGD(defended_model(_StepBase(), [(0, AS(3))]), verbose=0)._fused_input_chain() is None
-    assert PGD(defended_model(base, [(0, AS(3))] * 9), verbose=0)._fused_input_chain() is None  # past the cap
+    assert _step_loop(PGD(defended_model(base, [(0, AS(3)), (1, FeCoDefense(0.5))]), verbose=0))
+    assert _step_loop(PGD(defended_model(base, [(0, BPDA(AS(3)))]), verbose=0))
+    assert _step_loop(PGD(defended_model(_StepBase(), [(0, AS(3))]), verbose=0))
+    assert _step_loop(PGD(defended_model(base, [(0, AS(3))] * 9), verbose=0))  # past the cap
     assert PGD.fuse_input_defenses is True
     # a randomised stage keeps the step loop (and its noise keys) unless the device loop's schedule is asked for
     from speakerguard_amd.defense import AT
     at = PGD(defended_model(base, [(0, AS(3)), (0, AT(25))]), verbose=0)
-    assert PGD.fuse_randomised_input_defenses is False and at._fused_input_chain() is None
+    assert PGD.fuse_randomised_input_defenses is False and _step_loop(at)
     at.fuse_randomised_input_defenses = True
-    assert [type(d).__name__ for d in at._fused_input_chain()] == ["AS", "AT"]
+    name, (chain,) = at._device_route(B)
+    assert name == "pgd_run_defended" and [type(d).__name__ for d in chain] == ["AS", "AT"]
 
 
 # ---------------------------------------------------------------- header and ctypes mirror (tests/test_abi.py's method)

@@ -424,7 +424,7 @@ def test_audionet_feco_fused_loop(capsys):
     dm = defended_model(hip, defense=[(1, FeCoDefense(0.5))])
     y = dm.make_decision(x)[0]
     fused = PGD(dm, epsilon=eps, step_size=step, max_iter=K, batch_size=4, verbose=0)
-    assert fused._fused_feco(4) is not None and fused._fused_feco(1) is None
+    assert fused._device_route(4) == ('pgd_run_feco', (dm.defense[0][1],)) and fused._device_route(1) is None
     chained = PGD(dm, epsilon=eps, step_size=step, max_iter=K, batch_size=4, verbose=0)
     chained.fuse_defended = False
     adv_f, succ_f = fused.attack(x, y)

@@ -201,7 +201,7 @@ def test_pgd10_through_warped_feco_on_xv_plda(xv_weights):
     with torch.no_grad():
         assert om.make_decision(x)[0].tolist() == y.tolist()
     atk = PGD(dm, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B, verbose=0)
-    assert atk._fused_feco(B) is None  # the host-chained path
+    assert atk._device_route(B) is None  # the host-chained path
     adv, succ = atk.attack(x.to(DEV), y.to(DEV))
     oadv, osucc = oatk.PGD(om, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B).attack(x, y)
 
@@ -258,7 +258,7 @@ def test_audionet_level1_random_eot():
         with torch.no_grad():
             return float(np.mean([torch.nn.functional.cross_entropy(dm.score(a), y).item() for _ in range(4)]))
     atk = PGD(dm, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B, EOT_size=2, EOT_batch_size=2, verbose=0)
-    assert atk._fused_feco(B) is None
+    assert atk._device_route(B) is None
     before = ce(x)
     adv, succ = atk.attack(x, y)
     after = ce(adv)

@@ -117,7 +117,7 @@ def test_config3_one_gpus_shard(capsys):
     with torch.no_grad():
         assert om.make_decision(x)[0].tolist() == y.tolist()
     atk = PGD(dm, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B, verbose=0)
-    assert atk._fused_feco(B) is not None  # the device loop, not the host-chained one
+    assert atk._device_route(B) == ('pgd_run_feco', (dm.defense[0][1],))  # the device loop, not the host-chained one
     adv, succ = atk.attack(x.to(DEV), y.to(DEV))
     oadv, osucc = oatk.PGD(om, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B).attack(x, y)
 
@@ -458,7 +458,7 @@ def test_config3_timed_workload_random_start_eot2():
     y = hip.make_decision(x.to(DEV))[0].cpu()  # the undefended model's clean decisions
     dm, om = defended_model(hip, defense=[(1, FeCoDefense(ratio, init='random', seed=11))]), OracleDefended()
     atk = PGD(dm, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B, EOT_size=R, EOT_batch_size=R, verbose=0)
-    assert atk._fused_feco(B) is not None  # the device loop, not the host-chained one
+    assert atk._device_route(B) == ('pgd_run_feco', (dm.defense[0][1],))  # the device loop, not the host-chained one
     adv, succ = atk.attack(x.to(DEV), y.to(DEV))
     om.base_seed, om.it = hip.last_fused_seed, 0
     oadv, osucc = oatk.PGD(om, task="CSI", epsilon=eps, step_size=step, max_iter=K, batch_size=B, EOT_size=R, EOT_batch_size=R).attack(x, y)

@@ -559,7 +559,7 @@ def test_fused_eot_over_dither_equals_stepwise_replay(xv_weights, dev, monkeypat
     # host class: PGD(EOT_size=4) on a dithered model takes the fused path and respects the epsilon ball
     from speakerguard_amd.attack.PGD import PGD
     atk = PGD(m, epsilon=0.002, step_size=0.0004, max_iter=iters, batch_size=3, EOT_size=reps, EOT_batch_size=2, verbose=0)
-    assert atk._can_fuse()
+    assert atk._device_route(3) == ('pgd_run', ())
     adv, succ = atk.attack(x, y)
     assert (adv - x).abs().max().item() <= 0.002 + 1e-7 and len(succ) == 3
     frac = float(((xa - x).abs() > 0).float().mean())
@@ -929,8 +929,8 @@ def test_noise_does_not_depend_on_where_the_batch_is_cut(xv_weights, dev):
     y = md.make_decision(x)[0]
 
     class HostLoop(PGD):  # the step-by-step loop over EOT.forward instead of the device loop
-        def _can_fuse(self):
-            return False
+        def _device_route(self, n_audios):
+            return None
 
     makers = {
         "device loop": lambda bs: PGD(md, epsilon=0.002, step_size=0.0005, max_iter=2, batch_size=bs, EOT_size=4, EOT_batch_size=2, verbose=0),

@@ -68,7 +68,7 @@ with torch.no_grad():
     odec_h = om.make_decision(adv.cpu())[0]
 diff = (adv.cpu() - oadv).abs()
 print("configs[3], one GPU's shard: PGD-%d vs FeCo-defended AudioNet, %d utterances x 3 s (device loop: %s; HIP %.2f s, oracle %.0f s)"
-      % (K, B, atk._fused_feco(B) is not None, t_h, t_o))
+      % (K, B, (atk._device_route(B) or (None,))[0] == 'pgd_run_feco', t_h, t_o))
 print("  clean decisions equal: %s" % (y.tolist() == oy.tolist()))
 print("  success flags: HIP %d/%d, oracle %d/%d, equal per utterance: %d/%d; decisions on own audio equal: %d/%d; the oracle's decisions on "
       "the HIP audio equal the HIP model's: %d/%d" % (sum(succ), B, sum(osucc), B, sum(bool(a) == bool(b) for a, b in zip(succ, osucc)), B,

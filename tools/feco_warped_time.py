@@ -67,7 +67,7 @@ def main():
         dm = defended_model(model, defense=[(1, WarpedFeCoDefense(0.5, 'ts'))])
         y = dm.make_decision(x)[0]
         atk = PGD(dm, task="CSI", epsilon=0.002, step_size=0.0004, max_iter=10, batch_size=B, verbose=0)
-        assert atk._fused_feco(B) is None
+        assert atk._device_route(B) is None
         med, lo, hi = timed(lambda: atk.attack(x, y), a.attacks, 1)
         emit({"what": "PGD-10 attack, warped FeCo (ts, 0.5) at level 1", "model": name.split()[0], "B": B, "seconds": 3,
               "median_ms_per_attack": round(med, 2), "median_ms_per_step": round(med / 10, 2), "min_ms": round(lo, 2),

@@ -13,7 +13,7 @@ with tempfile.TemporaryDirectory() as d:
     y = model.make_decision(x)[0]
     attacker = PGD(model, task="CSI", epsilon=0.002, step_size=0.0004, max_iter=5, batch_size=4, EOT_size=4, EOT_batch_size=4, verbose=0)
     adver, success = attacker.attack(x, y)
-    print("file-based model, dither", base.dither, "fused", attacker._can_fuse(), "max|dx|", (adver - x).abs().max().item(), "success", success)
+    print("file-based model, dither", base.dither, "device loop", attacker._device_route(4), "max|dx|", (adver - x).abs().max().item(), "success", success)
     a2, s2 = ShardedAttack(attacker).attack(x, y)
     print("sharded wrapper (world 1):", s2)
     # adaptive attack on the FeCo-defended AudioNet (BASELINE configs[3]): one device-resident loop
@@ -25,7 +25,7 @@ with tempfile.TemporaryDirectory() as d:
     ya = net.make_decision(x)[0]
     atk = PGD(net, epsilon=0.002, step_size=0.0004, max_iter=10, batch_size=6, EOT_size=4, EOT_batch_size=4, verbose=0)
     adver, success = atk.attack(x, ya)
-    print("FeCo(random)-defended AudioNet: device loop", atk._fused_feco(6) is not None, "max|dx|", (adver - x).abs().max().item(), "success", success)
+    print("FeCo(random)-defended AudioNet: device loop", (atk._device_route(6) or (None,))[0], "max|dx|", (adver - x).abs().max().item(), "success", success)
     # black-box attack with the queries of every model call split over the ranks (one rank here: a pass-through)
     from speakerguard_amd.attack.FAKEBOB import FAKEBOB
     from speakerguard_amd.shard import QueryShardedModel
