@@ -39,6 +39,7 @@ ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 ASAN_EXE   := $(ASAN_DIR)/abi_asan_driver
 ASAN_DEF   := $(ASAN_DIR)/defended_asan_driver
 ASAN_AN    := $(ASAN_DIR)/an_defended_asan_driver
+ASAN_XVFECO := $(ASAN_DIR)/xv_feco_asan_driver
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
@@ -60,6 +61,10 @@ $(ASAN_DIR)/an_defended_asan_driver.o: tests/native/an_defended_asan_driver.cpp 
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
+$(ASAN_DIR)/xv_feco_asan_driver.o: tests/native/xv_feco_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
 # (the host objects reference their embedded-code-object symbols even when none is embedded: define them empty)
 $(ASAN_EXE): $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/abi_asan_driver.o
 	nm -u $(ASAN_OBJS) | grep -o '__hip_fatbin_[0-9a-f]*' | sort -u | sed 's/.*/char &[8];/' > $(ASAN_DIR)/fatbin_syms.c
@@ -76,10 +81,16 @@ $(ASAN_AN): $(ASAN_EXE) $(ASAN_DIR)/an_defended_asan_driver.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
 	    $(ASAN_DIR)/an_defended_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN)
+# ... and the x-vector FeCo loop's (sg_xv_pgd_run_feco), which prints its launch sequence: a fourth
+$(ASAN_XVFECO): $(ASAN_EXE) $(ASAN_DIR)/xv_feco_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/xv_feco_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_AN)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_XVFECO) > /dev/null
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

@@ -400,6 +400,11 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 #define SG_STAGE_DEF_SCALE 64     /* scale / clip decision of a stage that is not first, and of the MFCC, from the pass's rows */
 #define SG_STAGE_DEF_REPLICATE 65 /* the iterate copied once per EOT repeat of the pass */
 #define SG_STAGE_DEF_REP_SUM 66   /* repeat sum of the cotangents, carried on or turned into the sign step (one launch) */
+/* FeCo inside the x-vector device loop (sg_xv_pgd_run_feco): the clustering + compression launch, its backward, and the level-2
+ * column copy / slab sum either side of the TDNN (the CMVN launches of that loop carry SG_STAGE_CMVN_FWD / _BWD) */
+#define SG_STAGE_XV_FECO_FWD 67
+#define SG_STAGE_XV_FECO_BWD 68
+#define SG_STAGE_XV_FECO_COLS 69
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -472,6 +477,15 @@ int sg_feco_kmeans_compress(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
 int sg_feco_compress_backward_reps(sg_ctx* ctx, const float* dout_dev, const int32_t* assign_dev, const int32_t* counts_dev,
                                    int32_t B, int32_t F, int32_t D, int32_t k, int32_t force, int32_t reps,
                                    float* dfeats_dev, void* stream);
+/* sg_feco_kmeans_compress for EOT repeats that each have their OWN features (a dithered front-end in front of the defense):
+ * feats (reps,B,F,D), row r * B + u = repeat r of utterance u.  Instance (u, r) clusters row r * B + u from key
+ * seed + r * 0xC2B2AE3D27D4EB4F and utterance index_base + u -- ids, means and counts bit for bit those of a single-row
+ * sg_feco_kmeans_compress(feats + (r * B + u) F D, B = 1, ..., that key, index_base + u, reps = 1) -- and writes
+ * assign (reps,B,F), out (reps,B,k,D), counts (reps,B,k) at the same row.  random_init == 0: every row is clustered from the
+ * even start (reps > 1 allowed: the rows differ).  The matching gradient is sg_feco_compress_backward on reps * B rows. */
+int sg_feco_kmeans_compress_rows(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
+                                 int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base, int32_t reps,
+                                 int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream);
 int sg_feco_compress_backward(sg_ctx* ctx, const float* dout_dev, const int32_t* assign_dev, const int32_t* counts_dev,
                               int32_t B, int32_t F, int32_t D, int32_t k, int32_t force, float* dfeats_dev, void* stream);
 
@@ -669,6 +683,37 @@ int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
                            const sg_wav_stage* chain, int32_t n_stages, const sg_feco_params* feco, uint8_t* success_dev,
                            int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* loss_trace_dev,
                            int64_t* decision_trace_dev, void* stream);
+
+/* ---- FeCo inside the device-resident x-vector PGD loop -------------------------------------------------------
+ * sg_xv_pgd_run against defended_model(xv_plda, [(level, FeCoDefense)]): arguments and outputs as sg_xv_pgd_run, plus the
+ * FeCo block (k = int(F * ratio) computed by the caller) and the level: 1 = FeCo on the raw MFCC, before CMVN; 2 = on the
+ * CMVN features.  The TDNN, tail, loss and TDNN backward run on k frames per row.  Per pass (step `it`, group starting at
+ * repeat g0, pass key = it * 0x9E3779B97F4A7C15 + g0 * 0xC2B2AE3D27D4EB4F, added to the dither's and to FeCo's seed):
+ *   dither != 0: reps = eot_size, every repeat a row (row = repeat * B + utterance, G per pass as in sg_xv_pgd_run).  MFCC on
+ *     the G * B rows, sg_feco_kmeans_compress_rows (repeat r of the group at + r * 0xC2B2AE3D27D4EB4F), the network, back
+ *     through CMVN and sg_feco_compress_backward to d loss / d raw MFCC (G * B, F, 30), then the MFCC adjoint and the
+ *     overlap-add of sg_xv_pgd_run: it sums the repeats in repeat order, carries earlier groups and takes the step on the
+ *     step's last group.
+ *   dither == 0, random_init: only the defense is random.  MFCC once per step on B rows, sg_feco_kmeans_compress with the
+ *     group's repeats, the network on them as one batch, sg_feco_compress_backward_reps (the repeats summed at the feature
+ *     level in repeat order, earlier groups carried there), ONE MFCC adjoint on B rows after the step's last group.
+ *   dither == 0, random_init == 0: one pass per step.
+ *   The final pass (it == max_iter) is one forward repeat, FeCo included.
+ * Level 1: MFCC -> FeCo -> CMVN over k frames into the padded features; back: CMVN backward from the split-K slabs ->
+ * compression backward.  Level 2: MFCC -> CMVN over F frames -> FeCo -> column copy into the padded features; back: slab sum ->
+ * compression backward -> CMVN backward over F frames.  Per-step records as sg_xv_pgd_run.
+ * All buffers come from the context's workspace and are grown before the loop -- the two-CU exchange buffers of the k-means
+ * (sg_feco_set_two_cu) included; inside it nothing is allocated, nothing synchronises and nothing is copied to the host.
+ * The workspace, the group size G and the 2 GiB activation bound are all taken at F frames per row, not at the k <= F frames
+ * the TDNN sees: stricter than the passes need (a batch may be refused, or cut into more groups, where k frames would fit),
+ * never looser.
+ * SG_ERR_ARG before any launch: feco NULL, level outside {1, 2}, B < 2 (with one utterance the reference drops empty clusters:
+ * host path), k < 1 or k > F, k frames too few for the TDNN context, whatever sg_feco_kmeans_compress refuses about F, k and
+ * max_iter, eot_size % eot_batch_size != 0, more than 65535 rows per pass, the 2 GiB activation bound of sg_xv_pgd_run. */
+int sg_xv_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
+                       int32_t B, int32_t T, const sg_pgd_params* params, const sg_feco_params* feco, int32_t level,
+                       uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+                       float* loss_trace_dev, int64_t* decision_trace_dev, void* stream);
 
 #ifdef __cplusplus
 }

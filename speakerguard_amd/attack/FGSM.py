@@ -5,17 +5,31 @@ and nothing between attack and model needs Python (no defense wrapper), the whol
 over the front-end's random dither included -- max_iter x (forward, hand-coded backward, sign step,
 projection) + the final forward-only pass -- is ONE C-ABI call (``model.pgd_run``).  A wrapper that
 carries only native waveform-level defenses in sequential order runs the same way, the chain inside
-the loop (``model.pgd_run_defended``), and so do one FeCoDefense on AudioNet (``model.pgd_run_feco``) and
-such a chain in front of it (``model.pgd_run_defended_feco``).  ``_device_route`` is the one place that
+the loop (``model.pgd_run_defended``), and so do one FeCoDefense on AudioNet or on the x-vector model
+(``model.pgd_run_feco``) and, on AudioNet, such a chain in front of it (``model.pgd_run_defended_feco``).  ``_device_route`` is the one place that
 decides this, once per batch, from one reading of the model; ``attack_batch`` makes the one call it
 names.  Otherwise the same loop runs step by step over ``model.loss_grad`` / ``model.pgd_update``.
 """
+import types
+
 import numpy as np
 import torch
 
 from ..adaptive_attack.EOT import EOT
 from .Attack import Attack
 from .utils import resolve_loss, resolve_prediction
+
+
+class _Route(tuple):
+    """``(method name, extra positional arguments)`` of a device loop, with the keyword arguments the call takes besides.
+    A tuple subclass and not a 3-tuple because tests/test_device_route.py and the GPU tests pin the routes as 2-tuples
+    (``name, extra = route``, ``route == ('pgd_run', ())``); the one keyword so far is FeCo's ``level``."""
+    kwargs = types.MappingProxyType({})  # (read-only default; every instance gets its own dict)
+
+    def __new__(cls, name, extra, **kwargs):
+        self = super().__new__(cls, (name, extra))
+        self.kwargs = kwargs
+        return self
 
 
 class FGSM(Attack):
@@ -52,6 +66,7 @@ class FGSM(Attack):
     fuse_defended = True  # False: PGD against a FeCo-defended model runs the host-chained loop (tests compare the two)
     fuse_input_defenses = True  # False: ... against native input-level defenses likewise (tests, tools/defended_loop_time.py)
     fuse_randomised_input_defenses = False  # True: chains holding AT run on the device too, with the device loop's noise keys
+    fuse_randomised_feco = False  # True: FeCo on a base that re-keys (xv_plda) takes its loop with dither / random init too
 
     def _device_route(self, n_audios):
         """Which device-resident loop of the base model runs ``attack_batch`` for a batch of `n_audios`: None for the step loop
@@ -61,14 +76,18 @@ class FGSM(Attack):
 
           * chain: 1 .. 8 native waveform defense objects (defense.time_domain / defense.frequency_domain) as they stand -- no
             BPDA wrapper, no Python callable -- and exactly what the model applies at level 0 (``flag2defense[0]``);
-          * feco: the one entry that is not at level 0, a FeCoDefense at level 1; needs ``fuse_defended`` and two utterances
-            (one: the reference drops empty clusters, the frame count varies -> host path).
+          * feco: the one entry that is not at level 0, a FeCoDefense at level 1 -- or at another level the base model lists in
+            ``feco_loop_levels`` (xv_plda: 2; the route then carries ``level=``), without a chain; needs ``fuse_defended`` and two
+            utterances (one: the reference drops empty clusters, the frame count varies -> host path).
 
         A randomised stage (AT) draws DIFFERENT noise on the two routes for the same seed: the device loop keys a pass by
         (step, repeat), the step loop by the defense's call number.  An attack's result must not change under its user, so such
         a chain keeps the step loop unless ``fuse_randomised_input_defenses`` asks for the device loop's schedule, and always
-        in front of FeCo (the clusterings' gradients are summed behind ONE chain pass).  The base model says what it offers by
-        having the method."""
+        in front of FeCo (the clusterings' gradients are summed behind ONE chain pass).  The same holds for FeCo on a base whose
+        loop re-keys the noise (``feco_loop_rekeys``: xv_plda, whose loop keys dither and random init by (step, repeat)): with a
+        dithered front-end or ``init='random'`` it keeps the step loop unless ``fuse_randomised_feco`` is set; the deterministic
+        configuration is bit-equal on both routes and takes the loop by default.  AudioNet's loop does not re-key.  The base
+        model says what it offers by having the method."""
         m = self.model
         defense = getattr(m, 'defense', None)
         base = getattr(m, 'base_model', m if defense is None else None)
@@ -88,19 +107,27 @@ class FGSM(Attack):
             if not rest:
                 if chain_ok and (self.fuse_randomised_input_defenses or not randomised):
                     route = 'pgd_run_defended', (chain,)
-            elif len(rest) == 1 and rest[0][0] == 1 and isinstance(rest[0][1], FeCoDefense) and self.fuse_defended and n_audios >= 2:
-                feco = rest[0][1]
-                if not chain:
-                    route = 'pgd_run_feco', (feco,)
-                elif chain_ok and not randomised and m.flag2defense.get(1, []) == [feco]:
-                    route = 'pgd_run_defended_feco', (chain, feco)
-        return route if route is not None and hasattr(base, route[0]) else None
+            elif len(rest) == 1 and isinstance(rest[0][1], FeCoDefense) and self.fuse_defended and n_audios >= 2:
+                level, feco = rest[0]
+                noisy = feco.init == 'random' or float(getattr(base, 'dither', 0.0)) != 0.0
+                if getattr(base, 'feco_loop_rekeys', False) and noisy and not self.fuse_randomised_feco:
+                    pass  # the loop would draw other noise than the step loop does for this seed
+                elif level == 1:
+                    if not chain:
+                        route = 'pgd_run_feco', (feco,)
+                    elif chain_ok and not randomised and m.flag2defense.get(1, []) == [feco]:
+                        route = 'pgd_run_defended_feco', (chain, feco)
+                elif not chain and level in getattr(base, 'feco_loop_levels', (1,)):
+                    route = _Route('pgd_run_feco', (feco,), level=level)
+        if route is None or not hasattr(base, route[0]):
+            return None
+        return route if isinstance(route, _Route) else _Route(*route)
 
-    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, name, extra):
+    def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, name, extra, **kwargs):
         base = getattr(self.model, 'base_model', self.model)
         x_adv, success, dec, scores, loss, ltr, dtr = getattr(base, name)(
             x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, *extra,
-            self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose))
+            self.EOT_size, self.EOT_batch_size, trace=bool(self.verbose), **kwargs)
         if self.verbose:
             ltr, dtr = ltr.cpu().numpy(), dtr.cpu().numpy()
             target = y_batch.detach().cpu().numpy()
@@ -112,7 +139,7 @@ class FGSM(Attack):
     def attack_batch(self, x_batch, y_batch, lower, upper, batch_id):
         route = self._device_route(x_batch.shape[0])
         if route is not None:
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, *route)
+            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, *route, **getattr(route, 'kwargs', {}))
         x_batch = x_batch.clone()
         lower = lower.expand_as(x_batch).contiguous()
         upper = upper.expand_as(x_batch).contiguous()

@@ -170,8 +170,8 @@ __device__ __forceinline__ float row_tree_sum(float v) {
 //     final lists -- same ids, same ascending sums, same division as feco_compress_kernel -- handed out by the kernel.
 template <int DPAD>
 __global__ __launch_bounds__(kFecoThreads) void feco_kmeans_kernel(const float* __restrict__ feats, int F, int D, int k,
-                                                                   int max_iter, int seeded, uint64_t seed, int64_t index_base,
-                                                                   int x_in_lds, int fast_lists, int JC, FecoSched sched,
+                                                                   int max_iter, int seeded, int row_wise, uint64_t seed,
+                                                                   int64_t index_base, int x_in_lds, int fast_lists, int JC, FecoSched sched,
                                                                    FecoPair pr, int* __restrict__ assign, float* __restrict__ out,
                                                                    int* __restrict__ counts) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -195,14 +195,15 @@ __global__ __launch_bounds__(kFecoThreads) void feco_kmeans_kernel(const float* 
     const int tid = threadIdx.x;
     const int lane = tid & 63, lh = lane >> 5, ln = lane & 31;
     // blockIdx.y = repeat: the same utterances clustered again from other random frames (EOT over the defense); repeat r
-    // uses key seed + r * 0xC2B2AE3D27D4EB4F and writes slot r * gridDim.x + utterance of every output
+    // uses key seed + r * 0xC2B2AE3D27D4EB4F and writes slot r * gridDim.x + utterance of every output.  row_wise: the repeats
+    // have features of their own (a dithered front-end in front of the defense) -- repeat r reads that slot too
     // Two CUs per instance: the grid's z dimension is the half.  (Blocks go to the 8 XCDs round robin by linear index: with
     // the instances a multiple of 8 the two halves share an XCD -- a speed assumption only.  Halves as neighbours in x --
     // different XCDs -- measured 97 us per call against 90; x and x ^ 8 -- same XCD, dispatched together -- 92.)
     const int half = pr.on ? (int)blockIdx.z : 0;
     const int bx = (int)blockIdx.x, nbx = (int)gridDim.x;
-    const float* x = feats + (size_t)bx * F * D;
     const size_t slot = (size_t)blockIdx.y * nbx + bx;
+    const float* x = feats + (row_wise ? slot : (size_t)bx) * F * D;
     __shared__ int pair_solo;
     if (tid == 0) pair_solo = 0;
     seed += (uint64_t)blockIdx.y * 0xC2B2AE3D27D4EB4Full;
@@ -688,36 +689,69 @@ __global__ void feco_compress_bwd_kernel(const float* __restrict__ dout, const i
 // serves all of them.  dout (R, B, k, D), assign (R, B, F), counts (R, B, k) -> dfeats (B, F, D).
 __global__ void feco_compress_bwd_reps_kernel(const float* __restrict__ dout, const int* __restrict__ assign,
                                               const int* __restrict__ counts, int B, int F, int D, int k, int force, int R,
-                                              float* __restrict__ dfeats) {
+                                              const float* carry, float* dfeats) {
     const int b = blockIdx.y;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= F * D) return;
     const int i = e / D, d = e - i * D;
-    float acc = 0.f;
+    // carry: the sum over the repeats of earlier passes of the same step (may alias dfeats: one thread per element)
+    float acc = carry ? carry[((size_t)b * F + i) * D + d] : 0.f;
     for (int r = 0; r < R; ++r) {
         const size_t u = (size_t)r * B + b;
         const int j = assign[u * F + i];
         float g = dout[(u * k + j) * D + d] / (float)counts[u * k + j];
         if (force && i < k && counts[u * k + i] == 0) g = g + dout[(u * k + i) * D + d];
-        acc = r == 0 ? g : acc + g;
+        acc = r == 0 && !carry ? g : acc + g;
     }
     dfeats[((size_t)b * F + i) * D + d] = acc;
 }
 
+constexpr size_t kFecoLdsMax = 150 * 1024;  // (feco_kmeans_impl)
+
 }  // namespace
 
-static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
-                            int seeded, uint64_t seed, int64_t index_base, int reps, int32_t* assign_dev, float* out_dev,
-                            int32_t* counts_dev, void* stream) {
-    if (!ctx) return SG_ERR_ARG;
-    if (!feats_dev || !assign_dev || B <= 0 || F <= 0 || D <= 0 || D > kFecoMaxD || k <= 0 || k > F || max_iter <= 0 || reps < 1 ||
-        reps > 65535)
+int sg::feco_kmeans_check(sg_ctx* ctx, int B, int F, int D, int k, int max_iter, int reps) {
+    if (B <= 0 || F <= 0 || D <= 0 || D > kFecoMaxD || k <= 0 || k > F || max_iter <= 0 || reps < 1 || reps > 65535)
         return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
+    const size_t least = (size_t)feco_layout(F, k, D <= 32 ? 32 : 64, 1, 0, 0).total * sizeof(float);  // one chunk, no extras
+    if (least > kFecoLdsMax)
+        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: %d clusters x %d dims + %d frames need %zu bytes of LDS (limit %zu): "
+                         "utterance too long for one block", k, D, F, least, kFecoLdsMax);
+    return SG_OK;
+}
+
+bool sg::feco_pair_buffers(sg_ctx* ctx) {
+    if (ctx->feco_xchg) return true;
+    if (ctx->feco_two_cu == 0) return false;
+    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const size_t inst_max = (size_t)cus / 2, words = inst_max * 2 * 2 * kFecoMergeCap;  // room for the most instances that can be paired
+    void *px = nullptr, *pf = nullptr;
+    if (hipMalloc(&px, words * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&pf, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
+        hipMemset(pf, 0, inst_max * 2 * sizeof(unsigned)) == hipSuccess) {
+        ctx->feco_xchg = static_cast<unsigned long long*>(px);
+        ctx->feco_flags = static_cast<unsigned*>(pf);
+        ctx->model_allocs.push_back(px);
+        ctx->model_allocs.push_back(pf);
+        ctx->feco_epoch = 0;
+        return true;
+    }
+    if (px) (void)hipFree(px);  // no room: one block per instance
+    if (pf) (void)hipFree(pf);
+    (void)hipGetLastError();
+    return false;
+}
+
+static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
+                            int seeded, int row_wise, uint64_t seed, int64_t index_base, int reps, int32_t* assign_dev,
+                            float* out_dev, int32_t* counts_dev, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    if (!feats_dev || !assign_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
+    if (int rc = feco_kmeans_check(ctx, B, F, D, k, max_iter, reps)) return rc;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipSetDevice failed");
     // LDS holds the centred centroids (rows padded to 32 / 64 floats), ids, member lists and -- when they fit -- the chunk
     // counts of the fast member lists and the centred frames (else the frames are re-read from HBM / L2 in every step).
     // 150 KB cover ~19 s at D <= 32, ratio 0.5 (F = 1930, k = 965); beyond that the call is refused.
-    constexpr size_t kLdsMax = 150 * 1024;
+    constexpr size_t kLdsMax = kFecoLdsMax;
     const int dpad = D <= 32 ? 32 : 64;
     const int ntc = (k + 31) / 32;
     // a frame tile's centroid tiles are cut into JC chunks (300 x 150: 10 frame tiles x 2 chunks of 3 / 2 tiles)
@@ -736,10 +770,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     const bool pair_ok = ctx->feco_two_cu != 0 && dpad == 32 && 2 * (long)B * reps <= cus;
     const int kp_host = (k + 31) & ~31;
     auto bytes = [&](int jc, int fast, int xin) { return (size_t)feco_layout(F, k, dpad, jc, fast, xin).total * sizeof(float); };
-    if (bytes(JC, 0, 0) > kLdsMax) JC = 1;
-    if (bytes(JC, 0, 0) > kLdsMax)
-        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: %d clusters x %d dims + %d frames need %zu bytes of LDS (limit %zu): "
-                         "utterance too long for one block", k, D, F, bytes(JC, 0, 0), kLdsMax);
+    if (bytes(JC, 0, 0) > kLdsMax) JC = 1;  // (one chunk fits: feco_kmeans_check)
     // the assignment's units (frame tile, chunk jc of its centroid tiles [ntc jc / JC, ntc (jc + 1) / JC)) dealt to the waves:
     // largest first, each to the least loaded SIMD (waves w, w + 4, w + 8, w + 12) and there to the least loaded wave with a
     // free slot -- 300 x 150: 20 units of 2 / 3 tiles -> 12 / 13 / 12 / 13 tiles per SIMD
@@ -751,22 +782,7 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     // mask, and the flag values have room for the iterations
     if (pair_ok && JC > 1 && nunits <= 32 && max_iter <= kFecoPairMaxIter && kp_host <= 2048) {
         const size_t inst_max = (size_t)cus / 2, words = inst_max * 2 * 2 * kFecoMergeCap;
-        if (!ctx->feco_xchg) {  // room for the most instances that can be paired
-            void *px = nullptr, *pf = nullptr;
-            if (hipMalloc(&px, words * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&pf, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
-                hipMemset(pf, 0, inst_max * 2 * sizeof(unsigned)) == hipSuccess) {
-                ctx->feco_xchg = static_cast<unsigned long long*>(px);
-                ctx->feco_flags = static_cast<unsigned*>(pf);
-                ctx->model_allocs.push_back(px);
-                ctx->model_allocs.push_back(pf);
-                ctx->feco_epoch = 0;
-            } else {  // no room: one block per instance
-                if (px) (void)hipFree(px);
-                if (pf) (void)hipFree(pf);
-                (void)hipGetLastError();
-            }
-        }
-        if (ctx->feco_xchg) {
+        if (feco_pair_buffers(ctx)) {
             const unsigned launch = ++ctx->feco_epoch;  // (0 is what a fresh flag word holds: never a launch id)
             if (launch == 0) ctx->feco_epoch = 1;
             // tags repeat every 2^15 launches: the words of the last cycle are wiped before they could be taken for new ones
@@ -824,10 +840,10 @@ static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int3
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
     if (dpad == 32)
         hipLaunchKernelGGL(feco_kmeans_kernel<32>, dim3(B, reps, pr.on ? 2 : 1), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F,
-                           D, k, max_iter, seeded, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
+                           D, k, max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
     else
         hipLaunchKernelGGL(feco_kmeans_kernel<64>, dim3(B, reps), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F, D, k,
-                           max_iter, seeded, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
+                           max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
     static const bool tr_on = sg_tune_env("SG_FECO_TRACE") != nullptr;
@@ -867,12 +883,12 @@ extern "C" int sg_feco_set_two_cu(sg_ctx* ctx, int32_t mode) {
 
 extern "C" int sg_feco_kmeans(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                               int32_t max_iter, int32_t* assign_dev, void* stream) {
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, 0, 0, 0, 1, assign_dev, nullptr, nullptr, stream);
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, 0, 0, 0, 0, 1, assign_dev, nullptr, nullptr, stream);
 }
 
 extern "C" int sg_feco_kmeans_seeded(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                      int32_t max_iter, uint64_t seed, int64_t index_base, int32_t* assign_dev, void* stream) {
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, 1, seed, index_base, 1, assign_dev, nullptr, nullptr, stream);
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, 1, 0, seed, index_base, 1, assign_dev, nullptr, nullptr, stream);
 }
 
 extern "C" int sg_feco_kmeans_compress(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
@@ -881,7 +897,15 @@ extern "C" int sg_feco_kmeans_compress(sg_ctx* ctx, const float* feats_dev, int3
     if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: out and counts are required");
     if (reps > 1 && !random_init)
         return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: repeats of the evenly started clustering coincide (reps must be 1)");
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, random_init != 0, seed, index_base, reps, assign_dev, out_dev,
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, random_init != 0, 0, seed, index_base, reps, assign_dev, out_dev,
+                            counts_dev, stream);
+}
+
+extern "C" int sg_feco_kmeans_compress_rows(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
+                                            int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base, int32_t reps,
+                                            int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream) {
+    if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_rows: out and counts are required");
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, random_init != 0, 1, seed, index_base, reps, assign_dev, out_dev,
                             counts_dev, stream);
 }
 
@@ -921,9 +945,14 @@ extern "C" int sg_feco_compress_backward_reps(sg_ctx* ctx, const float* dout_dev
         return fail(ctx, SG_ERR_ARG, "sg_feco_compress_backward_reps: bad arguments");
     if (hipSetDevice(ctx->device) != hipSuccess)
         return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: hipSetDevice failed");
-    hipLaunchKernelGGL(feco_compress_bwd_reps_kernel, dim3((F * D + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, dout_dev,
-                       assign_dev, counts_dev, B, F, D, k, force, reps, dfeats_dev);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = launch_feco_bwd_reps(dout_dev, assign_dev, counts_dev, B, F, D, k, force, reps, nullptr, dfeats_dev, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_compress_backward_reps: %s", hipGetErrorString(e));
     return SG_OK;
+}
+
+hipError_t sg::launch_feco_bwd_reps(const float* dout, const int* assign, const int* counts, int B, int F, int D, int k, int force,
+                                    int R, const float* carry, float* dfeats, hipStream_t s) {
+    hipLaunchKernelGGL(feco_compress_bwd_reps_kernel, dim3((F * D + 255) / 256, B), dim3(256), 0, s, dout, assign, counts, B, F, D, k,
+                       force, R, carry, dfeats);
+    return hipGetLastError();
 }

@@ -235,15 +235,22 @@ struct PassDims {
 // waveform / features -> padded CMVN features in ws.feats
 // want_grad: a backward of this pass follows (the forward leaves its spectra and mel energies for it: 39 MB at 64 utterances,
 // not written by forward-only calls -- decisions, NES / FAKEBOB queries, the last pass of an attack)
+// the range decision (unless kept) and the MFCC of the pass: waveform -> ws.feats_raw
+int run_mfcc_forward(sg_ctx* ctx, const float* x, const PassDims& d, const sg_dither* dz, bool want_grad, hipStream_t s) {
+    Workspace& w = ctx->ws;
+    if (!d.keep_scale) SG_HIP(launch_input_scale(x, (int64_t)(d.Bu > 0 ? d.Bu : d.B) * d.T, ctx->range_scratch, w.scale, 0, s));
+    MfccTables tab = ctx->tab;
+    tab.spec_cache = want_grad ? w.spec_cache : nullptr;  // the backward of this pass starts from the stored spectrum
+    tab.mel_cache = want_grad ? w.mel_cache : nullptr;
+    tab.rep_utts = d.Bu;
+    SG_STAGE(SG_STAGE_MFCC_FWD, launch_mfcc_fwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.feats_raw, s));
+    return SG_OK;
+}
+
 int run_frontend(sg_ctx* ctx, const float* x, const PassDims& d, int flag, const sg_dither* dz, bool want_grad, hipStream_t s) {
     Workspace& w = ctx->ws;
     if (flag == SG_FLAG_WAV) {
-        if (!d.keep_scale) SG_HIP(launch_input_scale(x, (int64_t)(d.Bu > 0 ? d.Bu : d.B) * d.T, ctx->range_scratch, w.scale, 0, s));
-        MfccTables tab = ctx->tab;
-        tab.spec_cache = want_grad ? w.spec_cache : nullptr;  // the backward of this pass starts from the stored spectrum
-        tab.mel_cache = want_grad ? w.mel_cache : nullptr;
-        tab.rep_utts = d.Bu;
-        SG_STAGE(SG_STAGE_MFCC_FWD, launch_mfcc_fwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.feats_raw, s));
+        if (int rc = run_mfcc_forward(ctx, x, d, dz, want_grad, s)) return rc;
         SG_STAGE(SG_STAGE_CMVN_FWD, launch_cmvn_fwd(w.feats_raw, kCep, w.feats, kFeatPad, d.B, d.F, s));
     } else if (flag == SG_FLAG_RAW) {
         SG_HIP(launch_cmvn_fwd(x, kCep, w.feats, kFeatPad, d.B, d.F, s));
@@ -383,6 +390,28 @@ int check_dims(sg_ctx* ctx, int B, int TF, int flag, PassDims* d) {
     return SG_OK;
 }
 
+// d loss / d raw MFCC (ws.dfeats_raw) -> d loss / d waveform: the MFCC adjoint and the overlap-add, which sums the d.B / utterances
+// repeats of the pass (+ grad_acc_in, the earlier passes of the step) and, with x_update, takes the step
+int run_mfcc_adjoint(sg_ctx* ctx, const float* x, const PassDims& d, const sg_dither* dz, float* grad_out, float* x_update,
+                     const float* lower, const float* upper, float step, int grad_sign, hipStream_t s, const float* grad_acc_in) {
+    Workspace& w = ctx->ws;
+    MfccTables tab = ctx->tab;
+    static const bool use_cache = [] {
+        const char* e = sg_tune_env("SG_MFCC_CACHE");  // 0 = recompute the forward in the backward kernel
+        return !e || atoi(e) != 0;
+    }();
+    if (use_cache) {
+        tab.spec_cache = w.spec_cache;
+        tab.mel_cache = w.mel_cache;
+    }
+    tab.rep_utts = d.Bu;
+    const int utts = d.Bu > 0 ? d.Bu : d.B;
+    SG_STAGE(SG_STAGE_MFCC_BWD, launch_mfcc_bwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.dfeats_raw, w.dframes, s));
+    SG_STAGE(SG_STAGE_OVERLAP_ADD, launch_frames_to_wave(w.dframes, utts, d.T, d.F, d.B / utts, grad_acc_in, grad_out, x_update,
+                                                         lower, upper, step, grad_sign, s));
+    return SG_OK;
+}
+
 // after the tail produced ws.demb: chain back to the caller's input level
 int run_backward_to_input(sg_ctx* ctx, const float* x, const PassDims& d, int flag, const sg_dither* dz,
                           float* grad_out, float* x_update, const float* lower, const float* upper, float step,
@@ -399,20 +428,7 @@ int run_backward_to_input(sg_ctx* ctx, const float* x, const PassDims& d, int fl
     } else {
         SG_STAGE(SG_STAGE_CMVN_BWD, launch_cmvn_bwd(w.dfeats, kFeatPad, kL1BwdSplitK, (long long)d.B * d.F * kFeatPad,
                                                     w.dfeats_raw, kCep, d.B, d.F, s));
-        MfccTables tab = ctx->tab;
-        static const bool use_cache = [] {
-            const char* e = sg_tune_env("SG_MFCC_CACHE");  // 0 = recompute the forward in the backward kernel
-            return !e || atoi(e) != 0;
-        }();
-        if (use_cache) {
-            tab.spec_cache = w.spec_cache;
-            tab.mel_cache = w.mel_cache;
-        }
-        tab.rep_utts = d.Bu;
-        const int utts = d.Bu > 0 ? d.Bu : d.B;
-        SG_STAGE(SG_STAGE_MFCC_BWD, launch_mfcc_bwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.dfeats_raw, w.dframes, s));
-        SG_STAGE(SG_STAGE_OVERLAP_ADD, launch_frames_to_wave(w.dframes, utts, d.T, d.F, d.B / utts, grad_acc_in, grad_out, x_update,
-                                                             lower, upper, step, grad_sign, s));
+        return run_mfcc_adjoint(ctx, x, d, dz, grad_out, x_update, lower, upper, step, grad_sign, s, grad_acc_in);
     }
     return SG_OK;
 }
@@ -474,8 +490,66 @@ struct XvLoopCall {  // the caller's buffers, as the entry point received them
     LoopOut out;
 };
 
-// The device-resident PGD loop of the x-vector model: sg_xv_pgd_run (n_stages == 0: no chain, `ci` says identity) and
-// sg_xv_pgd_run_defended (the chain and what def_chain_check found), after their argument checks.
+// ---- FeCo inside the loop (sg_xv_pgd_run_feco)
+struct XvFecoPass {  // one pass of the loop as FeCo sees it
+    const sg_feco_params* f;
+    int level;     // 1: on the raw MFCC, before CMVN; 2: on the CMVN features
+    bool rowwise;  // dithered front-end: every repeat has MFCC rows of its own (else: the repeats cluster the same B rows)
+    int B, F;
+    int Gi;        // repeats of the pass
+    bool first_group, final_group;
+    uint64_t key;  // f->seed + the pass key; repeat r of the pass: + r * kRepKey (the kernels' stride)
+    int front_rows() const { return rowwise ? B * Gi : B; }  // rows of the MFCC and of every buffer in front of FeCo
+    int net_rows() const { return B * Gi; }                  // rows of the compressed features: what the TDNN sees
+};
+
+// ws.feats_raw -> the TDNN's padded input ws.feats, k frames per row
+int xv_feco_forward(sg_ctx* ctx, const XvFecoPass& q, hipStream_t s) {
+    Workspace& w = ctx->ws;
+    const sg_feco_params* f = q.f;
+    const float* in = w.feats_raw;
+    if (q.level == 2) {
+        // (shared rows: the first group's CMVN features serve every group of the step)
+        if (q.rowwise || q.first_group) SG_STAGE(SG_STAGE_CMVN_FWD, launch_cmvn_fwd(w.feats_raw, kCep, w.feco_cm, kCep, q.front_rows(), q.F, s));
+        in = w.feco_cm;
+    }
+    trace_mark(ctx, SG_STAGE_XV_FECO_FWD, s, 0);
+    int rc = q.rowwise ? sg_feco_kmeans_compress_rows(ctx, in, q.B, q.F, kCep, f->k, f->max_iter, f->random_init, q.key, f->index_base, q.Gi,
+                                                      w.feco_ids, w.feco_out, w.feco_cnt, s)
+                       : sg_feco_kmeans_compress(ctx, in, q.B, q.F, kCep, f->k, f->max_iter, f->random_init, q.key, f->index_base, q.Gi,
+                                                 w.feco_ids, w.feco_out, w.feco_cnt, s);
+    if (rc) return rc;
+    trace_mark(ctx, SG_STAGE_XV_FECO_FWD, s, 1);
+    if (q.level == 1) SG_STAGE(SG_STAGE_CMVN_FWD, launch_cmvn_fwd(w.feco_out, kCep, w.feats, kFeatPad, q.net_rows(), f->k, s));
+    else SG_STAGE(SG_STAGE_XV_FECO_COLS, launch_copy_cols(w.feco_out, kCep, w.feats, kFeatPad, (int64_t)q.net_rows() * f->k, kCep, s));
+    return SG_OK;
+}
+
+// the split-K slabs of the tdnn1 data gradient (ws.dfeats, k frames per row) -> d loss / d raw MFCC (ws.dfeats_raw).  Shared
+// rows: the repeats are summed here, in repeat order, earlier groups carried in the destination; ws.dfeats_raw is complete after
+// the step's last group.
+int xv_feco_backward(sg_ctx* ctx, const XvFecoPass& q, hipStream_t s) {
+    Workspace& w = ctx->ws;
+    const int k = q.f->k, rows = q.net_rows();
+    const long long slab = (long long)rows * k * kFeatPad;
+    if (q.level == 1) SG_STAGE(SG_STAGE_CMVN_BWD, launch_cmvn_bwd(w.dfeats, kFeatPad, kL1BwdSplitK, slab, w.dfeco, kCep, rows, k, s));
+    else SG_STAGE(SG_STAGE_XV_FECO_COLS, launch_sum_cols(w.dfeats, kFeatPad, kL1BwdSplitK, slab, w.dfeco, kCep, (int64_t)rows * k, kCep, s));
+    float* dst = q.level == 1 ? w.dfeats_raw : w.dfeco_cm;
+    trace_mark(ctx, SG_STAGE_XV_FECO_BWD, s, 0);
+    if (q.rowwise) {
+        if (int rc = sg_feco_compress_backward(ctx, w.dfeco, w.feco_ids, w.feco_cnt, rows, q.F, kCep, k, 1, dst, s)) return rc;
+    } else {
+        SG_HIP(launch_feco_bwd_reps(w.dfeco, w.feco_ids, w.feco_cnt, q.B, q.F, kCep, k, 1, q.Gi, q.first_group ? nullptr : dst, dst, s));
+    }
+    trace_mark(ctx, SG_STAGE_XV_FECO_BWD, s, 1);
+    if (q.level == 2 && (q.rowwise || q.final_group))
+        SG_STAGE(SG_STAGE_CMVN_BWD, launch_cmvn_bwd(w.dfeco_cm, kCep, 1, 0, w.dfeats_raw, kCep, q.front_rows(), q.F, s));
+    return SG_OK;
+}
+
+// The device-resident PGD loop of the x-vector model: sg_xv_pgd_run (n_stages == 0: no chain, `ci` says identity),
+// sg_xv_pgd_run_defended (the chain and what def_chain_check found) and sg_xv_pgd_run_feco (`feco` at `level`, no chain), after
+// their argument checks.
 //
 // Expectation over the front-end's random dither and over a randomised stage (adaptive_attack/EOT.py:16-54; the reference
 // hard-codes dither = 1.0 at xv_plda.py:119, so this IS its default behaviour): every gradient step runs eot_size passes
@@ -494,12 +568,18 @@ struct XvLoopCall {  // the caller's buffers, as the entry point received them
 // kernels read them once per repeat and key repeat r's dither by seed + r * kRepKey -- and the overlap-add sums the
 // repeats and takes the step.  Any other chain runs every repeat as its own row through chain, model and both backwards;
 // the sum comes last.
+//
+// FeCo between front-end and TDNN (sg_xv_pgd_run_feco; contract in speakerguard_hip.h): the TDNN sees k frames per row.  A
+// dithered front-end gives every repeat MFCC rows of its own: FeCo clusters them row-wise and the overlap-add sums the
+// repeats as above.  Without dither only the defense can be random: the repeats cluster the SAME B rows, their gradients are
+// summed at the feature level and one MFCC adjoint on B rows follows the step's last group.
 int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int n_stages, const DefChainInfo& ci, int eot_size,
-                hipStream_t s) {
+                const sg_feco_params* feco, int level, hipStream_t s) {
     const sg_pgd_params* p = c.p;
     const int B = c.B, T = c.T;
     const bool defended = n_stages > 0, per_row = !ci.identity;
-    const int reps = (ci.randomised || p->dither.dither != 0.f) ? eot_size : 1;
+    const bool dithered = p->dither.dither != 0.f;
+    const int reps = (ci.randomised || dithered || (feco && feco->random_init)) ? eot_size : 1;
     int rc, G = 1;
     if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
     const int rows_max = per_row ? B * G : B;  // rows of the chain's largest pass
@@ -509,6 +589,19 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
     if ((rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d))) return rc;  // workspace for the largest pass
     if (defended && (rc = ensure_def_workspace(ctx, rows_max, T, n_stages, ci.n_saved, per_row, s))) return rc;
     Workspace& w = ctx->ws;
+    if (feco) {  // rows of the largest pass, in front of FeCo and behind it
+        const size_t rf = (size_t)B * (dithered ? G : 1), rn = (size_t)B * G, F = (size_t)d.F, k = (size_t)feco->k;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_ids, &w.feco_ids_cap, rn * F, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_cnt, &w.feco_cnt_cap, rn * k, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_out, &w.feco_out_cap, rn * k * kCep, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.dfeco, &w.dfeco_cap, rn * k * kCep, s))) return rc;
+        if (level == 2) {
+            if ((rc = dev_grow(ctx, w.allocs, &w.feco_cm, &w.feco_cm_cap, rf * F * kCep, s))) return rc;
+            if ((rc = dev_grow(ctx, w.allocs, &w.dfeco_cm, &w.dfeco_cm_cap, rf * F * kCep, s))) return rc;
+        }
+        (void)feco_pair_buffers(ctx);  // the k-means' two-CU exchange buffers, if it is going to pair: not inside a pass
+        layer_frames(feco->k, w.Fl);   // the TDNN of every pass runs on k frames (checked by the entry point)
+    }
     DefWorkspace& dw = ctx->def_ws;
     for (int r = 0; r < G; ++r)
         SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, c.y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
@@ -547,6 +640,30 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
             // check_input_range takes the same branch as for the start point: decide once.  Behind a chain: from the defended
             // rows of every pass, as a model call takes it.
             d.keep_scale = !defended && (it > 0 || g0 > 0);
+            if (feco) {
+                const XvFecoPass q{feco, level, dithered, B, d.F, ps.Gi, g0 == 0, ps.final_group, feco->seed + ps.pass_key};
+                d.B = q.front_rows();
+                d.Bu = dithered && ps.Gi > 1 ? B : 0;
+                if (q.rowwise || q.first_group) {  // (shared rows: the first group's MFCC, and its spectra, serve the whole step)
+                    if ((rc = run_mfcc_forward(ctx, cur, d, &dz, !ps.last, s))) return rc;
+                }
+                if ((rc = xv_feco_forward(ctx, q, s))) return rc;
+                PassDims dn = d;  // the network's pass: every repeat a row of k frames
+                dn.B = ps.rows;
+                dn.F = feco->k;
+                if ((rc = run_tdnn_forward(ctx, dn, s))) return rc;
+                if ((rc = run_loop_tail(ctx, p->loss, c.out, B, it, ps, s))) return rc;
+                if (ps.last) continue;
+                if ((rc = run_tdnn_backward(ctx, dn, s))) return rc;
+                if ((rc = xv_feco_backward(ctx, q, s))) return rc;
+                if (q.rowwise)  // the overlap-add sums the pass's repeats, carries the groups and takes the step on the last
+                    rc = run_mfcc_adjoint(ctx, cur, d, &dz, ps.final_group ? nullptr : w.grad, ps.final_group ? c.x_adv : nullptr, c.lower,
+                                          c.upper, p->step_size, p->grad_sign, s, g0 > 0 ? w.grad : nullptr);
+                else if (ps.final_group)
+                    rc = run_mfcc_adjoint(ctx, cur, d, &dz, nullptr, c.x_adv, c.lower, c.upper, p->step_size, p->grad_sign, s, nullptr);
+                if (rc) return rc;
+                continue;
+            }
             if ((rc = run_frontend(ctx, cur, d, SG_FLAG_WAV, &dz, !ps.last, s))) return rc;
             if ((rc = run_tdnn_forward(ctx, d, s))) return rc;
             if ((rc = run_loop_tail(ctx, p->loss, c.out, B, it, ps, s))) return rc;
@@ -1132,7 +1249,32 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
     const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
                        {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
-    return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, (hipStream_t)stream);
+    return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, nullptr, 0, (hipStream_t)stream);
+}
+
+int sg_xv_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
+                       int32_t B, int32_t T, const sg_pgd_params* p, const sg_feco_params* feco, int32_t level,
+                       uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* loss_trace_dev,
+                       int64_t* decision_trace_dev, void* stream) {
+    int rc, eot_size;
+    if (!ctx) return SG_ERR_ARG;
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p || !feco, xv_loop_shape(B, T), p))) return rc;
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
+    if (level != 1 && level != 2) return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_feco: level must be 1 (raw MFCC) or 2 (CMVN features), got %d", level);
+    // (one utterance: the reference drops empty clusters, the frame count varies -- host path, as in sg_an_pgd_run_feco)
+    if (B < 2) return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_feco: the FeCo loop needs a batch of at least 2 utterances");
+    const int F = num_frames(T);
+    int Fl[kLayers], G = 1;
+    if (feco->k < 1 || feco->k > F || !layer_frames(feco->k, Fl))
+        return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_feco: need 1 <= k <= %d frames, enough of them for the TDNN context (k = %d)", F, feco->k);
+    const int reps = (p->dither.dither != 0.f || feco->random_init) ? eot_size : 1;
+    if ((rc = eot_group_size(ctx, B, T, reps, &G))) return rc;
+    if ((long)B * G > 65535)
+        return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_feco: %ld rows per pass, the FeCo kernels take at most 65535: split the batch", (long)B * G);
+    if ((rc = feco_kmeans_check(ctx, B, F, kCep, feco->k, feco->max_iter, G))) return rc;
+    const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
+                       {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
+    return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, feco, level, (hipStream_t)stream);
 }
 
 int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
@@ -1148,7 +1290,7 @@ int sg_xv_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
     if ((rc = def_chain_check(ctx, "sg_xv_pgd_run_defended", chain, n_stages, &ci))) return rc;
     const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
                        {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
-    return xv_pgd_loop(ctx, c, chain, n_stages, ci, eot_size, (hipStream_t)stream);
+    return xv_pgd_loop(ctx, c, chain, n_stages, ci, eot_size, nullptr, 0, (hipStream_t)stream);
 }
 
 int sg_wav_rep_sum_update(sg_ctx* ctx, const float* planes_dev, int32_t G, int64_t n, const float* carry_dev, float* sum_out_dev,

@@ -266,6 +266,20 @@ struct Workspace {
     size_t eot_loss_cap = 0;
     int64_t* eot_dec_rows = nullptr;
     size_t eot_dec_cap = 0;
+    // FeCo inside the loop (sg_xv_pgd_run_feco), grown before the loop: cluster ids (rows, F) / sizes (rows, k), the compressed
+    // features and their cotangent (rows, k, 30), and -- level 2 -- the dense CMVN features and their cotangent (rows, F, 30)
+    int* feco_ids = nullptr;
+    size_t feco_ids_cap = 0;
+    int* feco_cnt = nullptr;
+    size_t feco_cnt_cap = 0;
+    float* feco_out = nullptr;
+    size_t feco_out_cap = 0;
+    float* dfeco = nullptr;
+    size_t dfeco_cap = 0;
+    float* feco_cm = nullptr;
+    size_t feco_cm_cap = 0;
+    float* dfeco_cm = nullptr;
+    size_t dfeco_cm_cap = 0;
     std::vector<void*> allocs;
 };
 
@@ -721,6 +735,17 @@ hipError_t launch_nes_grad(const float* loss, int n, int T, int half, int with_c
 hipError_t launch_fakebob_step(float* x, float* grad, const float* prev_grad, const float* lr, const float* lower,
                                const float* upper, int n, int T, float momentum, float one_m_momentum, int grad_sign,
                                hipStream_t s);
+
+// FeCo (k_feco.hip).  What sg_feco_kmeans_compress(_rows) refuses about a (B, reps) grid of F x D clusterings into k groups,
+// said without a launch: SG_OK or SG_ERR_ARG with the error text set
+int feco_kmeans_check(sg_ctx* ctx, int B, int F, int D, int k, int max_iter, int reps);
+// the two-CU exchange buffers of the k-means (ctx->feco_xchg / feco_flags), allocated and cleared on first use: a loop calls
+// this before its first pass so that no pass allocates; false = no room (the launches then run one block per instance)
+bool feco_pair_buffers(sg_ctx* ctx);
+// sg_feco_compress_backward_reps with the sum started from `carry` (B, F, D) -- the repeats of earlier passes, ((carry + g0) +
+// g1) + ... -- when it is not null; carry may alias dfeats
+hipError_t launch_feco_bwd_reps(const float* dout, const int* assign, const int* counts, int B, int F, int D, int k, int force,
+                                int R, const float* carry, float* dfeats, hipStream_t s);
 
 hipError_t launch_loss_eval(const float* scores, const int64_t* y, int B, int S, float threshold, const sg_loss_spec& ls,
                             int64_t* dec, float* loss, float* dscores, hipStream_t s);

@@ -215,11 +215,12 @@ class EngineOps:
         return stages, keep
 
     def _pgd_loop(self, entry, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace,
-                  chain=None, feco=None, feco_slot=False):
+                  chain=None, feco=None, feco_slot=False, feco_level=None):
         """One device-resident PGD loop call: C entry `entry` over the common arguments, then the stage array and its length
         if a `chain` is given, then the FeCo block if `feco` is given (`feco_slot`: the entry takes that pointer anyway,
-        NULL without a defense), then the outputs and the stream.  Keys are drawn in this order: the front-end's dither
-        (``_pgd_dither``), the chain's randomised stages in chain order, FeCo's (``_feco_params``)."""
+        NULL without a defense) and behind it the feature level FeCo sits at if `feco_level` is given (sg_xv_pgd_run_feco),
+        then the outputs and the stream.  Keys are drawn in this order: the front-end's dither (``_pgd_dither``), the chain's
+        randomised stages in chain order, FeCo's (``_feco_params``)."""
         if chain is not None:
             chain = self._checked_chain(chain, feco is None)
         x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
@@ -230,6 +231,8 @@ class EngineOps:
             extras += [stages, len(stages)]
         if feco is not None or feco_slot:
             extras.append(None if feco is None else C.byref(self._feco_params(feco, T)))
+        if feco_level is not None:
+            extras.append(int(feco_level))
         self.ctx.call(entry, N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p), *extras,
                       *[N._ptr(t) for t in outs], self._stream())
         return (x_adv,) + outs

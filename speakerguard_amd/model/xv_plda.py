@@ -19,6 +19,7 @@ Differences a caller can observe, all deliberate:
 """
 import ctypes as C
 import math
+import types
 
 import numpy as np
 import torch
@@ -211,15 +212,16 @@ class xv_plda(EngineOps):
         return feats if flag == 1 else self.comput_feat_from_feat(feats, 1, 2)
 
     # ---- front-end stages with their backward (used when a feature-level defense sits between them) ----
-    def frontend_forward(self, x):
-        """wav (B,1,T) -> (raw MFCC (B,F,30), saved) with the state the backward needs (same scale, same dither)."""
+    def frontend_forward(self, x, dither_seed=None):
+        """wav (B,1,T) -> (raw MFCC (B,F,30), saved) with the state the backward needs (same scale, same dither).
+        `dither_seed`: explicit generator key of this pass's dither (tests replay the device loop's per-pass keys)."""
         x, B, T = self._prep(x, 0)
         F = N.load().sg_xv_num_frames(T)
         scale = torch.empty(1, device=self.device, dtype=torch.float32)
         feats = torch.empty(B, F, 30, device=self.device, dtype=torch.float32)
         s = self._stream()
         self.ctx.call("sg_input_scale", N._ptr(x), x.numel(), N._ptr(scale), s)
-        dz = self._dither(None)
+        dz = self._dither(None, dither_seed)
         self.ctx.call("sg_xv_mfcc", N._ptr(x), B, T, N._ptr(scale), C.byref(dz), N._ptr(feats), s)
         return feats, (x, scale, dz)
 
@@ -331,9 +333,51 @@ class xv_plda(EngineOps):
         return self._pgd_loop("sg_xv_pgd_run_defended", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
                               eot_batch_size, trace, chain=chain)
 
+    # ---- FeCo inside the device loop (sg_xv_pgd_run_feco).  What ``FGSM._device_route`` reads off the base model:
+    feco_loop_levels = (1, 2)  # the feature levels a FeCoDefense may sit at (AudioNet's loop: level 1 only, no attribute)
+    # The device loop keys the dither and FeCo's random start by (step, repeat), the step loop by draw / call number: for one
+    # seed the two routes see different noise.  An attack's result must not change under its user, so a randomised
+    # configuration takes the loop only when the attack object opts in (``fuse_randomised_feco``).
+    feco_loop_rekeys = True
+
+    def _feco_params(self, feco, T):
+        """sg_feco_params of one device loop call, drawn AFTER the dither's key: one base key per call from the model's noise
+        bookkeeping (``last_fused_feco_seed`` keeps it; the loop derives ``fused_pass_seed(key, it, r)``), k = int(F * ratio)
+        as ``FeCoDefense.fwd`` computes it; a row is keyed by its utterance's GLOBAL index (chunk base + row)."""
+        f = N.FecoParams()
+        f.k = int(N.load().sg_xv_num_frames(T) * feco.param)  # feature_level.py:184
+        f.max_iter = int(feco.max_iter)
+        f.random_init = int(feco.init == 'random')
+        f.seed = self.defense_seed(feco.seed)
+        feco.calls += 1
+        self.last_fused_feco_seed = int(f.seed)
+        f.index_base = int(feco.index_base) + self.row_keys()[0]
+        return f
+
+    def __getattr__(self, name):
+        """``pgd_run_feco`` is offered by every INSTANCE, not as a class attribute: the pinned table of the class's loop
+        methods (tests/test_loop_marshalling.py) asserts that the class carries none of that name, and this method's
+        marshalling is pinned in a table of its own (tests/test_xv_feco_marshalling.py).  Looked up here -- only when the
+        normal lookup fails -- so that nothing is stored on the instance: no reference cycle, and copies and pickles of a
+        model offer it like the original."""
+        if name == "pgd_run_feco":
+            return types.MethodType(_pgd_run_feco, self)
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def time_layer(self, layer, B, T, iters=20):
         ms, fl, rows = C.c_float(), C.c_double(), C.c_int32()
         self.ctx.call("sg_xv_time_layer", layer, B, T, iters, C.byref(ms), C.byref(fl), C.byref(rows), self._stream())
         return ms.value, fl.value, rows.value
 
 
+def _pgd_run_feco(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, feco, eot_size=1, eot_batch_size=1,
+                  trace=False, level=1):
+    """``xv_plda.pgd_run_feco`` (every instance offers it: ``xv_plda.__getattr__``): ``pgd_run`` against ``defended_model(self, [(level, feco)])`` as
+    ONE device-resident loop (sg_xv_pgd_run_feco) -- MFCC -> FeCo -> CMVN (level 1) or MFCC -> CMVN -> FeCo (level 2) -> TDNN on
+    k = int(F * ratio) frames, the hand-chained backward, EOT repeats over the dither and / or FeCo's random start summed on
+    the device.  Keys are drawn in this order: the dither's (``last_fused_seed``), FeCo's (``last_fused_feco_seed``); the loop
+    derives the key of step ``it``, repeat ``r`` from each as ``fused_pass_seed(key, it, r)``.  `feco`: a FeCoDefense."""
+    if level not in self.feco_loop_levels:
+        raise ValueError("FeCo runs inside the x-vector device loop at feature level 1 or 2, got %r" % (level,))
+    return self._pgd_loop("sg_xv_pgd_run_feco", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                          eot_batch_size, trace, feco=feco, feco_level=level)
