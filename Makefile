@@ -21,7 +21,7 @@ $(ORACLE_SO): oracle/conv_chain.c
 
 oracle: $(ORACLE_SO)
 
-$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h include/speakerguard_hip.h
+$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h $(CSRC)/k_feco_kmeans.h include/speakerguard_hip.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -40,8 +40,9 @@ ASAN_EXE   := $(ASAN_DIR)/abi_asan_driver
 ASAN_DEF   := $(ASAN_DIR)/defended_asan_driver
 ASAN_AN    := $(ASAN_DIR)/an_defended_asan_driver
 ASAN_XVFECO := $(ASAN_DIR)/xv_feco_asan_driver
+ASAN_FECOCOS := $(ASAN_DIR)/feco_cos_asan_driver
 
-$(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h include/speakerguard_hip.h
+$(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h $(CSRC)/k_feco_kmeans.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -c $< -o $@
 
@@ -62,6 +63,10 @@ $(ASAN_DIR)/an_defended_asan_driver.o: tests/native/an_defended_asan_driver.cpp 
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
 $(ASAN_DIR)/xv_feco_asan_driver.o: tests/native/xv_feco_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
+$(ASAN_DIR)/feco_cos_asan_driver.o: tests/native/feco_cos_asan_driver.cpp include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
@@ -86,11 +91,17 @@ $(ASAN_XVFECO): $(ASAN_EXE) $(ASAN_DIR)/xv_feco_asan_driver.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
 	    $(ASAN_DIR)/xv_feco_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO)
+# ... and the FeCo forward with the distance as an argument (sg_feco_kmeans_compress_metric): a fifth
+$(ASAN_FECOCOS): $(ASAN_EXE) $(ASAN_DIR)/feco_cos_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/feco_cos_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO) $(ASAN_FECOCOS)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_AN)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_XVFECO) > /dev/null
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_FECOCOS)
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

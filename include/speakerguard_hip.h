@@ -456,7 +456,10 @@ int sg_eer_threshold(sg_ctx* ctx, const float* target_dev, int32_t n_target, con
  *   randomised defense that expectation-over-transformation attacks (adaptive_attack/EOT.py) average over.
  * sg_feco_compress: :204-216 given the ids: out (B,k,D) = cluster means, an empty cluster i takes frame i (the
  *   reference's `force` fallback; with B == 1 the reference drops such rows -- the host compacts using counts).
- * sg_feco_compress_backward: the gradient autograd derives for that step. */
+ * sg_feco_compress_backward: the gradient autograd derives for that step.
+ * sg_feco_kmeans_compress_metric: the whole forward under either distance of the reference's kmeans() (:174-182 other_param
+ *   "L2" / "cos"): SG_FECO_L2 is the clustering above, SG_FECO_COS the cosine distance under a contract of its own (k_feco.hip
+ *   header, "cosine").  The gradient depends on the ids only: sg_feco_compress_backward(_reps) serves both. */
 int sg_feco_kmeans(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
                    int32_t* assign_dev, void* stream);
 int sg_feco_kmeans_seeded(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
@@ -488,6 +491,20 @@ int sg_feco_kmeans_compress_rows(sg_ctx* ctx, const float* feats_dev, int32_t B,
                                  int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream);
 int sg_feco_compress_backward(sg_ctx* ctx, const float* dout_dev, const int32_t* assign_dev, const int32_t* counts_dev,
                               int32_t B, int32_t F, int32_t D, int32_t k, int32_t force, float* dfeats_dev, void* stream);
+/* The forward with the distance as an argument.  metric == SG_FECO_L2: sg_feco_kmeans_compress (row_wise 0) or
+ * sg_feco_kmeans_compress_rows (row_wise 1), bit for bit, with their refusals.  metric == SG_FECO_COS: the cosine contract --
+ * raw frames (no centring), unit centroids (a mean divided by sqrtf of its tree-summed squares, a zero mean stays zero: never
+ * NaN), score = the fmaf chain of the L2 contract started at 0.f, largest score wins, ties to the lowest index; initial
+ * frames, keys, index_base, reps and row_wise as in the L2 entries, the same shapes refused, outputs laid out alike and
+ * out / counts equal to sg_feco_compress of the returned ids bit for bit.
+ * SG_ERR_ARG before any launch: a metric other than the two, row_wise outside {0, 1}, whatever the L2 entries refuse.
+ * The device-resident loops (sg_*_pgd_run_feco, sg_*_pgd_run_defended) cluster with L2 only. */
+#define SG_FECO_L2 0
+#define SG_FECO_COS 1
+int sg_feco_kmeans_compress_metric(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
+                                   int32_t max_iter, int32_t metric, int32_t random_init, uint64_t seed, int64_t index_base,
+                                   int32_t reps, int32_t row_wise, int32_t* assign_dev, float* out_dev, int32_t* counts_dev,
+                                   void* stream);
 
 /* FeCo with warped k-means (defense/feature_level.py:53-165 warped_kmeans / wk_compute): the F frames of each row cut into
  * k contiguous segments, the boundaries moved frame by frame while the squared error falls, out (B,k,D) = the final

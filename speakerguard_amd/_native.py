@@ -26,7 +26,7 @@ EXPORTS = (
     "sg_an_logmel_backward", "sg_an_configure", "sg_xv_configure", "sg_xv_enroll_override", "sg_health", "sg_set_streamk", "sg_debug_lose_handoffs", "sg_debug_feco_epoch", "sg_feco_set_two_cu", "sg_trace_begin", "sg_trace_end",
     "sg_wav_defense_forward", "sg_wav_defense_backward", "sg_wav_filter_forward", "sg_wav_filter_backward",
     "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update", "sg_an_pgd_run_defended",
-    "sg_feco_kmeans_compress_rows", "sg_xv_pgd_run_feco",
+    "sg_feco_kmeans_compress_rows", "sg_xv_pgd_run_feco", "sg_feco_kmeans_compress_metric",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -46,6 +46,7 @@ STAGE_NAMES.update({62: "fd_fwd", 63: "fd_bwd"})  # frequency-domain input defen
 STAGE_NAMES.update({64: "def_scale", 65: "def_replicate", 66: "def_rep_sum"})
 # FeCo inside the x-vector device loop (SG_STAGE_XV_FECO_*)
 STAGE_NAMES.update({67: "xv_feco_fwd", 68: "xv_feco_bwd", 69: "xv_feco_cols"})
+SG_FECO_L2, SG_FECO_COS = 0, 1  # sg_feco_kmeans_compress_metric
 SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
 SG_WAV_CHAIN_MAX = 8
 SG_WAV_STAGE_DEFENSE, SG_WAV_STAGE_FILTER = 0, 1
@@ -190,6 +191,8 @@ def load():
         "sg_feco_kmeans_compress": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp]),
         "sg_feco_compress_backward_reps": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "sg_feco_kmeans_compress_rows": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp]),
+        "sg_feco_kmeans_compress_metric": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_int64, i32, i32, vp, vp, vp,
+                                                     vp]),
         "sg_xv_pgd_run_feco": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(FecoParams), i32, vp, vp, vp,
                                          vp, vp, vp, vp]),
         "sg_feco_compress": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -78,7 +78,8 @@ class FGSM(Attack):
             BPDA wrapper, no Python callable -- and exactly what the model applies at level 0 (``flag2defense[0]``);
           * feco: the one entry that is not at level 0, a FeCoDefense at level 1 -- or at another level the base model lists in
             ``feco_loop_levels`` (xv_plda: 2; the route then carries ``level=``), without a chain; needs ``fuse_defended`` and two
-            utterances (one: the reference drops empty clusters, the frame count varies -> host path).
+            utterances (one: the reference drops empty clusters, the frame count varies -> host path).  Only the L2 distance:
+            the loops cluster with L2, a cosine FeCo (``other_param='cos'``) inside one would silently be another defense.
 
         A randomised stage (AT) draws DIFFERENT noise on the two routes for the same seed: the device loop keys a pass by
         (step, repeat), the step loop by the defense's call number.  An attack's result must not change under its user, so such
@@ -107,7 +108,8 @@ class FGSM(Attack):
             if not rest:
                 if chain_ok and (self.fuse_randomised_input_defenses or not randomised):
                     route = 'pgd_run_defended', (chain,)
-            elif len(rest) == 1 and isinstance(rest[0][1], FeCoDefense) and self.fuse_defended and n_audios >= 2:
+            elif (len(rest) == 1 and isinstance(rest[0][1], FeCoDefense) and getattr(rest[0][1], 'other_param', 'L2') == 'L2'
+                  and self.fuse_defended and n_audios >= 2):
                 level, feco = rest[0]
                 noisy = feco.init == 'random' or float(getattr(base, 'dither', 0.0)) != 0.0
                 if getattr(base, 'feco_loop_rekeys', False) and noisy and not self.fuse_randomised_feco:

@@ -1,5 +1,5 @@
 """FeCo feature-level defense on the native engine; mirrors reference defense/feature_level.py:15-50,168-217
-(method 'kmeans', distance 'L2').
+(method 'kmeans', distances 'L2' and 'cos').
 
 ``FeCo(feat, method, param, other_param)`` keeps the reference's function signature (forward only).
 ``FeCoDefense`` is the same transform as an object with ``fwd`` / ``bwd`` so that ``defended_model`` can chain
@@ -16,7 +16,12 @@ index of the chunk's first utterance, call number inside the chunk), like the MF
 and independent of how the batch is cut into per-GPU shards.
 Method 'warped_kmeans' (:53-165) is ``WarpedFeCoDefense`` (and the reference-named ``warped_kmeans`` for one utterance):
 contiguous segments, boundaries moved frame by frame (contract in csrc/k_feco_warped.hip).  It is not reachable through the
-string route ``FeCo(feat, 'warped_kmeans', ...)``, which keeps refusing it.  The cosine distance is not built.
+string route ``FeCo(feat, 'warped_kmeans', ...)``, which keeps refusing it.
+``other_param='cos'`` is the reference's cosine distance (:174-182) under a contract of its own (csrc/k_feco.hip header,
+"cosine": raw frames, unit centroids, largest dot product wins; a zero centroid scores 0 where the reference would give NaN):
+same ``init`` / keys / ``max_iter`` / ``force`` handling, same backward (the gradient depends on the ids only).  Like the
+reference (:183) it asserts an even feature dimension.  It runs under every attack through the step-by-step route; the
+device-resident PGD loops cluster with L2 and refuse it (``FGSM._device_route`` never offers them one).
 """
 import ctypes as C
 
@@ -36,11 +41,12 @@ class FeCoDefense:
     def __init__(self, param=0.5, method='kmeans', other_param='L2', max_iter=10, init='even', seed=0):
         if method != 'kmeans':
             raise NotImplementedError('Currently FEATURE COMPRESSION only supports kmeans on the native engine')
-        if other_param != 'L2':
-            raise NotImplementedError("only the 'L2' distance is built (the reference notes 'cos' works poorly, :178)")
+        if other_param not in ('L2', 'cos'):
+            raise NotImplementedError("other_param must be 'L2' or 'cos' (:174)")
         if init not in ('even', 'random'):
             raise ValueError("init must be 'even' or 'random'")
         self.param, self.max_iter, self.init, self.seed = param, max_iter, init, int(seed)
+        self.other_param = other_param
         self.calls = 0       # fwd calls so far: every call of the randomised defense draws fresh initial frames
         self.index_base = 0  # global index of row 0 (set by sharded callers)
 
@@ -62,6 +68,8 @@ class FeCoDefense:
         if not feat.is_cuda:
             raise N.NativeError("FeCo runs on the HIP device only")
         B, F, D = feat.shape
+        if self.other_param == 'cos':
+            assert D % 2 == 0  # :183 (kmeans_pytorch's cosine distance)
         k = int(F * self.param)  # :184
         ctx, s = _context(feat.device), N.current_stream_ptr(feat.device)
         out = torch.empty(B, k, D, device=feat.device, dtype=torch.float32)
@@ -86,9 +94,14 @@ class FeCoDefense:
                 u = g - rep * rep_rows
                 nb = min(B - b0, rep_rows - u) if rep_rows > 0 else B
                 sl = slice(b0, b0 + nb)
-                ctx.call("sg_feco_kmeans_compress", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, int(self.init == 'random'),
-                         C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF), int(index_base + u), 1,
-                         N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
+                if self.other_param == 'cos':
+                    ctx.call("sg_feco_kmeans_compress_metric", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, N.SG_FECO_COS,
+                             int(self.init == 'random'), C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF),
+                             int(index_base + u), 1, 0, N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
+                else:
+                    ctx.call("sg_feco_kmeans_compress", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, int(self.init == 'random'),
+                             C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF), int(index_base + u), 1,
+                             N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
                 b0 += nb
         force = B > 1  # :33 force=feat.shape[0] > 1
         keep = None

@@ -136,6 +136,9 @@ class audionet_csine(EngineOps):
     def _feco_params(self, feco, T):
         """sg_feco_params of one fused call: one key per call, from the model's noise bookkeeping (attack call, restart, call
         number); the passes inside derive theirs from it; a row is keyed by its utterance's GLOBAL index (chunk base + row)"""
+        if getattr(feco, 'other_param', 'L2') != 'L2':
+            raise N.NativeError("the device loops cluster with the L2 distance only: FeCo with other_param=%r takes the step loop"
+                                % (feco.other_param,))
         f = N.FecoParams()
         f.k = int(N.load().sg_an_num_frames(T) * feco.param)  # feature_level.py:184
         f.max_iter = int(feco.max_iter)

@@ -344,6 +344,9 @@ class xv_plda(EngineOps):
         """sg_feco_params of one device loop call, drawn AFTER the dither's key: one base key per call from the model's noise
         bookkeeping (``last_fused_feco_seed`` keeps it; the loop derives ``fused_pass_seed(key, it, r)``), k = int(F * ratio)
         as ``FeCoDefense.fwd`` computes it; a row is keyed by its utterance's GLOBAL index (chunk base + row)."""
+        if getattr(feco, 'other_param', 'L2') != 'L2':
+            raise N.NativeError("the device loops cluster with the L2 distance only: FeCo with other_param=%r takes the step loop"
+                                % (feco.other_param,))
         f = N.FecoParams()
         f.k = int(N.load().sg_xv_num_frames(T) * feco.param)  # feature_level.py:184
         f.max_iter = int(feco.max_iter)
