@@ -41,6 +41,7 @@ ASAN_DEF   := $(ASAN_DIR)/defended_asan_driver
 ASAN_AN    := $(ASAN_DIR)/an_defended_asan_driver
 ASAN_XVFECO := $(ASAN_DIR)/xv_feco_asan_driver
 ASAN_FECOCOS := $(ASAN_DIR)/feco_cos_asan_driver
+ASAN_DS    := $(ASAN_DIR)/ds_asan_driver
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h $(CSRC)/k_feco_kmeans.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
@@ -70,6 +71,10 @@ $(ASAN_DIR)/feco_cos_asan_driver.o: tests/native/feco_cos_asan_driver.cpp includ
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
+$(ASAN_DIR)/ds_asan_driver.o: tests/native/ds_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
 # (the host objects reference their embedded-code-object symbols even when none is embedded: define them empty)
 $(ASAN_EXE): $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/abi_asan_driver.o
 	nm -u $(ASAN_OBJS) | grep -o '__hip_fatbin_[0-9a-f]*' | sort -u | sed 's/.*/char &[8];/' > $(ASAN_DIR)/fatbin_syms.c
@@ -96,12 +101,18 @@ $(ASAN_FECOCOS): $(ASAN_EXE) $(ASAN_DIR)/feco_cos_asan_driver.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
 	    $(ASAN_DIR)/feco_cos_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO) $(ASAN_FECOCOS)
+# ... and the down-/up-sampling defense's (sg_wav_resample_forward / _backward: spec validation, table cache): a sixth
+$(ASAN_DS): $(ASAN_EXE) $(ASAN_DIR)/ds_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/ds_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO) $(ASAN_FECOCOS) $(ASAN_DS)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_AN)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_XVFECO) > /dev/null
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_FECOCOS)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DS)
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_* and sg_wav_filter_* are (tags 60 .. 63), and so are sg_xv_pgd_run_defended and sg_an_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_*, sg_wav_filter_* and sg_wav_resample_* are (tags 60 .. 63, 70, 71), and so are sg_xv_pgd_run_defended and sg_an_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -405,6 +405,9 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 #define SG_STAGE_XV_FECO_FWD 67
 #define SG_STAGE_XV_FECO_BWD 68
 #define SG_STAGE_XV_FECO_COLS 69
+/* the down-/up-sampling input defense (sg_wav_resample_forward / _backward), traced like the other input defenses */
+#define SG_STAGE_DS_FWD 70
+#define SG_STAGE_DS_BWD 71
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -622,6 +625,43 @@ int sg_wav_filter_forward(sg_ctx* ctx, const sg_wav_filter* f, const float* x_de
                           const float* scale_dev, float* out_dev, int8_t* mask_dev, void* stream);
 int sg_wav_filter_backward(sg_ctx* ctx, const sg_wav_filter* f, const float* g_dev, const int8_t* mask_dev, int32_t B,
                            int32_t T, float* gx_dev, void* stream);
+
+/* ---- the down-/up-sampling input defense (defense/frequency_domain.py DS :8-31) -----------------------------------------
+ * y = Up(Down(x)), truncated to the first T samples when same_size is set; x (B,T), y / g (B,N), gx (B,T) float32 on the
+ * device, one utterance per row.  N is the row length of y: T with same_size, else n_up, where n_low = ceil(T down.out_unit /
+ * down.in_unit) and n_up = ceil(n_low up.out_unit / up.in_unit); the caller passes it and the call refuses another value.
+ * A stage is Kaldi's LinearResample as torchaudio 0.6.0 ports it, handed over as its polyphase tables (HOST pointers, read
+ * during the call): output m = u out_unit + p is the sum over j < W of weight[p * W + j] * in[first[p] + u * in_unit + j], `in`
+ * zero outside its length.  The tables are the caller's (defense.frequency_domain.ds_tables builds them with float32
+ * operations in torchaudio's order); the library keeps a device copy per distinct content in the context (up to 32; past that
+ * the oldest leaves after one stream synchronisation).  A table is uploaded on the stream of its first call -- a call on
+ * another stream must be ordered after that one.  Apart from that both calls are stream-ordered, allocate nothing after a
+ * table's first use and never synchronise.  One launch per direction; the low-rate intermediate never leaves the chip.
+ *   forward   every output one float32 fmaf chain from 0 in ascending tap order.
+ *   backward  gx = Down^T(Up^T(g padded with zeros to n_up)) in gather form: every value one float32 fmaf chain from 0 over
+ *             the outputs whose window holds it, in ascending output index.  No clamp, no mask: the exact adjoint.
+ * (csrc/k_resample.hip header: the contract, zero-padded terms included; restated in tests/ds_restate.py.)
+ * SG_ERR_ARG before any launch: B or T < 1 or T > 2^30, a missing pointer, same_size outside {0, 1}, N not the length above,
+ * a stage with in_unit or out_unit outside 1 .. 1024, W < 1 or out_unit * W > 2048 (the TABLE BOUND: both stages' tables, the
+ * backward's sorted pair lists included, then take at most 48 KB of a block's 64 KB of LDS and leave room for a tile of 2048
+ * samples with its halo and intermediate; a spec whose tables and tile still do not fit is refused as well), |first[p]| >
+ * 2^20, a weight that is not finite, first[0] > 0 (a window that cannot reach its own output). */
+typedef struct sg_resample_stage {
+    int32_t in_unit;      /* fi / gcd(fi, fo) */
+    int32_t out_unit;     /* fo / gcd(fi, fo): the number of phases */
+    int32_t W;            /* taps per phase */
+    const int32_t* first; /* host, (out_unit) */
+    const float* weight;  /* host, (out_unit, W) */
+} sg_resample_stage;
+typedef struct sg_wav_resample {
+    sg_resample_stage down; /* fs -> int(fs * param) */
+    sg_resample_stage up;   /* ... and back */
+    int32_t same_size;
+} sg_wav_resample;
+int sg_wav_resample_forward(sg_ctx* ctx, const sg_wav_resample* r, const float* x_dev, int32_t B, int32_t T, float* out_dev,
+                            int32_t N, void* stream);
+int sg_wav_resample_backward(sg_ctx* ctx, const sg_wav_resample* r, const float* g_dev, int32_t B, int32_t T, int32_t N,
+                             float* gx_dev, void* stream);
 
 /* ---- input-level defenses inside the device-resident x-vector PGD loop ---------------------------------------
  * sg_xv_pgd_run for a model that carries a chain of 1 .. SG_WAV_CHAIN_MAX waveform-level defenses (flag 0, sequential

@@ -27,6 +27,7 @@ EXPORTS = (
     "sg_wav_defense_forward", "sg_wav_defense_backward", "sg_wav_filter_forward", "sg_wav_filter_backward",
     "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update", "sg_an_pgd_run_defended",
     "sg_feco_kmeans_compress_rows", "sg_xv_pgd_run_feco", "sg_feco_kmeans_compress_metric",
+    "sg_wav_resample_forward", "sg_wav_resample_backward",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -46,6 +47,7 @@ STAGE_NAMES.update({62: "fd_fwd", 63: "fd_bwd"})  # frequency-domain input defen
 STAGE_NAMES.update({64: "def_scale", 65: "def_replicate", 66: "def_rep_sum"})
 # FeCo inside the x-vector device loop (SG_STAGE_XV_FECO_*)
 STAGE_NAMES.update({67: "xv_feco_fwd", 68: "xv_feco_bwd", 69: "xv_feco_cols"})
+STAGE_NAMES.update({70: "ds_fwd", 71: "ds_bwd"})  # the down-/up-sampling input defense (SG_STAGE_DS_*)
 SG_FECO_L2, SG_FECO_COS = 0, 1  # sg_feco_kmeans_compress_metric
 SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
 SG_WAV_CHAIN_MAX = 8
@@ -104,6 +106,15 @@ class WavDefense(C.Structure):
 class WavFilter(C.Structure):
     _fields_ = [("n_sections", C.c_int32), ("sos", C.POINTER(C.c_double)), ("clip_mode", C.c_int32), ("bits", C.c_int32),
                 ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
+
+
+class ResampleStage(C.Structure):
+    _fields_ = [("in_unit", C.c_int32), ("out_unit", C.c_int32), ("W", C.c_int32), ("first", C.POINTER(C.c_int32)),
+                ("weight", C.POINTER(C.c_float))]
+
+
+class WavResample(C.Structure):
+    _fields_ = [("down", ResampleStage), ("up", ResampleStage), ("same_size", C.c_int32)]
 
 
 class _WavStageU(C.Union):
@@ -201,6 +212,8 @@ def load():
         "sg_wav_defense_backward": (C.c_int, [vp, C.POINTER(WavDefense), vp, vp, vp, i32, i32, vp, vp]),
         "sg_wav_filter_forward": (C.c_int, [vp, C.POINTER(WavFilter), vp, i32, i32, vp, vp, vp, vp]),
         "sg_wav_filter_backward": (C.c_int, [vp, C.POINTER(WavFilter), vp, vp, i32, i32, vp, vp]),
+        "sg_wav_resample_forward": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),  # (the spec: byref(WavResample))
+        "sg_wav_resample_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -75,7 +75,8 @@ class FGSM(Attack):
         sequential order whose defenses are
 
           * chain: 1 .. 8 native waveform defense objects (defense.time_domain / defense.frequency_domain) as they stand -- no
-            BPDA wrapper, no Python callable -- and exactly what the model applies at level 0 (``flag2defense[0]``);
+            BPDA wrapper, no Python callable -- and exactly what the model applies at level 0 (``flag2defense[0]``); a defense
+            that is no stage of the loops yet (``device_loop`` False: ``DS``) keeps the whole chain on the step loop;
           * feco: the one entry that is not at level 0, a FeCoDefense at level 1 -- or at another level the base model lists in
             ``feco_loop_levels`` (xv_plda: 2; the route then carries ``level=``), without a chain; needs ``fuse_defended`` and two
             utterances (one: the reference drops empty clusters, the frame count varies -> host path).  Only the L2 distance:
@@ -103,6 +104,7 @@ class FGSM(Attack):
             chain = [d for flag, d in defense if flag == 0]
             rest = [(flag, d) for flag, d in defense if flag != 0]
             chain_ok = (self.fuse_input_defenses and 1 <= len(chain) <= 8 and all(isinstance(d, _WavDefense) for d in chain)
+                        and all(getattr(d, 'device_loop', True) for d in chain)
                         and chain == m.flag2defense.get(0, []))  # (what process_sequential applies, in its order)
             randomised = any(getattr(d, 'randomised', False) for d in chain)
             if not rest:

@@ -299,6 +299,9 @@ struct DefWorkspace {
     std::vector<void*> allocs;
 };
 
+// device copies of the resampling defense's tables, keyed by content (k_resample.hip); freed by rs_cache_free
+struct RsCache;
+
 }  // namespace sg
 
 struct sg_ctx {
@@ -314,6 +317,7 @@ struct sg_ctx {
     sg::XvModel xv;
     sg::Workspace ws;
     sg::DefWorkspace def_ws;
+    sg::RsCache* rs_cache = nullptr;
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
@@ -685,6 +689,7 @@ hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, cons
 // k_freq_domain.hip): SG_OK or SG_ERR_ARG with the context's error text set
 int wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d);
 int wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f);
+void rs_cache_free(sg_ctx* ctx);
 
 // ---- the chain of the defended device loops (sg_api.hip), shared by sg_xv_pgd_run_defended and sg_an_pgd_run_defended
 // buffers for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the replicated iterate and the two

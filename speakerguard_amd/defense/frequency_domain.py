@@ -1,5 +1,5 @@
 """Frequency-domain input transformations on the native engine; mirrors reference defense/frequency_domain.py: the
-Butterworth low-pass ``LPF`` (:33-70) and band-pass ``BPF`` (:72-112).  (``DS``, :8-31, is not built: DESIGN.md section 7.)
+down-/up-sampling ``DS`` (:8-31), the Butterworth low-pass ``LPF`` (:33-70) and band-pass ``BPF`` (:72-112).
 
 Like the time-domain classes, the reference's functions become objects whose constructors take the functions' keyword
 parameters (same names, same defaults) and which expose the protocol ``defended_model`` chains at input level 0:
@@ -15,8 +15,17 @@ The reference casts the direct form (b, a) to float32 and filters on the host, o
 float32 direct form is stable the two agree to its coefficient rounding; for the default ``BPF`` it is NOT stable (largest
 pole radius 0.985 in float64, 1.33 after the cast: the reference returns NaN), and this class computes the designed filter.
 The gradient is exact: the anti-causal filter applied to the cotangent masked by the clamp.
+
+``DS`` is two ``torchaudio.transforms.Resample`` calls of torchaudio 0.6.0 -- Kaldi's ``LinearResample``: a polyphase
+evaluation of one Hann-windowed sinc.  torchaudio is not a dependency: ``ds_tables`` restates its table construction (torch
+CPU float32 operations in its order, so the window starts and weights are the ones it would use), and the device runs down-
+sampling, up-sampling and truncation as ONE launch per direction (csrc/k_resample.hip, C-ABI ``sg_wav_resample_forward`` /
+``_backward``), the low-rate signal staying in LDS.  The reference neither clamps the result nor wraps it in BPDA: the
+backward is the exact adjoint, in gather form.  Unpinned by a reference run (none can be made without torchaudio),
+corroborated independently against ``scipy.signal.upfirdn``: DESIGN.md section 2.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -27,6 +36,10 @@ from ..metric.metric import _context
 from .time_domain import _WavDefense
 
 MAX_SECTIONS = 16
+LOWPASS_FILTER_WIDTH = 6   # torchaudio 0.6.0 kaldi.resample_waveform's default
+DS_MAX_TABLE = 2048        # out_unit * W of a stage (sg_wav_resample_*'s table bound)
+DS_MAX_UNIT = 1024
+DS_TILE = 2048             # samples of the result one block owns, in whole units (csrc/k_resample.hip kRsTile)
 
 
 class _Butterworth(_WavDefense):
@@ -123,3 +136,111 @@ class BPF(_Butterworth):
 
     def _edges(self):
         return [2 * w / self.fs for w in self.wp], [2 * w / self.fs for w in self.param]
+
+
+def _ds_first_f64(fi, fo, out_unit, w):
+    """the window starts of ``ds_tables`` in float64 (the guard's second opinion)"""
+    t = np.arange(out_unit, dtype=np.float64) / fo
+    return np.ceil((t - w) * fi).astype(np.int64)
+
+
+def ds_tables(fi, fo):
+    """Polyphase tables of one ``Resample(fi -> fo)`` of torchaudio 0.6.0 (kaldi.resample_waveform, its
+    ``_get_LR_indices_and_weights``, lowpass_filter_width 6) -> dict(in_unit, out_unit, W, first int32 (out_unit,), weight
+    float32 (out_unit, W)).  Pure, host only.  The arithmetic is torch CPU float32, operation for operation in torchaudio's
+    order -- float64 tables move the composite by 1.5e-7 .. 3e-6.  ``first`` is also computed in float64: a float32 product
+    that lands on an integer the float64 one misses would select another window silently, so a disagreement raises."""
+    fi, fo = int(fi), int(fo)
+    if fi < 1 or fo < 1:
+        raise ValueError("the sample rates must be positive, got %d -> %d" % (fi, fo))
+    g = math.gcd(fi, fo)
+    in_unit, out_unit = fi // g, fo // g
+    cutoff = 0.99 * 0.5 * min(fi, fo)
+    w = LOWPASS_FILTER_WIDTH / (2 * cutoff)
+    t = torch.arange(0., out_unit) / fo
+    min_t = t - w
+    max_t = t + w
+    first = torch.ceil(min_t * fi)
+    last = torch.floor(max_t * fi)
+    W = int((last - first + 1).max())
+    idx = first.unsqueeze(1) + torch.arange(W).unsqueeze(0)
+    delta = (idx / fi) - t.unsqueeze(1)
+    weight = torch.zeros_like(delta)
+    inside = delta.abs().lt(w)
+    weight[inside] = 0.5 * (1 + torch.cos(2 * math.pi * cutoff / LOWPASS_FILTER_WIDTH * delta[inside]))
+    zero = delta.eq(0.0)
+    weight[~zero] *= torch.sin(2 * math.pi * cutoff * delta[~zero]) / (math.pi * delta[~zero])
+    weight[zero] *= 2 * cutoff
+    weight /= fi
+    first = first.to(torch.int64).numpy()
+    first64 = _ds_first_f64(fi, fo, out_unit, w)
+    if not np.array_equal(first, first64):
+        p = int(np.nonzero(first != first64)[0][0])
+        raise ValueError("resampling %d -> %d: the float32 window start of phase %d (%d) is not the float64 one (%d)"
+                         % (fi, fo, p, first[p], first64[p]))
+    return dict(in_unit=in_unit, out_unit=out_unit, W=W, first=np.ascontiguousarray(first, np.int32),
+                weight=np.ascontiguousarray(weight.numpy(), np.float32))
+
+
+def ds_out_len(n, tab):
+    """samples a stage returns for n: ceil(n out_unit / in_unit) (torchaudio's tick arithmetic, simplified)"""
+    return -((-int(n) * tab["out_unit"]) // tab["in_unit"])
+
+
+def check_ds_tables(tab):
+    """what sg_wav_resample_* refuse about a stage's tables, said at construction"""
+    if not (1 <= tab["in_unit"] <= DS_MAX_UNIT and 1 <= tab["out_unit"] <= DS_MAX_UNIT) or tab["out_unit"] * tab["W"] > DS_MAX_TABLE:
+        raise ValueError("tables of up to %d entries with units up to %d are built, this ratio needs %d x %d taps on units %d -> %d"
+                         % (DS_MAX_TABLE, DS_MAX_UNIT, tab["out_unit"], tab["W"], tab["in_unit"], tab["out_unit"]))
+    if not np.isfinite(tab["weight"]).all() or tab["first"][0] > 0:
+        raise ValueError("the tables hold a non-finite weight or a window that cannot reach its output")
+
+
+class DS(_WavDefense):
+    """Down-sampling to ``int(fs * param)`` Hz and up-sampling back (:8-31), truncated to the input's length when
+    ``same_size``; otherwise the up-sampler's own length, as in the reference (odd lengths come back one sample longer).  No
+    clamp: white noise of amplitude 1 comes out at up to 1.34.  Backward: the exact adjoint."""
+    device_loop = False  # not yet a stage of the device-resident loops: FGSM._device_route keeps such a chain on the step loop
+
+    def __init__(self, param=0.5, fs=16000, same_size=True):
+        super().__init__(param, same_size)
+        self.fs, self.new_freq = int(fs), int(fs * param)
+        self.down, self.up = ds_tables(self.fs, self.new_freq), ds_tables(self.new_freq, self.fs)
+        for tab in (self.down, self.up):
+            check_ds_tables(tab)
+        self._spec = N.WavResample()
+        for st, tab in ((self._spec.down, self.down), (self._spec.up, self.up)):  # (self.down / .up keep the arrays alive)
+            st.in_unit, st.out_unit, st.W = tab["in_unit"], tab["out_unit"], tab["W"]
+            st.first = tab["first"].ctypes.data_as(C.POINTER(C.c_int32))
+            st.weight = tab["weight"].ctypes.data_as(C.POINTER(C.c_float))
+        self._spec.same_size = 1 if same_size else 0
+
+    @property
+    def tile(self):
+        """output samples one block of the forward kernel owns"""
+        return max(1, DS_TILE // self.up["out_unit"]) * self.up["out_unit"]
+
+    def out_len(self, T):
+        return int(T) if self.same_size else ds_out_len(ds_out_len(T, self.down), self.up)
+
+    def stage(self):
+        raise NotImplementedError("DS is not a stage of the device-resident loops")
+
+    def fwd(self, audio):
+        x, shape = self._rows(audio)
+        n = self.out_len(x.shape[1])
+        out = torch.empty(x.shape[0], n, device=x.device, dtype=torch.float32)
+        _context(x.device).call("sg_wav_resample_forward", C.byref(self._spec), N._ptr(x), x.shape[0], x.shape[1], N._ptr(out), n,
+                                N.current_stream_ptr(x.device))
+        out_shape = tuple(shape[:-1]) + (n,)
+        return out.view(out_shape), (tuple(x.shape), shape, out_shape)
+
+    def bwd(self, saved, g):
+        rows, shape, out_shape = saved
+        if tuple(g.shape) != tuple(out_shape):
+            raise ValueError("the cotangent must have the forward's shape")
+        g, _ = self._rows(g)
+        gx = torch.empty(rows, device=g.device, dtype=torch.float32)
+        _context(g.device).call("sg_wav_resample_backward", C.byref(self._spec), N._ptr(g), rows[0], rows[1], g.shape[1], N._ptr(gx),
+                                N.current_stream_ptr(g.device))
+        return gx.view(shape)
