@@ -42,6 +42,7 @@ ASAN_AN    := $(ASAN_DIR)/an_defended_asan_driver
 ASAN_XVFECO := $(ASAN_DIR)/xv_feco_asan_driver
 ASAN_FECOCOS := $(ASAN_DIR)/feco_cos_asan_driver
 ASAN_DS    := $(ASAN_DIR)/ds_asan_driver
+ASAN_SP    := $(ASAN_DIR)/spectrum_asan_driver
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(CSRC)/sg_internal.h $(CSRC)/fft512.h $(CSRC)/fft512t.h $(CSRC)/loss_device.h $(CSRC)/k_feco_kmeans.h include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
@@ -72,6 +73,10 @@ $(ASAN_DIR)/feco_cos_asan_driver.o: tests/native/feco_cos_asan_driver.cpp includ
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
 $(ASAN_DIR)/ds_asan_driver.o: tests/native/ds_asan_driver.cpp include/speakerguard_hip.h
+	@mkdir -p $(ASAN_DIR)
+	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
+
+$(ASAN_DIR)/spectrum_asan_driver.o: tests/native/spectrum_asan_driver.cpp include/speakerguard_hip.h
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(ASAN_FLAGS) -x hip -c $< -o $@
 
@@ -106,13 +111,19 @@ $(ASAN_DS): $(ASAN_EXE) $(ASAN_DIR)/ds_asan_driver.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
 	    $(ASAN_DIR)/ds_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
 
-asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO) $(ASAN_FECOCOS) $(ASAN_DS)
+# ... and the spectrum gate's (sg_wav_spectrum / sg_wav_spectrum_gate: refusals, plan, table builder and cache, workspace): a seventh
+$(ASAN_SP): $(ASAN_EXE) $(ASAN_DIR)/spectrum_asan_driver.o
+	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o \
+	    $(ASAN_DIR)/spectrum_asan_driver.o $(ASAN_DIR)/fatbin_syms.o
+
+asan: $(ASAN_EXE) $(ASAN_DEF) $(ASAN_AN) $(ASAN_XVFECO) $(ASAN_FECOCOS) $(ASAN_DS) $(ASAN_SP)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_EXE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DEF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_AN)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_XVFECO) > /dev/null
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_FECOCOS)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_DS)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $(ASAN_SP)
 
 clean:
 	rm -rf build $(LIB) $(ORACLE_SO)

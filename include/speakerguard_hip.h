@@ -663,6 +663,38 @@ int sg_wav_resample_forward(sg_ctx* ctx, const sg_wav_resample* r, const float* 
 int sg_wav_resample_backward(sg_ctx* ctx, const sg_wav_resample* r, const float* g_dev, int32_t B, int32_t T, int32_t N,
                              float* gx_dev, void* stream);
 
+/* ---- the whole-utterance spectrum gate (attack/_kenan_fft.py fft_compression :57-82, the peak of :198) ---------------------
+ * X = rfft(x) over each row of x (B,T) float32 on the device, T EVEN and 2 <= T <= 2^22 (the reference's own gate breaks on an
+ * odd T: its irfft returns T - 1 samples); spec (B, T/2+1, 2) float32 as (re, im) pairs, peak (B) float32, factor (B) float32,
+ * out (B,T) float32, keep (B, T/2+1) bytes 0 / 1, kept (B) int32, all on the device, rows contiguous.
+ *   sg_wav_spectrum        spec = X and / or peak[b] = max_k |X[b,k]| (either may be NULL, not both).
+ *   sg_wav_spectrum_gate   keep[b,k] = !(|X[b,k]| < factor[b]); out = irfft(X where keep, else 0), scaled by the float32 1 / T;
+ *                          kept[b] = the row sum of keep.  keep_dev and kept_dev may be NULL.
+ * |X| = sqrtf(re * re + im * im) in float32 without fused multiply-add, and the comparison is STRICT: a bin whose magnitude
+ * equals the factor stays.  It follows from the comparison that a factor that is NaN, negative or zero keeps every bin, and that
+ * a bin whose magnitude is NaN stays.  DC and Nyquist have a zero imaginary part and are gated on their real value.
+ * One launch per call, one workgroup per utterance: forward transform, magnitudes, peak, gate and inverse run inside it, and a
+ * row's bits depend on T alone, not on B or on the row's place in the call.  The transform is a complex Stockham network of
+ * length T / 2 (radices 4, 2, 3, 5) with the real post-pass when T / 2 = 2^a 3^b 5^c, and Bluestein's convolution over a
+ * power-of-two network otherwise; twiddles, chirp and transformed chirp are built on the host in float64, rounded once, and kept
+ * on the device per distinct T in the context (up to 16; past that the oldest leaves after one stream synchronisation).  A table
+ * is uploaded on the stream of its first call -- a call on another stream must be ordered after that one.  Lengths whose two
+ * buffers do not fit a workgroup's 160 KB of LDS (a network longer than 10224 points: T = 48000) run through a workspace in the
+ * context, B x 2 x network length complex values, grown (one stream synchronisation) when a call needs more than any before.
+ * Apart from those two first-use cases both calls are stream-ordered, never synchronise and allocate nothing after the first
+ * call at a given (B,T).  The workspace makes the calls of ONE context on DIFFERENT streams unsafe to overlap.
+ * out_dev may not alias x_dev (the call refuses the same pointer; overlapping rows are the caller's to avoid): the rows are read
+ * by other waves than those that write them.
+ * A table costs 6 T bytes on the host and on the device for such a smooth T and up to 38 T bytes otherwise (a non-smooth T near
+ * 2^22: ~90 MB each, and a float64 FFT of 2^22 points on the host at its first call); the host copy lives as long as the entry.
+ * (csrc/k_spectrum.hip header: the network and its arithmetic; restated in tests/kenan_restate.py, which the GPU suite holds the
+ * kernel to value for value.)
+ * SG_ERR_ARG before any launch: ctx NULL, x_dev / factor_dev / out_dev NULL, both outputs of sg_wav_spectrum NULL, B < 1, T odd
+ * or outside 2 .. 2^22, out_dev == x_dev. */
+int sg_wav_spectrum(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, float* spec_dev, float* peak_dev, void* stream);
+int sg_wav_spectrum_gate(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, const float* factor_dev, float* out_dev,
+                         uint8_t* keep_dev, int32_t* kept_dev, void* stream);
+
 /* ---- input-level defenses inside the device-resident x-vector PGD loop ---------------------------------------
  * sg_xv_pgd_run for a model that carries a chain of 1 .. SG_WAV_CHAIN_MAX waveform-level defenses (flag 0, sequential
  * order), applied in chain order to the waveform before the MFCC.  A stage is one sg_wav_defense or one sg_wav_filter,

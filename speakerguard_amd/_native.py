@@ -28,6 +28,7 @@ EXPORTS = (
     "sg_xv_pgd_run_defended", "sg_wav_rep_sum_update", "sg_an_pgd_run_defended",
     "sg_feco_kmeans_compress_rows", "sg_xv_pgd_run_feco", "sg_feco_kmeans_compress_metric",
     "sg_wav_resample_forward", "sg_wav_resample_backward",
+    "sg_wav_spectrum", "sg_wav_spectrum_gate",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -214,6 +215,8 @@ def load():
         "sg_wav_filter_backward": (C.c_int, [vp, C.POINTER(WavFilter), vp, vp, i32, i32, vp, vp]),
         "sg_wav_resample_forward": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),  # (the spec: byref(WavResample))
         "sg_wav_resample_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        "sg_wav_spectrum": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
+        "sg_wav_spectrum_gate": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -851,6 +851,7 @@ void sg_destroy(sg_ctx* ctx) {
     free_pool(ctx->ws.allocs);
     free_pool(ctx->def_ws.allocs);
     rs_cache_free(ctx);
+    sp_cache_free(ctx);
     free_pool(ctx->an_ws.allocs);  // (leaked until round 4: found by the sanitizer build's leak check, `make asan`)
     free_pool(ctx->xv.allocs);
     free_pool(ctx->model_allocs);

@@ -301,6 +301,8 @@ struct DefWorkspace {
 
 // device copies of the resampling defense's tables, keyed by content (k_resample.hip); freed by rs_cache_free
 struct RsCache;
+// the spectrum gate's per-T tables and its workspace (k_spectrum.hip); freed by sp_cache_free
+struct SpCache;
 
 }  // namespace sg
 
@@ -318,6 +320,7 @@ struct sg_ctx {
     sg::Workspace ws;
     sg::DefWorkspace def_ws;
     sg::RsCache* rs_cache = nullptr;
+    sg::SpCache* sp_cache = nullptr;
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
@@ -690,6 +693,7 @@ hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, cons
 int wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d);
 int wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f);
 void rs_cache_free(sg_ctx* ctx);
+void sp_cache_free(sg_ctx* ctx);
 
 // ---- the chain of the defended device loops (sg_api.hip), shared by sg_xv_pgd_run_defended and sg_an_pgd_run_defended
 // buffers for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the replicated iterate and the two
