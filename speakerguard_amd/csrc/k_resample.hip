@@ -274,31 +274,10 @@ void rs_build_stage(const sg_resample_stage& st, RsStageGeo* g, std::vector<int3
     bwd->resize(rs_pad4((int)bwd->size()));
 }
 
-struct RsEntry {
-    std::vector<int32_t> key;   // the spec's content: units, W, first and weight bits of both stages
-    std::vector<int32_t> blob;  // what the device copy holds (kept: the upload is asynchronous)
-    int32_t* dev = nullptr;
+struct RsEntry : DevTable {  // key: the spec's content -- units, W, first and weight bits of both stages
     RsGeo geo{};
     size_t lds_fwd = 0, lds_bwd = 0;
 };
-
-}  // namespace
-
-struct sg::RsCache {
-    std::vector<RsEntry*> entries;  // oldest first
-};
-
-void sg::rs_cache_free(sg_ctx* ctx) {
-    if (!ctx->rs_cache) return;
-    for (RsEntry* e : ctx->rs_cache->entries) {
-        if (e->dev) (void)hipFree(e->dev);
-        delete e;
-    }
-    delete ctx->rs_cache;
-    ctx->rs_cache = nullptr;
-}
-
-namespace {
 
 void rs_key_stage(const sg_resample_stage& st, std::vector<int32_t>* key) {
     key->push_back(st.in_unit), key->push_back(st.out_unit), key->push_back(st.W);
@@ -313,10 +292,7 @@ int rs_tables(sg_ctx* ctx, const char* who, const sg_wav_resample* r, hipStream_
     std::vector<int32_t> key;
     rs_key_stage(r->down, &key);
     rs_key_stage(r->up, &key);
-    if (!ctx->rs_cache) ctx->rs_cache = new RsCache();
-    std::vector<RsEntry*>& all = ctx->rs_cache->entries;
-    for (RsEntry* e : all)
-        if (e->key == key) return *out = e, SG_OK;
+    if (DevTable* hit = ctx->rs_cache.find(key)) return *out = static_cast<RsEntry*>(hit), SG_OK;
 
     RsEntry* e = new RsEntry();
     e->key.swap(key);
@@ -325,8 +301,9 @@ int rs_tables(sg_ctx* ctx, const char* who, const sg_wav_resample* r, hipStream_
     rs_build_stage(r->down, &g.d, &fwd, &bwd);
     rs_build_stage(r->up, &g.u, &fwd, &bwd);
     g.fwd_words = (int)fwd.size(), g.bwd_off = g.fwd_words, g.bwd_words = (int)bwd.size();
-    e->blob = fwd;
-    e->blob.insert(e->blob.end(), bwd.begin(), bwd.end());
+    fwd.insert(fwd.end(), bwd.begin(), bwd.end());
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(fwd.data());
+    e->blob.assign(bytes, bytes + fwd.size() * sizeof(int32_t));
     g.UT = std::max(1, kRsTile / g.u.ou), g.VT = std::max(1, kRsTile / g.d.iu);
     // the largest tiles any block stages (the kernels' own formulas, bounded over the tile's position)
     g.f_low_max = (g.UT - 1) * g.u.iu + g.u.span;
@@ -341,26 +318,7 @@ int rs_tables(sg_ctx* ctx, const char* who, const sg_wav_resample* r, hipStream_
         return fail(ctx, SG_ERR_ARG, "%s: tables and tile need %zu (forward) / %zu (backward) bytes of LDS, a block has %zu", who, f, b,
                     kRsLdsBytes);
     }
-    void* dev = nullptr;
-    if (hipMalloc(&dev, e->blob.size() * sizeof(int32_t)) != hipSuccess) {
-        delete e;
-        return fail(ctx, SG_ERR_HIP, "%s: no device memory for the tables", who);
-    }
-    e->dev = static_cast<int32_t*>(dev);
-    bool ok = hipMemcpyAsync(e->dev, e->blob.data(), e->blob.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
-    // a full cache: the oldest table leaves once nothing enqueued can still read it (the one case that waits for the stream)
-    if (ok && all.size() >= kRsCacheMax) ok = hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) {
-        (void)hipFree(e->dev);
-        delete e;
-        return fail(ctx, SG_ERR_HIP, "%s: the upload of the tables failed", who);
-    }
-    if (all.size() >= kRsCacheMax) {
-        (void)hipFree(all.front()->dev);
-        delete all.front();
-        all.erase(all.begin());
-    }
-    all.push_back(e);
+    if (int rc = dev_tables_insert(ctx, who, "", &ctx->rs_cache, kRsCacheMax, e, s)) return rc;
     return *out = e, SG_OK;
 }
 

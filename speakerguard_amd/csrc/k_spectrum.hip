@@ -120,10 +120,8 @@ void sp_fft64(std::vector<double>& re, std::vector<double>& im) {  // in place, 
     }
 }
 
-void sp_build_tables(const SpPlan& p, std::vector<float2>* blob) {
+void sp_build_tables(const SpPlan& p, float2* t) {  // t: p.words values, zeroed
     const double pi = 3.14159265358979323846;
-    blob->assign((size_t)p.words, make_float2(0.f, 0.f));
-    float2* t = blob->data();
     for (int j = 0; j < p.N; ++j) {
         const double a = 2 * pi * (double)j / (double)p.N;
         t[p.o_tw + j] = make_float2((float)std::cos(a), (float)-std::sin(a));
@@ -332,64 +330,23 @@ sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float2* spec,
     }
 }
 
-// ---------------------------------------------------------------- per-T tables and the workspace, kept in the context
-struct SpEntry {
+// ---------------------------------------------------------------- per-T tables, kept in the context
+struct SpEntry : DevTable {  // key: T
     SpPlan plan{};
-    std::vector<float2> blob;  // what the device copy holds (kept: the upload is asynchronous)
-    float2* dev = nullptr;
 };
-
-}  // namespace
-
-struct sg::SpCache {
-    std::vector<SpEntry*> entries;  // oldest first
-    float2* ws = nullptr;           // [rows][2][N] of the largest call so far that did not fit LDS
-    size_t ws_cap = 0;
-    std::vector<void*> pool;
-    bool lds_opted = false;
-};
-
-void sg::sp_cache_free(sg_ctx* ctx) {
-    if (!ctx->sp_cache) return;
-    for (SpEntry* e : ctx->sp_cache->entries) {
-        if (e->dev) (void)hipFree(e->dev);
-        delete e;
-    }
-    for (void* q : ctx->sp_cache->pool) (void)hipFree(q);
-    delete ctx->sp_cache;
-    ctx->sp_cache = nullptr;
-}
-
-namespace {
 
 // T's tables on the device: found, or built and uploaded on `s` (first use of T only)
 int sp_tables(sg_ctx* ctx, const char* who, const SpPlan& plan, hipStream_t s, SpEntry** out) {
-    std::vector<SpEntry*>& all = ctx->sp_cache->entries;
-    for (SpEntry* e : all)
-        if (e->plan.T == plan.T) return *out = e, SG_OK;
+    const std::vector<int32_t> key{plan.T};
+    if (DevTable* hit = ctx->sp_cache.find(key)) return *out = static_cast<SpEntry*>(hit), SG_OK;
     SpEntry* e = new SpEntry();
+    e->key = key;
     e->plan = plan;
-    sp_build_tables(plan, &e->blob);
-    void* dev = nullptr;
-    if (hipMalloc(&dev, e->blob.size() * sizeof(float2)) != hipSuccess) {
-        delete e;
-        return fail(ctx, SG_ERR_HIP, "%s: no device memory for the tables of T = %d", who, plan.T);
-    }
-    e->dev = static_cast<float2*>(dev);
-    bool ok = hipMemcpyAsync(e->dev, e->blob.data(), e->blob.size() * sizeof(float2), hipMemcpyHostToDevice, s) == hipSuccess;
-    // a full cache: the oldest table leaves once nothing enqueued can still read it (the one case that waits for the stream)
-    if (ok && all.size() >= kSpCacheMax) ok = hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) {
-        (void)hipFree(e->dev);
-        delete e;
-        return fail(ctx, SG_ERR_HIP, "%s: the upload of the tables failed", who);
-    }
-    if (all.size() >= kSpCacheMax) {
-        (void)hipFree(all.front()->dev);
-        delete all.front();
-        all.erase(all.begin());
-    }
-    all.push_back(e);
+    e->blob.resize((size_t)plan.words * sizeof(float2));
+    sp_build_tables(plan, reinterpret_cast<float2*>(e->blob.data()));
+    char of[32];
+    snprintf(of, sizeof(of), " of T = %d", plan.T);
+    if (int rc = dev_tables_insert(ctx, who, of, &ctx->sp_cache, kSpCacheMax, e, s)) return rc;
     return *out = e, SG_OK;
 }
 
@@ -399,25 +356,23 @@ int sp_run(sg_ctx* ctx, const char* who, const float* x_dev, int32_t B, int32_t 
     if (B < 1 || !sp_make_plan(T, &plan))
         return fail(ctx, SG_ERR_ARG, "%s: need B >= 1 and an even T in 2 .. %d (B %d, T %d)", who, kSpMaxLen, B, T);
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!ctx->sp_cache) ctx->sp_cache = new SpCache();
-    SpCache* c = ctx->sp_cache;
     SpEntry* e = nullptr;
     if (int rc = sp_tables(ctx, who, plan, s, &e)) return rc;
     const bool lds = sp_in_lds(plan);
     size_t dyn = 0;
     if (lds) {
         dyn = (size_t)plan.N * 2 * sizeof(float2);
-        if (!c->lds_opted) {
+        if (!ctx->sp_lds_opted) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(kSpLdsBytes - kSpLdsStatic)) != hipSuccess)
                 return fail(ctx, SG_ERR_HIP, "%s: a workgroup cannot take %zu bytes of LDS on this device", who, kSpLdsBytes);
-            c->lds_opted = true;
+            ctx->sp_lds_opted = true;
         }
     } else {
-        if (int rc = dev_grow(ctx, c->pool, &c->ws, &c->ws_cap, (size_t)B * 2 * (size_t)plan.N, s)) return rc;
+        if (int rc = dev_grow(ctx, ctx->model_allocs, &ctx->sp_ws, (size_t)B * 2 * (size_t)plan.N, s)) return rc;
     }
     auto kernel = lds ? sp_kernel<true> : sp_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kSpThreads), dyn, s, e->plan, (const float2*)e->dev, x_dev, c->ws,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kSpThreads), dyn, s, e->plan, (const float2*)e->dev, x_dev, ctx->sp_ws.ptr,
                        reinterpret_cast<float2*>(spec), peak, factor, out, keep, kept);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s: %s", who, hipGetErrorString(err));

@@ -467,8 +467,8 @@ int run_loop_tail(sg_ctx* ctx, const sg_loss_spec& loss, const LoopOut& o, int B
     // rows, the grouped rows are grown before the loop
     float* lrec = o.loss_trace ? o.loss_trace + (size_t)it * B : nullptr;
     int64_t* drec = o.decision_trace ? o.decision_trace + (size_t)it * B : nullptr;
-    t.loss_trace = loop_record_rows(ps, lrec, w.loss, w.eot_loss_rows);
-    t.decision_trace = loop_record_rows(ps, drec, w.decisions, w.eot_dec_rows);
+    t.loss_trace = loop_record_rows(ps, lrec, w.loss, w.eot_loss_rows.ptr);
+    t.decision_trace = loop_record_rows(ps, drec, w.decisions, w.eot_dec_rows.ptr);
     t.coef_rows = B;  // SG_LOSS_LINEAR: the caller's (B, S) table serves every repeat of an utterance
     SG_STAGE(SG_STAGE_TAIL, launch_tail(t, s));
     if (ps.reduce) {
@@ -591,13 +591,13 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
     Workspace& w = ctx->ws;
     if (feco) {  // rows of the largest pass, in front of FeCo and behind it
         const size_t rf = (size_t)B * (dithered ? G : 1), rn = (size_t)B * G, F = (size_t)d.F, k = (size_t)feco->k;
-        if ((rc = dev_grow(ctx, w.allocs, &w.feco_ids, &w.feco_ids_cap, rn * F, s))) return rc;
-        if ((rc = dev_grow(ctx, w.allocs, &w.feco_cnt, &w.feco_cnt_cap, rn * k, s))) return rc;
-        if ((rc = dev_grow(ctx, w.allocs, &w.feco_out, &w.feco_out_cap, rn * k * kCep, s))) return rc;
-        if ((rc = dev_grow(ctx, w.allocs, &w.dfeco, &w.dfeco_cap, rn * k * kCep, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_ids, rn * F, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_cnt, rn * k, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.feco_out, rn * k * kCep, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.dfeco, rn * k * kCep, s))) return rc;
         if (level == 2) {
-            if ((rc = dev_grow(ctx, w.allocs, &w.feco_cm, &w.feco_cm_cap, rf * F * kCep, s))) return rc;
-            if ((rc = dev_grow(ctx, w.allocs, &w.dfeco_cm, &w.dfeco_cm_cap, rf * F * kCep, s))) return rc;
+            if ((rc = dev_grow(ctx, w.allocs, &w.feco_cm, rf * F * kCep, s))) return rc;
+            if ((rc = dev_grow(ctx, w.allocs, &w.dfeco_cm, rf * F * kCep, s))) return rc;
         }
         (void)feco_pair_buffers(ctx);  // the k-means' two-CU exchange buffers, if it is going to pair: not inside a pass
         layer_frames(feco->k, w.Fl);   // the TDNN of every pass runs on k frames (checked by the entry point)
@@ -607,8 +607,8 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
         SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, c.y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     const bool want_rec = c.out.loss_trace || c.out.decision_trace;
     if (want_rec && G < reps) {  // LoopPass::GROUPED: every pass of a step leaves its rows here
-        if ((rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, &w.eot_loss_cap, (size_t)reps * B, s))) return rc;
-        if ((rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, &w.eot_dec_cap, (size_t)reps * B, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, (size_t)reps * B, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, (size_t)reps * B, s))) return rc;
     }
     const size_t n = (size_t)B * T;
     // the iterate is clamped into [lower, upper] within [-1, 1] at every step: a first stage's own decision is taken once
@@ -850,8 +850,8 @@ void sg_destroy(sg_ctx* ctx) {
     (void)hipDeviceSynchronize();
     free_pool(ctx->ws.allocs);
     free_pool(ctx->def_ws.allocs);
-    rs_cache_free(ctx);
-    sp_cache_free(ctx);
+    ctx->rs_cache.clear();
+    ctx->sp_cache.clear();
     free_pool(ctx->an_ws.allocs);  // (leaked until round 4: found by the sanitizer build's leak check, `make asan`)
     free_pool(ctx->xv.allocs);
     free_pool(ctx->model_allocs);

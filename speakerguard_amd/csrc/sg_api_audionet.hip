@@ -484,15 +484,10 @@ int an_frontend_backward(sg_ctx* ctx, const float* x, const AnDims& d, const flo
 }
 
 // the buffer the fused overlap-add steps into (null: the separate pair updates in place)
-float* an_step_target(sg_ctx* ctx, const AnDims& d) {
+float* an_step_target(sg_ctx* ctx, const AnDims& d, hipStream_t s) {
     AnWorkspace& w = ctx->an_ws;
     if (!an_use_ola(ctx, d.B, d.F)) return nullptr;
-    if (!w.x_alt) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)w.B * w.T * sizeof(float)) != hipSuccess) return nullptr;  // falls back to the separate pair
-        w.allocs.push_back(p);
-        w.x_alt = static_cast<float*>(p);
-    }
+    if (dev_grow(ctx, w.allocs, &w.x_alt, (size_t)w.B * w.T, s)) return nullptr;  // falls back to the separate pair
     return w.x_alt;
 }
 
@@ -539,7 +534,7 @@ int an_pgd_loop(sg_ctx* ctx, const AnLoopCall& c, AnDims d, bool identity, int r
     const bool want_rec = c.loss_trace || c.decision_trace;
     d.B = B;
     float* xc = c.x_adv;
-    float* xn = identity ? an_step_target(ctx, d) : nullptr;
+    float* xn = identity ? an_step_target(ctx, d, s) : nullptr;
     if (!xn) xn = c.x_adv;
     int rc;
     for (int it = 0; it <= p->max_iter; ++it) {
@@ -579,8 +574,8 @@ int an_pgd_loop(sg_ctx* ctx, const AnLoopCall& c, AnDims d, bool identity, int r
             // per-step records (LoopPass::Records): a pass of several repeats reduces its rows right after the head, the groups of
             // a step after the last one
             const AnHeadArgs head = an_head_args(ctx, c.y, p->loss, c.coef_rows, nullptr, ps.last ? c.scores : nullptr, ps.last ? c.decisions : nullptr,
-                                                 ps.last ? c.loss : nullptr, loop_record_rows(ps, lrec, w.trace_l, w.eot_loss_rows),
-                                                 loop_record_rows(ps, drec, w.trace_d, w.eot_dec_rows), ps.last ? c.success : nullptr);
+                                                 ps.last ? c.loss : nullptr, loop_record_rows(ps, lrec, w.trace_l, w.eot_loss_rows.ptr),
+                                                 loop_record_rows(ps, drec, w.trace_d, w.eot_dec_rows.ptr), ps.last ? c.success : nullptr);
             const AnEotRecords reduce = {ps.nrep, B, lrec, drec};
             const AnNetPlan& plan = ps.last ? final_plan : (ps.Gi == cap ? full_plan : tail_plan);
             rc = an_net_step(ctx, plan, net_in, ps.rows, head, ps.rec == LoopPass::PASS ? &reduce : nullptr, ps.last ? nullptr : dnet, s);
@@ -887,9 +882,9 @@ int sg_an_pgd_run_defended(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, 
     AnWorkspace& w = ctx->an_ws;
     if (G < reps) {  // the repeats of a step run as several passes: the carried sum, and the rows of LoopPass::GROUPED
         const bool want_rec = loss_trace_dev || decision_trace_dev;
-        if ((rc = dev_grow(ctx, w.allocs, &w.grad_carry, &w.grad_carry_cap, (size_t)B * T, s))) return rc;
-        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, &w.eot_loss_cap, (size_t)reps * B, s))) return rc;
-        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, &w.eot_dec_cap, (size_t)reps * B, s))) return rc;
+        if ((rc = dev_grow(ctx, w.allocs, &w.grad_carry, (size_t)B * T, s))) return rc;
+        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_loss_rows, (size_t)reps * B, s))) return rc;
+        if (want_rec && (rc = dev_grow(ctx, w.allocs, &w.eot_dec_rows, (size_t)reps * B, s))) return rc;
     }
     for (int r = 0; r < (feco ? R : G); ++r)
         SG_HIP(hipMemcpyAsync(w.y_rep + (size_t)r * B, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));

@@ -44,6 +44,14 @@ constexpr int kL1BwdSplitK = 10;       // tdnn1 data gradient: two K-slabs per t
 
 inline int num_frames(int T) { return (T + kShift / 2) / kShift; }
 
+// a device buffer that is grown on demand (dev_grow): the pointer and the elements it has room for; reads as the pointer
+template <typename T>
+struct DevBuf {
+    T* ptr = nullptr;
+    size_t cap = 0;
+    operator T*() const { return ptr; }
+};
+
 // ---------------------------------------------------------------- AudioNet CSI-NE (model/audionet_csine.py)
 constexpr int kAnFft = 1024, kAnHop = 160, kAnWin = 800, kAnMel = 32, kAnBins = 513;  // Preprocessor.py:13-23
 constexpr int kAnConv = 7;                                                              // conv2 .. conv8
@@ -156,15 +164,12 @@ struct AnWorkspace {
     float2* spec_cache = nullptr;  // (B, F, 512) packed spectra of the forward pass (allocated on first use, grown on demand)
     size_t spec_cache_bytes = 0;
     bool spec_cache_refused = false;  // an allocation failed once: the passes run without the cache
-    float* x_alt = nullptr;      // (B, T) the other half of the waveform ping-pong of the fused overlap-add update (on demand)
+    DevBuf<float> x_alt;         // (B, T) the other half of the waveform ping-pong of the fused overlap-add update (on demand)
     // the defended loop (sg_an_pgd_run_defended) when a step's EOT repeats run as several passes: the cotangent sum carried
     // from group to group, and the per-repeat records the last group reduces (both on demand, before the loop)
-    float* grad_carry = nullptr;     // (n) floats, n = utterances x T of the call
-    size_t grad_carry_cap = 0;
-    float* eot_loss_rows = nullptr;  // (reps * utterances)
-    size_t eot_loss_cap = 0;
-    int64_t* eot_dec_rows = nullptr;
-    size_t eot_dec_cap = 0;
+    DevBuf<float> grad_carry;        // (n) floats, n = utterances x T of the call
+    DevBuf<float> eot_loss_rows;     // (reps * utterances)
+    DevBuf<int64_t> eot_dec_rows;
     // which input the mel cache belongs to (sg_an_logmel_backward(reuse_forward) checks pointer and shape, not contents)
     const float* cache_x = nullptr;
     int cache_B = 0, cache_T = 0;
@@ -262,24 +267,12 @@ struct Workspace {
     int64_t* decisions = nullptr;      // [B]
     float* grad = nullptr;             // [B][T]
     int64_t* y_rep = nullptr;          // [B] labels repeated for EOT repeats batched into one pass
-    float* eot_loss_rows = nullptr;    // [reps * B] per-repeat records of a step whose repeats run as several passes
-    size_t eot_loss_cap = 0;
-    int64_t* eot_dec_rows = nullptr;
-    size_t eot_dec_cap = 0;
+    DevBuf<float> eot_loss_rows;       // [reps * B] per-repeat records of a step whose repeats run as several passes
+    DevBuf<int64_t> eot_dec_rows;
     // FeCo inside the loop (sg_xv_pgd_run_feco), grown before the loop: cluster ids (rows, F) / sizes (rows, k), the compressed
     // features and their cotangent (rows, k, 30), and -- level 2 -- the dense CMVN features and their cotangent (rows, F, 30)
-    int* feco_ids = nullptr;
-    size_t feco_ids_cap = 0;
-    int* feco_cnt = nullptr;
-    size_t feco_cnt_cap = 0;
-    float* feco_out = nullptr;
-    size_t feco_out_cap = 0;
-    float* dfeco = nullptr;
-    size_t dfeco_cap = 0;
-    float* feco_cm = nullptr;
-    size_t feco_cm_cap = 0;
-    float* dfeco_cm = nullptr;
-    size_t dfeco_cm_cap = 0;
+    DevBuf<int> feco_ids, feco_cnt;
+    DevBuf<float> feco_out, dfeco, feco_cm, dfeco_cm;
     std::vector<void*> allocs;
 };
 
@@ -299,10 +292,29 @@ struct DefWorkspace {
     std::vector<void*> allocs;
 };
 
-// device copies of the resampling defense's tables, keyed by content (k_resample.hip); freed by rs_cache_free
-struct RsCache;
-// the spectrum gate's per-T tables and its workspace (k_spectrum.hip); freed by sp_cache_free
-struct SpCache;
+// Tables on the device, found by key, else built by the caller and uploaded (dev_tables_insert).  An entry keeps the host
+// bytes beside their device copy for as long as that lives: the upload is asynchronous, from pageable memory.  What a user
+// keeps beside them -- geometry, a plan -- it adds by deriving from DevTable.
+struct DevTable {
+    std::vector<int32_t> key;
+    std::vector<unsigned char> blob;  // what the device copy holds
+    void* dev = nullptr;
+    virtual ~DevTable() {
+        if (dev) (void)hipFree(dev);
+    }
+};
+struct DevTableCache {
+    std::vector<DevTable*> entries;  // oldest first; a hit does not move an entry
+    DevTable* find(const std::vector<int32_t>& key) const {
+        for (DevTable* e : entries)
+            if (e->key == key) return e;
+        return nullptr;
+    }
+    void clear() {
+        for (DevTable* e : entries) delete e;
+        entries.clear();
+    }
+};
 
 }  // namespace sg
 
@@ -319,8 +331,10 @@ struct sg_ctx {
     sg::XvModel xv;
     sg::Workspace ws;
     sg::DefWorkspace def_ws;
-    sg::RsCache* rs_cache = nullptr;
-    sg::SpCache* sp_cache = nullptr;
+    sg::DevTableCache rs_cache;      // the resampling defense's tables, keyed by content (k_resample.hip)
+    sg::DevTableCache sp_cache;      // the spectrum gate's, keyed by T (k_spectrum.hip) ...
+    sg::DevBuf<float2> sp_ws;        // ... its workspace (in model_allocs): [rows][2][N] of the largest call that did not fit LDS ...
+    bool sp_lds_opted = false;       // ... and its > 64 KB dynamic-LDS opt-in
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
@@ -417,18 +431,42 @@ int dev_upload(sg_ctx* ctx, std::vector<void*>& pool, T** out, const std::vector
 // an on-demand workspace buffer of at least `need` elements, grown before a loop: the old one is released once the stream
 // has drained (nothing enqueued still uses it), not left in the pool until sg_destroy
 template <typename T>
-int dev_grow(sg_ctx* ctx, std::vector<void*>& pool, T** buf, size_t* cap, size_t need, hipStream_t s) {
-    if (*buf && *cap >= need) return SG_OK;
-    if (*buf) {
+int dev_grow(sg_ctx* ctx, std::vector<void*>& pool, DevBuf<T>* buf, size_t need, hipStream_t s) {
+    if (buf->ptr && buf->cap >= need) return SG_OK;
+    if (buf->ptr) {
         SG_HIP(hipStreamSynchronize(s));
-        (void)hipFree(*buf);
-        pool.erase(std::remove(pool.begin(), pool.end(), static_cast<void*>(*buf)), pool.end());
-        *buf = nullptr;
-        *cap = 0;
+        (void)hipFree(buf->ptr);
+        pool.erase(std::remove(pool.begin(), pool.end(), static_cast<void*>(buf->ptr)), pool.end());
+        *buf = DevBuf<T>();
     }
-    int rc = dev_alloc(ctx, pool, buf, need);
+    int rc = dev_alloc(ctx, pool, &buf->ptr, need);
     if (rc) return rc;
-    *cap = need;
+    buf->cap = need;
+    return SG_OK;
+}
+// A new entry (key and blob filled in; the cache owns it from here on) goes to the device on `s` and into `cache`, which holds
+// `cap` entries: when it is full, the oldest leaves once nothing enqueued can still read it -- the upload is enqueued first,
+// then the stream is waited for, the one case that waits.  On any failure the entry and its device memory are released.  `of`
+// ends the text of a refusal for lack of memory.
+inline int dev_tables_insert(sg_ctx* ctx, const char* who, const char* of, DevTableCache* cache, size_t cap, DevTable* e,
+                             hipStream_t s) {
+    std::vector<DevTable*>& all = cache->entries;
+    if (hipMalloc(&e->dev, e->blob.size()) != hipSuccess) {
+        e->dev = nullptr;
+        delete e;
+        return fail(ctx, SG_ERR_HIP, "%s: no device memory for the tables%s", who, of);
+    }
+    bool ok = hipMemcpyAsync(e->dev, e->blob.data(), e->blob.size(), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok && all.size() >= cap) ok = hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+        delete e;
+        return fail(ctx, SG_ERR_HIP, "%s: the upload of the tables failed", who);
+    }
+    if (all.size() >= cap) {
+        delete all.front();
+        all.erase(all.begin());
+    }
+    all.push_back(e);
     return SG_OK;
 }
 
@@ -692,8 +730,6 @@ hipError_t launch_wav_rep_sum_update(const float* planes, int G, int64_t n, cons
 // k_freq_domain.hip): SG_OK or SG_ERR_ARG with the context's error text set
 int wav_defense_check_spec(sg_ctx* ctx, const char* who, const sg_wav_defense* d);
 int wav_filter_check_spec(sg_ctx* ctx, const char* who, const sg_wav_filter* f);
-void rs_cache_free(sg_ctx* ctx);
-void sp_cache_free(sg_ctx* ctx);
 
 // ---- the chain of the defended device loops (sg_api.hip), shared by sg_xv_pgd_run_defended and sg_an_pgd_run_defended
 // buffers for passes of `rows` x T: n_out stage outputs, n_saved int8 planes, and -- `rep` -- the replicated iterate and the two

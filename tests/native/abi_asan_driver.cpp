@@ -19,97 +19,17 @@
 // without dither, EOT repeats as one pass, as full groups and with a tail group, sg_xv_pgd_run_defended and
 // sg_an_pgd_run_defended over identity, per-row, randomised and FeCo chains.  Every launch form of a loop gives the same bits
 // too.  Recorded in tests/native/loop_launch_sequence.expected (tests/test_loop_launch_sequence.py).
-#include <cxxabi.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "speakerguard_hip.h"
+#include "driver_common.h"
 #include "../../speakerguard_amd/csrc/sg_internal.h"  // ConvGemmArgs: the launch table reads the first kernel argument
-
-extern "C" long hipdouble_launches();
-extern "C" long hipdouble_live_allocs();
-extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-static std::vector<float> rnd(size_t n, unsigned seed, float scale = 0.1f, float shift = 0.f) {
-    std::vector<float> v(n);
-    unsigned s = seed * 2654435761u + 12345u;
-    for (size_t i = 0; i < n; ++i) {
-        s = s * 1664525u + 1013904223u;
-        v[i] = shift + scale * ((float)(s >> 8) / 8388608.0f - 1.0f);
-    }
-    return v;
-}
-
-struct XvModel {
-    std::vector<float> w[5], b[5], mean[5], var[5], fc1w, fc1b, emean, lda, pmean, ptrans, ppsi, enroll;
-    sg_xv_weights desc{};
-    XvModel(int D, int S) {
-        const int cin[5] = {30, 512, 512, 512, 512}, cout[5] = {512, 512, 512, 512, 1500}, k[5] = {5, 5, 7, 1, 1};
-        for (int l = 0; l < 5; ++l) {
-            w[l] = rnd((size_t)cout[l] * cin[l] * k[l], 10 + l);
-            b[l] = rnd(cout[l], 20 + l);
-            mean[l] = rnd(cout[l], 30 + l);
-            var[l] = rnd(cout[l], 40 + l, 0.5f, 1.0f);
-            desc.tdnn_weight[l] = w[l].data(); desc.tdnn_bias[l] = b[l].data();
-            desc.bn_mean[l] = mean[l].data(); desc.bn_var[l] = var[l].data();
-        }
-        fc1w = rnd((size_t)512 * 3000, 1); fc1b = rnd(512, 2); emean = rnd(512, 3); lda = rnd((size_t)D * 513, 4);
-        pmean = rnd(D, 5); ptrans = rnd((size_t)D * D, 6); ppsi = rnd(D, 7, 0.5f, 1.0f); enroll = rnd((size_t)S * D, 8);
-        desc.fc1_weight = fc1w.data(); desc.fc1_bias = fc1b.data(); desc.emb_mean = emean.data(); desc.lda = lda.data();
-        desc.plda_mean = pmean.data(); desc.plda_transform = ptrans.data(); desc.plda_psi = ppsi.data(); desc.enroll = enroll.data();
-        desc.D = D; desc.S = S; desc.bn_eps = 1e-5f; desc.threshold = -INFINITY;
-    }
-};
-
-struct AnModel {
-    std::vector<float> c1w, c1b, bn1[4], cw[7], cb[7], g[7], be[7], mu[7], va[7], fcw, fcb;
-    sg_an_weights desc{};
-    explicit AnModel(int S) {
-        const int cin[7] = {32, 64, 128, 128, 128, 128, 64}, cout[7] = {64, 128, 128, 128, 128, 64, 32};
-        c1w = rnd(25, 50); c1b = rnd(1, 51);
-        for (int i = 0; i < 4; ++i) { bn1[i] = rnd(1, 52 + i, 0.1f, i == 3 || i == 0 ? 1.f : 0.f); desc.bn1[i] = bn1[i].data(); }
-        desc.conv1_weight = c1w.data(); desc.conv1_bias = c1b.data();
-        for (int l = 0; l < 7; ++l) {
-            cw[l] = rnd((size_t)cout[l] * cin[l] * 3, 60 + l); cb[l] = rnd(cout[l], 70 + l); g[l] = rnd(cout[l], 80 + l, 0.1f, 1.f);
-            be[l] = rnd(cout[l], 90 + l); mu[l] = rnd(cout[l], 100 + l); va[l] = rnd(cout[l], 110 + l, 0.3f, 1.f);
-            desc.conv_weight[l] = cw[l].data(); desc.conv_bias[l] = cb[l].data(); desc.bn_weight[l] = g[l].data();
-            desc.bn_bias[l] = be[l].data(); desc.bn_mean[l] = mu[l].data(); desc.bn_var[l] = va[l].data();
-        }
-        fcw = rnd((size_t)S * 32, 120); fcb = rnd(S, 121);
-        desc.fc_weight = fcw.data(); desc.fc_bias = fcb.data(); desc.num_class = S; desc.bn_eps = 1e-5f;
-    }
-};
 
 // ---- the launch table ------------------------------------------------------------------------------------------
 static std::string g_case;                 // label of the call being walked: every line carries it
 static int g_epi = -1;                     // its epilogue
 static std::vector<std::string> g_lines;   // the conv_gemm* launches it made
 
-static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void** args) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    std::string name = dm ? dm : mangled;
-    std::free(dm);
-    name = name.substr(0, name.find('('));  // "void sg::conv_gemm_q_kernel<1, 2>"
-    const size_t at = name.find("conv_gemm");
-    if (at == std::string::npos) return;
-    name = name.substr(at);
-    name.erase(std::remove(name.begin(), name.end(), ' '), name.end());  // one token: "conv_gemm_q_kernel<1,2>"
+static void conv_launch(const Launch& l, void** args) {
+    std::string name = kernel_name(l.name);  // one token: "conv_gemm_q_kernel<1,2>"
+    if (name.find("conv_gemm") != 0) return;
     // the template argument that is the epilogue (the last one of conv_gemm_kernel, the first one of the others) is printed as
     // E where it is the epilogue asked for, so that the three epilogues of a case can share a line; a wrong one stays a number
     const size_t e = name.find("conv_gemm_kernel<") == 0 ? name.size() - 2 : name.find('<') + 1;
@@ -122,7 +42,7 @@ static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shm
     for (int i = 1; i <= n_scalars; ++i) scalars += (i > 1 ? "," : "") + std::to_string(*static_cast<const int*>(args[i]));
     char line[256];
     std::snprintf(line, sizeof(line), "%s grid=%u,%u,%u block=%u lds=%zu Wq=%d a_bytes=%u w_bytes=%u sk_xcd=%d ablate=%d trace=%d args=%s",
-                  name.c_str(), grid.x, grid.y, grid.z, block.x, shmem, a.Wq != nullptr, a.a_bytes, a.w_bytes, a.sk_xcd, a.ablate,
+                  name.c_str(), l.grid.x, l.grid.y, l.grid.z, l.block.x, l.lds, a.Wq != nullptr, a.a_bytes, a.w_bytes, a.sk_xcd, a.ablate,
                   a.trace != nullptr, scalars.c_str());
     g_lines.push_back(line);
 }
@@ -169,6 +89,7 @@ static void walk_conv(sg_ctx* ctx, const ConvShape& c, int kernel_lo, int kernel
 // kernels at the eleven shapes where tests/test_gpu_conv.py forces them, with / without the models
 static int launch_table(const std::string& mode) {
     setenv("SG_TUNE", "1", 1);  // the knobs of the caller's environment count
+    g_on_launch = conv_launch;
     hipdouble_set_launch_hook(record_launch);
     sg_ctx* ctx = nullptr;
     if (sg_create(0, &ctx) != SG_OK) return 1;
@@ -234,28 +155,9 @@ static int launch_table(const std::string& mode) {
 static std::string g_an_label;
 static int g_an_n = 0;
 
-// "void sg::(anonymous namespace)::k<1, (sg::E)2>(args)" -> "k<1,(E)2>"
-static std::string kernel_name(const char* mangled) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    std::string name = dm ? dm : mangled;
-    std::free(dm);
-    for (const char* drop : {"(anonymous namespace)::", "sg::", "void "})
-        for (size_t at; (at = name.find(drop)) != std::string::npos;) name.erase(at, std::strlen(drop));
-    int depth = 0;
-    for (size_t i = 0; i < name.size(); ++i) {  // the parameter list opens at template depth 0
-        depth += name[i] == '<' ? 1 : name[i] == '>' ? -1 : 0;
-        if (name[i] == '(' && depth == 0) { name.resize(i); break; }
-    }
-    name.erase(std::remove(name.begin(), name.end(), ' '), name.end());
-    return name;
-}
-
-static void record_an_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void** args) {
-    const std::string name = kernel_name(mangled);
-    std::printf("%s #%d | %s grid=%u,%u,%u block=%u lds=%zu", g_an_label.c_str(), ++g_an_n, name.c_str(), grid.x, grid.y, grid.z,
-                block.x * block.y * block.z, shmem);
-    if (name.find("an_cnn_") == 0) {
+static void an_launch(const Launch& launch, void** args) {
+    print_launch(g_an_label, ++g_an_n, launch);
+    if (kernel_name(launch.name).find("an_cnn_") == 0) {
         const sg::AnFusedArgs& a = *static_cast<const sg::AnFusedArgs*>(args[0]);
         std::printf(" S=%d buf_floats=%d Fnet=%d head=%d Tin=", a.S, a.buf_floats, a.Fnet, a.head.on);
         for (int l = 0; l < sg::kAnConv; ++l) std::printf("%s%d", l ? "," : "", a.Tin[l]);
@@ -309,7 +211,8 @@ static void walk_an_feco(sg_ctx* ctx, AnBuffers& b, int k, bool random_eot2, boo
 // One context per shape: the workspace keeps the largest batch and the longest utterance it has seen, and the two extremes
 // below together would not fit the sanitizer build.
 static int an_sequence(bool configure) {
-    hipdouble_set_launch_hook(record_an_launch);
+    g_on_launch = an_launch;
+    hipdouble_set_launch_hook(record_launch);
     const int Sa = 11;
     AnModel an(Sa);
     // (B, T): three small / odd shapes, the benchmark's, a batch at which the planner cuts S = 1 by itself, and an utterance of
@@ -346,15 +249,6 @@ static int an_sequence(bool configure) {
 }
 
 // ---- the device loops' launch sequence ----------------------------------------------------------------------------
-static sg_wav_stage td(int kind, float param) {
-    sg_wav_stage st{};
-    st.tag = SG_WAV_STAGE_DEFENSE;
-    st.u.defense.kind = kind;
-    st.u.defense.param = param;
-    st.u.defense.seed = 17;
-    return st;
-}
-
 // SG_EOT_MAX_ROWS is read at every call (behind SG_TUNE=1): 0 = unset
 static void eot_max_rows(int rows) {
     if (rows > 0) setenv("SG_EOT_MAX_ROWS", std::to_string(rows).c_str(), 1);
@@ -364,12 +258,11 @@ static void eot_max_rows(int rows) {
 static int loop_sequence() {
     setenv("SG_TUNE", "1", 1);
     unsetenv("SG_EOT_MAX_ROWS");
-    hipdouble_set_launch_hook(record_an_launch);
+    g_on_launch = an_launch;
+    hipdouble_set_launch_hook(record_launch);
     const int K = 2;
-    const double sos[2][6] = {{0.2, 0.4, 0.2, 1.0, -0.3, 0.1}, {1.0, 2.0, 1.0, 1.0, -0.2, 0.3}};
-    sg_wav_stage lpf{};
-    lpf.tag = SG_WAV_STAGE_FILTER;
-    lpf.u.filter.n_sections = 2; lpf.u.filter.sos = &sos[0][0]; lpf.u.filter.clip_mode = SG_FD_CLIP_RANGE; lpf.u.filter.bits = 16;
+    const sg_wav_stage lpf = lpf_stage();
+    const auto td = [](int kind, float param) { return ::td(kind, param, 17); };
     const sg_wav_stage qt = td(SG_TD_QT, 512.f), bdr = td(SG_TD_QT, 256.f) /* BDR to 8 of 16 bits */, ms = td(SG_TD_MS, 3.f), at = td(SG_TD_AT, 25.f);
     const sg_wav_stage qt_bdr[2] = {qt, bdr}, qt_ms_lpf[3] = {qt, ms, lpf}, lpf_qt[2] = {lpf, qt};
     const sg_wav_stage eight[SG_WAV_CHAIN_MAX] = {td(SG_TD_MS, 5.f), td(SG_TD_AS, 31.f), td(SG_TD_QT, 256.f), lpf, at, td(SG_TD_QT, 128.f), ms, lpf};

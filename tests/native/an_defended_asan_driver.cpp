@@ -2,71 +2,14 @@
 // defended_asan_driver.cpp): walks sg_an_pgd_run_defended -- refusals before any launch, workspace growth, the stage / key /
 // buffer bookkeeping of every pass, repeat groups with a carried sum, the chain in front of FeCo -- under AddressSanitizer +
 // UBSan.  "Device" buffers are host buffers sized exactly as the header says.  No kernel runs.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-static std::vector<float> rnd(size_t n, unsigned seed, float scale = 0.1f, float shift = 0.f) {
-    std::vector<float> v(n);
-    unsigned s = seed * 2654435761u + 12345u;
-    for (size_t i = 0; i < n; ++i) {
-        s = s * 1664525u + 1013904223u;
-        v[i] = shift + scale * ((float)(s >> 8) / 8388608.0f - 1.0f);
-    }
-    return v;
-}
-
-struct AnModel {
-    std::vector<float> c1w, c1b, bn1[4], cw[7], cb[7], g[7], be[7], mu[7], va[7], fcw, fcb;
-    sg_an_weights desc{};
-    explicit AnModel(int S) {
-        const int cin[7] = {32, 64, 128, 128, 128, 128, 64}, cout[7] = {64, 128, 128, 128, 128, 64, 32};
-        c1w = rnd(25, 50); c1b = rnd(1, 51);
-        for (int i = 0; i < 4; ++i) { bn1[i] = rnd(1, 52 + i, 0.1f, i == 3 || i == 0 ? 1.f : 0.f); desc.bn1[i] = bn1[i].data(); }
-        desc.conv1_weight = c1w.data(); desc.conv1_bias = c1b.data();
-        for (int l = 0; l < 7; ++l) {
-            cw[l] = rnd((size_t)cout[l] * cin[l] * 3, 60 + l); cb[l] = rnd(cout[l], 70 + l); g[l] = rnd(cout[l], 80 + l, 0.1f, 1.f);
-            be[l] = rnd(cout[l], 90 + l); mu[l] = rnd(cout[l], 100 + l); va[l] = rnd(cout[l], 110 + l, 0.3f, 1.f);
-            desc.conv_weight[l] = cw[l].data(); desc.conv_bias[l] = cb[l].data(); desc.bn_weight[l] = g[l].data();
-            desc.bn_bias[l] = be[l].data(); desc.bn_mean[l] = mu[l].data(); desc.bn_var[l] = va[l].data();
-        }
-        fcw = rnd((size_t)S * 32, 120); fcb = rnd(S, 121);
-        desc.fc_weight = fcw.data(); desc.fc_bias = fcb.data(); desc.num_class = S; desc.bn_eps = 1e-5f;
-    }
-};
-
-static sg_wav_stage td(int kind, float param) {
-    sg_wav_stage st{};
-    st.tag = SG_WAV_STAGE_DEFENSE;
-    st.u.defense.kind = kind;
-    st.u.defense.param = param;
-    return st;
-}
+#include "driver_common.h"
 
 int main() {
     setenv("SG_TUNE", "1", 1);
     const int B = 3, K = 2;
     std::vector<int64_t> y(B, 1), dec(B);
     std::vector<uint8_t> succ(B);
-    const double sos[2][6] = {{0.2, 0.4, 0.2, 1.0, -0.3, 0.1}, {1.0, 2.0, 1.0, 1.0, -0.2, 0.3}};
-    sg_wav_stage lpf{};
-    lpf.tag = SG_WAV_STAGE_FILTER;
-    lpf.u.filter.n_sections = 2; lpf.u.filter.sos = &sos[0][0]; lpf.u.filter.clip_mode = SG_FD_CLIP_RANGE; lpf.u.filter.bits = 16;
+    const sg_wav_stage lpf = lpf_stage();
     sg_wav_stage one = td(SG_TD_AS, 3.f), bad = one;
     std::vector<sg_wav_stage> nine(SG_WAV_CHAIN_MAX + 1, one);
     sg_wav_stage qt2[2] = {td(SG_TD_QT, 128.f), td(SG_TD_QT, 256.f)};

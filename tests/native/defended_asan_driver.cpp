@@ -3,63 +3,7 @@
 // stage / key / buffer bookkeeping of every pass -- under AddressSanitizer + UBSan.  "Device" buffers are host buffers
 // sized exactly as the header says; the double's copies are real, so a replicated iterate or a label copy past an extent is
 // an ASan error here.  No kernel runs.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-static std::vector<float> rnd(size_t n, unsigned seed, float scale = 0.1f, float shift = 0.f) {
-    std::vector<float> v(n);
-    unsigned s = seed * 2654435761u + 12345u;
-    for (size_t i = 0; i < n; ++i) {
-        s = s * 1664525u + 1013904223u;
-        v[i] = shift + scale * ((float)(s >> 8) / 8388608.0f - 1.0f);
-    }
-    return v;
-}
-
-struct XvModel {
-    std::vector<float> w[5], b[5], mean[5], var[5], fc1w, fc1b, emean, lda, pmean, ptrans, ppsi, enroll;
-    sg_xv_weights desc{};
-    XvModel(int D, int S) {
-        const int cin[5] = {30, 512, 512, 512, 512}, cout[5] = {512, 512, 512, 512, 1500}, k[5] = {5, 5, 7, 1, 1};
-        for (int l = 0; l < 5; ++l) {
-            w[l] = rnd((size_t)cout[l] * cin[l] * k[l], 10 + l);
-            b[l] = rnd(cout[l], 20 + l);
-            mean[l] = rnd(cout[l], 30 + l);
-            var[l] = rnd(cout[l], 40 + l, 0.5f, 1.0f);
-            desc.tdnn_weight[l] = w[l].data(); desc.tdnn_bias[l] = b[l].data();
-            desc.bn_mean[l] = mean[l].data(); desc.bn_var[l] = var[l].data();
-        }
-        fc1w = rnd((size_t)512 * 3000, 1); fc1b = rnd(512, 2); emean = rnd(512, 3); lda = rnd((size_t)D * 513, 4);
-        pmean = rnd(D, 5); ptrans = rnd((size_t)D * D, 6); ppsi = rnd(D, 7, 0.5f, 1.0f); enroll = rnd((size_t)S * D, 8);
-        desc.fc1_weight = fc1w.data(); desc.fc1_bias = fc1b.data(); desc.emb_mean = emean.data(); desc.lda = lda.data();
-        desc.plda_mean = pmean.data(); desc.plda_transform = ptrans.data(); desc.plda_psi = ppsi.data(); desc.enroll = enroll.data();
-        desc.D = D; desc.S = S; desc.bn_eps = 1e-5f; desc.threshold = -INFINITY;
-    }
-};
-
-static sg_wav_stage td(int kind, float param) {
-    sg_wav_stage st{};
-    st.tag = SG_WAV_STAGE_DEFENSE;
-    st.u.defense.kind = kind;
-    st.u.defense.param = param;
-    return st;
-}
+#include "driver_common.h"
 
 int main() {
     setenv("SG_TUNE", "1", 1);
@@ -74,11 +18,8 @@ int main() {
     std::vector<uint8_t> succ(B);
     sg_pgd_params pp{};
     pp.step_size = 4e-4f; pp.max_iter = K; pp.grad_sign = 1; pp.eot_size = 4; pp.eot_batch_size = 2;
-    const double sos[2][6] = {{0.2, 0.4, 0.2, 1.0, -0.3, 0.1}, {1.0, 2.0, 1.0, 1.0, -0.2, 0.3}};
     const double bad_sos[1][6] = {{1.0, 0.0, 0.0, 1.0, -2.5, 1.0}};
-    sg_wav_stage lpf{};
-    lpf.tag = SG_WAV_STAGE_FILTER;
-    lpf.u.filter.n_sections = 2; lpf.u.filter.sos = &sos[0][0]; lpf.u.filter.clip_mode = SG_FD_CLIP_RANGE; lpf.u.filter.bits = 16;
+    const sg_wav_stage lpf = lpf_stage();
     auto run = [&](const sg_wav_stage* chain, int n, bool trace) {
         return sg_xv_pgd_run_defended(ctx, x.data(), y.data(), lower.data(), upper.data(), B, T, &pp, chain, n, succ.data(), dec.data(),
                                       scores.data(), loss.data(), trace ? ltr.data() : nullptr, trace ? dtr.data() : nullptr, nullptr);

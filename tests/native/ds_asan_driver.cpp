@@ -3,46 +3,9 @@
 // the table builder (the backward's sorted pair lists included) for ratios 1:2, 3:10 and 33:100, the content-keyed table cache
 // (a hit allocates nothing, 32 tables stay, the 33rd replaces the oldest) and the grid and dynamic LDS of both launches.
 // "Device" buffers are host buffers sized exactly as the header says.  No kernel runs.
-#include <cxxabi.h>
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-extern "C" long hipdouble_live_allocs();
-extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-struct Launch {
-    std::string name;
-    dim3 grid, block;
-    size_t lds = 0;
-};
-static std::vector<Launch> g_seen;
-static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void**) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    Launch l;
-    l.name = dm ? dm : mangled;
-    std::free(dm);
-    l.grid = grid; l.block = block; l.lds = shmem;
-    g_seen.push_back(l);
-}
+#include "driver_common.h"
 
 // one stage of a down-/up-sampler between rates in the ratio in_unit : out_unit: windows and weights of the right shape (a
 // triangle: the walk is about extents, not about audio), exactly sized

@@ -3,47 +3,8 @@
 // metrics, row_wise 0 / 1, reps 1 and 3, DPAD 32 and 64, one and two CUs per instance.  It checks which kernel a call launches
 // and on what grid: the L2 metric must issue exactly the launch of the entry it stands for, the cosine metric the same grid,
 // block and dynamic LDS on the cosine kernel.  "Device" buffers are host buffers sized exactly as the header says.  No kernel runs.
-#include <cxxabi.h>
-#include <hip/hip_runtime.h>
+#include "driver_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-extern "C" long hipdouble_live_allocs();
-extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-struct Launch {
-    std::string name;
-    dim3 grid, block;
-    size_t lds = 0;
-    bool same_shape(const Launch& o) const {
-        return grid.x == o.grid.x && grid.y == o.grid.y && grid.z == o.grid.z && block.x == o.block.x && lds == o.lds;
-    }
-};
-static std::vector<Launch> g_seen;
-static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void**) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    Launch l;
-    l.name = dm ? dm : mangled;
-    std::free(dm);
-    l.grid = grid; l.block = block; l.lds = shmem;
-    g_seen.push_back(l);
-}
 static bool is_kernel(const Launch& l, const char* kernel, int dpad) {
     return l.name.find(std::string("::") + kernel + "<" + std::to_string(dpad) + ">(") != std::string::npos;
 }

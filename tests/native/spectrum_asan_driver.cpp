@@ -4,44 +4,7 @@
 // launch geometry and dynamic LDS, the float64 table builder (Bluestein's transformed chirp included), the per-T table cache (a
 // hit allocates nothing, 16 tables stay, the 17th replaces the oldest) and the workspace (grown only when a call needs more).
 // "Device" buffers are host buffers sized exactly as the header says.  No kernel runs.
-#include <cxxabi.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-extern "C" long hipdouble_live_allocs();
-extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-struct Launch {
-    std::string name;
-    dim3 grid, block;
-    size_t lds = 0;
-};
-static std::vector<Launch> g_seen;
-static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void**) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    Launch l;
-    l.name = dm ? dm : mangled;
-    std::free(dm);
-    l.grid = grid; l.block = block; l.lds = shmem;
-    g_seen.push_back(l);
-}
+#include "driver_common.h"
 
 int main() {
     hipdouble_set_launch_hook(record_launch);

@@ -3,90 +3,19 @@
 // template arguments, grid, block, dynamic LDS -- for tests/test_xv_feco_launch_sequence.py, which compares the output with
 // tests/native/xv_feco_launch_sequence.expected.  Every refusal leaves one line with its return code and must come before the
 // first launch.  "Device" buffers are host buffers sized exactly as the header says; the double's copies are real.  No kernel runs.
-#include <cxxabi.h>
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "speakerguard_hip.h"
-
-extern "C" long hipdouble_launches();
-extern "C" long hipdouble_live_allocs();
-extern "C" void hipdouble_set_launch_hook(void (*)(const char*, dim3, dim3, size_t, void**));
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            ++g_fail;                                                                \
-        }                                                                            \
-    } while (0)
-
-static std::vector<float> rnd(size_t n, unsigned seed, float scale = 0.1f, float shift = 0.f) {
-    std::vector<float> v(n);
-    unsigned s = seed * 2654435761u + 12345u;
-    for (size_t i = 0; i < n; ++i) {
-        s = s * 1664525u + 1013904223u;
-        v[i] = shift + scale * ((float)(s >> 8) / 8388608.0f - 1.0f);
-    }
-    return v;
-}
-
-struct XvModel {
-    std::vector<float> w[5], b[5], mean[5], var[5], fc1w, fc1b, emean, lda, pmean, ptrans, ppsi, enroll;
-    sg_xv_weights desc{};
-    XvModel(int D, int S) {
-        const int cin[5] = {30, 512, 512, 512, 512}, cout[5] = {512, 512, 512, 512, 1500}, k[5] = {5, 5, 7, 1, 1};
-        for (int l = 0; l < 5; ++l) {
-            w[l] = rnd((size_t)cout[l] * cin[l] * k[l], 10 + l);
-            b[l] = rnd(cout[l], 20 + l);
-            mean[l] = rnd(cout[l], 30 + l);
-            var[l] = rnd(cout[l], 40 + l, 0.5f, 1.0f);
-            desc.tdnn_weight[l] = w[l].data(); desc.tdnn_bias[l] = b[l].data();
-            desc.bn_mean[l] = mean[l].data(); desc.bn_var[l] = var[l].data();
-        }
-        fc1w = rnd((size_t)512 * 3000, 1); fc1b = rnd(512, 2); emean = rnd(512, 3); lda = rnd((size_t)D * 513, 4);
-        pmean = rnd(D, 5); ptrans = rnd((size_t)D * D, 6); ppsi = rnd(D, 7, 0.5f, 1.0f); enroll = rnd((size_t)S * D, 8);
-        desc.fc1_weight = fc1w.data(); desc.fc1_bias = fc1b.data(); desc.emb_mean = emean.data(); desc.lda = lda.data();
-        desc.plda_mean = pmean.data(); desc.plda_transform = ptrans.data(); desc.plda_psi = ppsi.data(); desc.enroll = enroll.data();
-        desc.D = D; desc.S = S; desc.bn_eps = 1e-5f; desc.threshold = -INFINITY;
-    }
-};
-
-// "void sg::(anonymous namespace)::k<1, (sg::E)2>(args)" -> "k<1,(E)2>"
-static std::string kernel_name(const char* mangled) {
-    int status = 0;
-    char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-    std::string name = dm ? dm : mangled;
-    std::free(dm);
-    for (const char* drop : {"(anonymous namespace)::", "sg::", "void "})
-        for (size_t at; (at = name.find(drop)) != std::string::npos;) name.erase(at, std::strlen(drop));
-    int depth = 0;
-    for (size_t i = 0; i < name.size(); ++i) {  // the parameter list opens at template depth 0
-        depth += name[i] == '<' ? 1 : name[i] == '>' ? -1 : 0;
-        if (name[i] == '(' && depth == 0) { name.resize(i); break; }
-    }
-    name.erase(std::remove(name.begin(), name.end(), ' '), name.end());
-    return name;
-}
+#include "driver_common.h"
 
 static std::string g_label;
 static int g_n = 0;
-static void record_launch(const char* mangled, dim3 grid, dim3 block, size_t shmem, void**) {
-    std::printf("%s #%d | %s grid=%u,%u,%u block=%u lds=%zu\n", g_label.c_str(), ++g_n, kernel_name(mangled).c_str(), grid.x, grid.y,
-                grid.z, block.x * block.y * block.z, shmem);
+static void print_line(const Launch& l, void**) {
+    print_launch(g_label, ++g_n, l);
+    std::printf("\n");
 }
 
 int main() {
     setenv("SG_TUNE", "1", 1);  // SG_EOT_MAX_ROWS counts, where a case sets it
     unsetenv("SG_EOT_MAX_ROWS");
+    g_on_launch = print_line;
     hipdouble_set_launch_hook(record_launch);
     sg_ctx* ctx = nullptr;
     EXPECT(sg_create(0, &ctx) == SG_OK && ctx != nullptr);

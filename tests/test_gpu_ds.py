@@ -51,12 +51,12 @@ def fwd(ds, x, raw=False, B=None, T=None, N=None, spec=None):
     return out.cpu().numpy()
 
 
-def bwd(ds, g, T):
+def bwd(ds, g, T, spec=None):
     from speakerguard_amd import _native as N_
     gd = torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(DEV)
     gx = torch.full((gd.shape[0], T), 7.0, device=DEV)
-    _ctx().call("sg_wav_resample_backward", C.byref(ds._spec), N_._ptr(gd), gd.shape[0], T, gd.shape[1], N_._ptr(gx),
-                N_.current_stream_ptr(DEV))
+    _ctx().call("sg_wav_resample_backward", C.byref(ds._spec if spec is None else spec), N_._ptr(gd), gd.shape[0], T, gd.shape[1],
+                N_._ptr(gx), N_.current_stream_ptr(DEV))
     torch.cuda.synchronize()
     return gx.cpu().numpy()
 
@@ -159,6 +159,28 @@ def test_shapes_lengths_and_refusals():
     assert ctx.lib.sg_wav_resample_backward(ctx.handle, C.byref(d._spec), N_._ptr(xd), 3, T, T, None, None) == 1
     assert ctx.lib.sg_wav_resample_backward(ctx.handle, None, N_._ptr(xd), 3, T, T, N_._ptr(gd), None) == 1
     torch.cuda.synchronize()
+
+
+def test_tables_pushed_out_of_the_cache_come_back_the_same():
+    """the context keeps the tables of 32 specs, keyed by content: 32 other specs (DS(0.5)'s tables with one weight's last bit
+    flipped, another weight each time) push the original's out, freed behind the stream; rebuilt, they give the first call's bits"""
+    from speakerguard_amd import _native as N_
+    d = _ds(0.5)
+    B, T = 2, 1000
+    x, g = _case(B, T, T, seed=21)
+    first = fwd(d, x), bwd(d, g, T)
+    assert np.abs(first[0]).max() > 0.01 and np.abs(first[1]).max() > 0.01
+    n_down = d.down["weight"].size
+    assert n_down + d.up["weight"].size >= 32
+    for k in range(32):
+        down, up = np.ascontiguousarray(d.down["weight"], np.float32).copy(), np.ascontiguousarray(d.up["weight"], np.float32).copy()
+        (down if k < n_down else up).reshape(-1).view(np.uint32)[k if k < n_down else k - n_down] ^= 1
+        spec = N_.WavResample()
+        C.memmove(C.byref(spec), C.byref(d._spec), C.sizeof(spec))
+        spec.down.weight, spec.up.weight = (w.ctypes.data_as(C.POINTER(C.c_float)) for w in (down, up))
+        fwd(d, x, spec=spec), bwd(d, g, T, spec=spec)
+    again = fwd(d, x), bwd(d, g, T)
+    assert np.array_equal(bits(again[0]), bits(first[0])) and np.array_equal(bits(again[1]), bits(first[1]))
 
 
 # ---------------------------------------------------------------- the adjoint, from the device's outputs

@@ -153,6 +153,22 @@ def test_row_of_a_batch_equals_the_row_alone(T):
     assert 0 < int(kept[0]) < T // 2 + 1
 
 
+@pytest.mark.parametrize("T", [480, 662], ids=["smooth", "bluestein"])
+def test_tables_pushed_out_of_the_cache_come_back_the_same(T):
+    """the context keeps the tables of 16 lengths: 16 other lengths push T's out, freed behind the stream; rebuilt, they give
+    the first call's bits"""
+    from speakerguard_amd.attack.Kenan import wav_spectrum
+    xd = torch.from_numpy(_inputs(2, T, "noise")).to(DEV).unsqueeze(1)
+    spec, peak = wav_spectrum(xd)
+    first = torch.view_as_real(spec).cpu().numpy(), peak.cpu().numpy()
+    assert first[1].min() > 0
+    for other in range(100, 161, 4):
+        wav_spectrum(xd[:, :, :other].contiguous())
+    spec, peak = wav_spectrum(xd)
+    assert np.array_equal(bits(torch.view_as_real(spec).cpu().numpy()), bits(first[0]))
+    assert np.array_equal(bits(peak.cpu().numpy()), bits(first[1]))
+
+
 def test_factor_edge_cases():
     """a NaN, a negative and a zero factor keep everything; a factor above the peak keeps nothing; the comparison is strict"""
     from speakerguard_amd.attack.Kenan import wav_spectrum_gate
