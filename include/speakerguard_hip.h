@@ -695,6 +695,39 @@ int sg_wav_spectrum(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, float
 int sg_wav_spectrum_gate(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, const float* factor_dev, float* out_dev,
                          uint8_t* keep_dev, int32_t* kept_dev, void* stream);
 
+/* ---- singular spectrum analysis of whole utterances (attack/_kenan.py ssa_compression :86-112, attack/ssa_core.py) -----------
+ * Kenan's `ssa` variant without the trajectory matrix: W = min(int(0.05 T), 3000), t = T - W + 1; float64 (or exact integers)
+ * after the quantisation; no buffer larger than W x W per utterance.  csrc/k_ssa.hip's header states every formula and every
+ * summation order; tests/ssa_restate.py restates the route in numpy.
+ *   sg_ssa_window      pure: W for T, or -1 when T < 20 (W would be 0) or T > 2^22.
+ *   sg_ssa_decompose   x (B,T) float32 -> xq (B,T) int16: per utterance, when 0.9f * max <= 1 and 0.9f * min >= -1 (float32) the
+ *                      samples are multiplied by 2^(bits-1) in float32; then int32 toward zero (NaN: 0, beyond int32: its nearest
+ *                      end), low 16 bits -- a value outside the int16 range WRAPS.  The W x W lag covariance C[a][b] = sum_{p<t}
+ *                      xq[p+a] xq[p+b] is formed exactly in int64 (cov (B,W,W) float64, optional: the exact values), and its
+ *                      eigenpairs by a two-sided cyclic Jacobi iteration in a fixed round-robin order, closed by one Newton-Schulz
+ *                      step on the accumulated rotations (V <- V (1.5 I - 0.5 V^T V)): eval (B,W) float64 in descending order,
+ *                      ties by index; evec (B,W,W) float64, ROW j = eigenvector j; sweeps (B) int32 = the sweeps
+ *                      that rotated (0 for a silent utterance).  A pair (p,q) is left alone when a_pq == 0 or |a_pq| <= 2^-52
+ *                      sqrt(|a_pp a_qq|); an utterance is done after a sweep without a rotation.  The host reads the rotation
+ *                      counters once per sweep: the call SYNCHRONISES the stream, once per sweep and once at its end.
+ *                      SG_ERR_STATE when an utterance still rotates after 30 sweeps (the outputs are then undefined).
+ *   sg_ssa_reconstruct xq, evec as above and k (B) int32 ON THE HOST (read before the call returns), 1 <= k[b] <= W: the rank-k[b]
+ *                      reconstruction P = V_k V_k^T, diagonal averaging as one FIR filter (taps = the diagonal sums of P) away
+ *                      from the first and last W - 1 samples and triangular sums there, divided by min(m+1, W, T-m); out (B,T)
+ *                      float32 = the int16 value (toward zero; wraps like xq), out64 (B,T) float64 (optional) = the value before
+ *                      that cast.  Stream-ordered, no synchronisation.
+ * All other pointers are device pointers, rows contiguous.  The workspace comes from the context: at most B (2 W^2 + 3 W + 2) float64 for
+ * sg_ssa_decompose, B (W^2 + 2 W) for sg_ssa_reconstruct, grown (one stream synchronisation) when a call needs more than any before,
+ * which makes the calls of ONE context on DIFFERENT streams unsafe to overlap.  An utterance's results do not depend on B or on its
+ * place in the call, and two calls give the same bits.
+ * SG_ERR_ARG before any launch: ctx or a required pointer NULL, B outside 1 .. 65535, T outside 20 .. 2^22, bits outside 1 .. 16,
+ * a k[b] outside 1 .. W. */
+int32_t sg_ssa_window(int32_t T);
+int sg_ssa_decompose(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, int32_t bits, int16_t* xq_dev, double* eval_dev,
+                     double* evec_dev, int32_t* sweeps_dev, double* cov_dev, void* stream);
+int sg_ssa_reconstruct(sg_ctx* ctx, const int16_t* xq_dev, const double* evec_dev, const int32_t* k_host, int32_t B, int32_t T,
+                       float* out_dev, double* out64_dev, void* stream);
+
 /* ---- input-level defenses inside the device-resident x-vector PGD loop ---------------------------------------
  * sg_xv_pgd_run for a model that carries a chain of 1 .. SG_WAV_CHAIN_MAX waveform-level defenses (flag 0, sequential
  * order), applied in chain order to the waveform before the MFCC.  A stage is one sg_wav_defense or one sg_wav_filter,

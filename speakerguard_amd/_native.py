@@ -29,6 +29,7 @@ EXPORTS = (
     "sg_feco_kmeans_compress_rows", "sg_xv_pgd_run_feco", "sg_feco_kmeans_compress_metric",
     "sg_wav_resample_forward", "sg_wav_resample_backward",
     "sg_wav_spectrum", "sg_wav_spectrum_gate",
+    "sg_ssa_window", "sg_ssa_decompose", "sg_ssa_reconstruct",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -217,6 +218,9 @@ def load():
         "sg_wav_resample_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp]),
         "sg_wav_spectrum": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "sg_wav_spectrum_gate": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "sg_ssa_window": (i32, [i32]),
+        "sg_ssa_decompose": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sg_ssa_reconstruct": (C.c_int, [vp, vp, vp, C.POINTER(i32), i32, i32, vp, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -11,7 +11,8 @@ Faithfulness notes:
     equal to its input;
   * ``early_stop`` is accepted and unused (:180), ``raster_width`` is not read by the ``fft`` variant (:196-198);
   * the whole chunk is queried at every iteration, succeeded utterances included (:226);
-  * ``atk_name='ssa'`` (a CPU SVD per query, int16 audio) is not built: NotImplementedError.
+  * ``atk_name='ssa'`` is a class of its own, ``speakerguard_amd.attack.KenanSSA.KenanSSA`` (int16 audio, a native
+    decomposition per utterance, a native reconstruction per query); asked for here it is a NotImplementedError that says so.
 """
 import numpy as np
 import torch
@@ -69,7 +70,7 @@ class Kenan(object):
     def __init__(self, model, atk_name='fft', max_iter=15, raster_width=100, early_stop=False, targeted=False, verbose=1,
                  BITS=16, batch_size=1, gate=None, peak=None):
         if atk_name == 'ssa':
-            raise NotImplementedError("Kenan's ssa variant (a CPU SVD per query) is not built; use atk_name='fft'")
+            raise NotImplementedError("Kenan's ssa variant is speakerguard_amd.attack.KenanSSA.KenanSSA(model, ...); this class runs atk_name='fft'")
         if atk_name != 'fft':
             raise NotImplementedError("unknown Kenan variant %r (built: 'fft')" % (atk_name,))
         self.model = model  # remember to call model.eval()

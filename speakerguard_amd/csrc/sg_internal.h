@@ -335,6 +335,8 @@ struct sg_ctx {
     sg::DevTableCache sp_cache;      // the spectrum gate's, keyed by T (k_spectrum.hip) ...
     sg::DevBuf<float2> sp_ws;        // ... its workspace (in model_allocs): [rows][2][N] of the largest call that did not fit LDS ...
     bool sp_lds_opted = false;       // ... and its > 64 KB dynamic-LDS opt-in
+    sg::DevBuf<double> ssa_ws;       // the SSA calls' workspace (k_ssa.hip; in model_allocs): the largest call's matrices ...
+    sg::DevBuf<int32_t> ssa_iws;     // ... and its counters, flags and ranks
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
