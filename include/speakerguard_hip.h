@@ -357,7 +357,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
  * Between sg_trace_begin and sg_trace_end every launch of sg_xv_forward / sg_xv_loss_grad / sg_xv_pgd_run and of
  * sg_an_forward / sg_an_loss_grad / sg_an_pgd_run / sg_an_pgd_run_feco (tags 30..) is bracketed by a pair of HIP events
  * on the launch stream, up to max_records launches (further launches are not recorded).  The per-stage entry points
- * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_*, sg_wav_filter_* and sg_wav_resample_* are (tags 60 .. 63, 70, 71), and so are sg_xv_pgd_run_defended and sg_an_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
+ * (sg_xv_mfcc, sg_an_logmel, sg_feco_*, the attack-state updates) are not traced; sg_wav_defense_*, sg_wav_filter_* and sg_wav_resample_* are (tags 60 .. 63, 70, 71), sg_wav_stoi is (tags 72 .. 76), and so are sg_xv_pgd_run_defended and sg_an_pgd_run_defended (tags 64 .. 66 besides).  An event record that fails drops
  * its launch record, and sg_trace_end then returns SG_ERR_HIP with the count in sg_last_error.
  * sg_trace_end waits for the last recorded event, writes tag and elapsed milliseconds of each record in launch order
  * (at most `capacity`), the number of records to *n_out, and switches the trace off.  Tags: +l / -l = forward /
@@ -408,6 +408,12 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
 /* the down-/up-sampling input defense (sg_wav_resample_forward / _backward), traced like the other input defenses */
 #define SG_STAGE_DS_FWD 70
 #define SG_STAGE_DS_BWD 71
+/* the launches of sg_wav_stoi, traced so that its stages can be timed from outside */
+#define SG_STAGE_STOI_SCALE 72
+#define SG_STAGE_STOI_RESAMPLE 73
+#define SG_STAGE_STOI_MASK 74
+#define SG_STAGE_STOI_BANDS 75
+#define SG_STAGE_STOI_SEGMENTS 76
 int sg_trace_begin(sg_ctx* ctx, int32_t max_records);
 int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity, int32_t* n_out);
 
@@ -440,6 +446,28 @@ int sg_conv1d_rows(sg_ctx* ctx, const float* a_dev, const float* w_dev, float* c
  * pcm_dev or metrics_dev may be NULL; benign_dev is only needed for the metrics. */
 int sg_wav_finalize(sg_ctx* ctx, const float* benign_dev, const float* adver_dev, int32_t B, int32_t T,
                     int16_t* pcm_dev, double* metrics_dev, void* stream);
+
+/* STOI of B utterance pairs (reference metric/metric.py:50-54, which calls pystoi; Taal, Hendriks, Heusdens, Jensen 2011), float64
+ * after the float32 samples are read.  The contract -- written from the published algorithm, unpinned by pystoi -- is DESIGN.md
+ * section 4; csrc/k_stoi.hip's header states every summation order, tests/stoi_restate.py restates them in numpy.
+ *   benign, adver (B,T) float32 at fs = 16000 (resampled by 5/8 with Octave's resample filter) or fs = 10000 (taken as is); each
+ *   row of each signal is divided by 2^15 unless -1 <= max <= 1 (metric.py:10-14).  Frames of 256 samples at hop 128 of the benign
+ *   signal more than 40 dB under its loudest frame are dropped from both signals; stoi (B) double is the mean clipped, normalised
+ *   correlation of the 15 one-third-octave band envelopes over every 30-frame segment, or exactly 1e-5 for a row that keeps fewer
+ *   than 31 frames (pystoi's "not enough frames" value).  frames (B) int32, optional: the frames the row kept (the value is 1e-5
+ *   iff frames - 1 < 30).
+ * Five launches on `stream`, no synchronisation and no host round trip between them; tables (keyed by fs) and workspace come from the
+ * context: the first use of an fs uploads its tables, a call larger than any before grows the workspace (one stream
+ * synchronisation), which makes the calls of ONE context on DIFFERENT streams unsafe to overlap.  A row's result depends on its own
+ * samples, T and fs only: not on B, not on its place in the call.  Traced (tags 72 .. 76).
+ * SG_ERR_ARG before any launch: ctx or a required pointer NULL, B outside 1 .. 65535, fs other than 10000 / 16000, T outside
+ * 1 .. 2^24, a T whose length at 10 kHz (ceil(5 T / 8) for fs = 16000) is <= 256. */
+/* pure, no context (parity tests): the bytes of sg_wav_stoi's device tables as the host builds them -- float64 [5][123] polyphase
+ * branches (+ 1 pad), [256] window, [448] + [72] complex twiddles, the clipping factor (+ 1 pad), then int32 [16] + [16] band edges --
+ * copied to `out` when it is not NULL and `capacity` bytes hold them; returns their size in bytes either way. */
+int32_t sg_stoi_debug_tables(void* out, int32_t capacity);
+int sg_wav_stoi(sg_ctx* ctx, const float* benign_dev, const float* adver_dev, int32_t B, int32_t T, int32_t fs,
+                double* stoi_dev, int32_t* frames_dev, void* stream);
 
 /* set_threshold.py:22-47 set_threshold(score_target, score_untarget): scans the target scores in order and
  * keeps the first one minimising |FRR - FAR| (both in percent).  out3_dev: threshold, FRR, FAR (doubles).

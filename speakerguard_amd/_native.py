@@ -30,6 +30,7 @@ EXPORTS = (
     "sg_wav_resample_forward", "sg_wav_resample_backward",
     "sg_wav_spectrum", "sg_wav_spectrum_gate",
     "sg_ssa_window", "sg_ssa_decompose", "sg_ssa_reconstruct",
+    "sg_wav_stoi", "sg_stoi_debug_tables",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -50,6 +51,8 @@ STAGE_NAMES.update({64: "def_scale", 65: "def_replicate", 66: "def_rep_sum"})
 # FeCo inside the x-vector device loop (SG_STAGE_XV_FECO_*)
 STAGE_NAMES.update({67: "xv_feco_fwd", 68: "xv_feco_bwd", 69: "xv_feco_cols"})
 STAGE_NAMES.update({70: "ds_fwd", 71: "ds_bwd"})  # the down-/up-sampling input defense (SG_STAGE_DS_*)
+# the launches of sg_wav_stoi (SG_STAGE_STOI_*)
+STAGE_NAMES.update({72: "stoi_scale", 73: "stoi_resample", 74: "stoi_mask", 75: "stoi_bands", 76: "stoi_segments"})
 SG_FECO_L2, SG_FECO_COS = 0, 1  # sg_feco_kmeans_compress_metric
 SG_TD = {"QT": 0, "AS": 1, "MS": 2, "AT": 3}
 SG_WAV_CHAIN_MAX = 8
@@ -218,6 +221,8 @@ def load():
         "sg_wav_resample_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp]),
         "sg_wav_spectrum": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "sg_wav_spectrum_gate": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "sg_wav_stoi": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "sg_stoi_debug_tables": (i32, [vp, i32]),
         "sg_ssa_window": (i32, [i32]),
         "sg_ssa_decompose": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "sg_ssa_reconstruct": (C.c_int, [vp, vp, vp, C.POINTER(i32), i32, i32, vp, vp, vp]),

@@ -852,6 +852,7 @@ void sg_destroy(sg_ctx* ctx) {
     free_pool(ctx->def_ws.allocs);
     ctx->rs_cache.clear();
     ctx->sp_cache.clear();
+    ctx->stoi_cache.clear();
     free_pool(ctx->an_ws.allocs);  // (leaked until round 4: found by the sanitizer build's leak check, `make asan`)
     free_pool(ctx->xv.allocs);
     free_pool(ctx->model_allocs);

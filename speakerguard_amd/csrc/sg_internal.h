@@ -337,6 +337,9 @@ struct sg_ctx {
     bool sp_lds_opted = false;       // ... and its > 64 KB dynamic-LDS opt-in
     sg::DevBuf<double> ssa_ws;       // the SSA calls' workspace (k_ssa.hip; in model_allocs): the largest call's matrices ...
     sg::DevBuf<int32_t> ssa_iws;     // ... and its counters, flags and ranks
+    sg::DevTableCache stoi_cache;    // STOI's tables, keyed by fs (k_stoi.hip) ...
+    sg::DevBuf<double> stoi_ws;      // ... its workspace (in model_allocs): the largest call's 10 kHz signals, energies and band values ...
+    sg::DevBuf<int32_t> stoi_iws;    // ... and its kept-frame counts and indices
     // Health word: host-pinned, device-mapped.  A kernel that gives up on a stream-K hand-off (bounded spin) ORs a
     // bit into it; every pass entry point and sg_sync read the host side and fail loudly (no synchronisation needed).
     unsigned* err_host = nullptr;
