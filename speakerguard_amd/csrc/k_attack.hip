@@ -7,18 +7,14 @@
 //                 turned into the sign step (attack/FGSM.py:65,68)
 #include "loss_device.h"
 #include "sg_internal.h"
+#include "philox.h"
+#include "wave_reduce.h"
 
 // These updates mirror torch elementwise expressions (separate multiply and add roundings); keep hipcc
 // from contracting them into FMAs so the results are bit-identical to the reference formulas.
 #pragma clang fp contract(off)
 
 namespace sg {
-
-__device__ __forceinline__ float wave_sum_a(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------- CW2
 // One pass: (optional) Adam update of the modifier from d loss1/d input_x of the CURRENT input, then
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(256) void cw2_step_kernel(float* __restrict__ modif
         acc += d * d;
     }
     __shared__ float red[4];
-    acc = wave_sum_a(acc);
+    acc = wave_sum_xor(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -70,7 +66,7 @@ __global__ __launch_bounds__(64) void row_sum_kernel(const float* __restrict__ p
     const int b = blockIdx.x;
     float acc = 0.f;
     for (int i = threadIdx.x; i < n; i += 64) acc += part[(size_t)b * n + i];
-    acc = wave_sum_a(acc);
+    acc = wave_sum_xor(acc);
     if (threadIdx.x == 0) out[b] = acc;
 }
 
@@ -89,30 +85,12 @@ hipError_t launch_cw2_step(float* modifier, float* exp_avg, float* exp_avg_sq, c
 }
 
 // ---------------------------------------------------------------- NES / FAKEBOB
-__device__ __forceinline__ uint32_t philox_a(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                             uint32_t* second) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    *second = c1;
-    return c0;
-}
-
 // standard normal for (example index, antithetic pair index, sample t): Box-Muller on two Philox words
 __device__ __forceinline__ float nes_normal(uint64_t seed, int64_t example, int pair, int t) {
     uint32_t r1;
-    const uint32_t r0 = philox_a(seed, (uint32_t)t, (uint32_t)pair, (uint32_t)example, (uint32_t)((uint64_t)example >> 32), &r1);
-    const float u0 = ((float)(r0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(r1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const uint32_t r0 = philox4x32_10_w01(seed, (uint32_t)t, (uint32_t)pair, (uint32_t)example, (uint32_t)((uint64_t)example >> 32), &r1);
+    const float u0 = philox_unit24(r0);
+    const float u1 = philox_unit24(r1);
     return sqrtf(-2.f * logf(u0)) * cosf(6.283185307179586f * u1);
 }
 

@@ -10,7 +10,6 @@
 #include "loss_device.h"
 #include "sg_internal.h"
 #include "fft512.h"
-#include "fft512t.h"
 
 namespace sg {
 
@@ -19,17 +18,11 @@ constexpr int kAnCus = 256;
 constexpr int kAnHalf = kAnFft / 2; // 512: a 1024-point REAL frame is one 512-point complex transform + a split step
 constexpr int kAnMelLaneBins = 20;  // bins per lane of the mel stage: a filter's bins in runs of <= 20 (an_build_tables)
 
-__device__ __forceinline__ float an_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-#pragma clang fp contract(off)  // see fft512t.h: every fused multiply-add of the log-mel front-end is written out
+#pragma clang fp contract(off)  // see fft512.h: every fused multiply-add of the log-mel front-end is written out
 
 // Log-mel front-end, one wave per frame (same recipe as the MFCC kernels, k_mfcc.hip):
 //   * the 1024 real samples x[q] of a frame are packed as z[n] = x[2n] + i x[2n+1] and transformed by ONE 512-point
-//     complex FFT (fft512t.h: in-register radix-8, padded conflict-free LDS buffer); the spectrum follows from
+//     complex FFT (fft512.h: in-register radix-8, padded conflict-free LDS buffer); the spectrum follows from
 //         X[k] = A_k Z[k] + B_k conj(Z[512-k]),   A_k = (1 - i W^k)/2,  B_k = (1 + i W^k)/2,  W = exp(-2 pi i/1024),
 //     for k = 0..512 -- half the butterflies and half the LDS of a 1024-point transform;
 //   * the backward is the adjoint of exactly that: dZ[j] = conj(A_j) G[j] + B_{512-j} conj(G[512-j]) (+ the k = 512
@@ -270,7 +263,7 @@ __global__ __launch_bounds__(256, sizeof(R) == 4 ? 4 : 2) void an_logmel_fwd_ker
         cx<R> z[8];
         an_frame_forward<R, true, true>(tw1, tw2, L, lc, cur, scale, lane, z);
         if (t.spec_cache) {  // packed spectrum for the backward of the same pass (float32 whatever R is), in TRANSFORM order
-            float2* sc = t.spec_cache + (size_t)gf * kAnHalf;  // (fft512_transform_pos): straight from the registers
+            float2* sc = t.spec_cache + (size_t)gf * kAnHalf;  // (transform order: element 64 d + lane): straight from the registers
 #pragma unroll
             for (int d = 0; d < 8; ++d) sc[lane + 64 * d] = make_float2((float)z[d].x, (float)z[d].y);
         }

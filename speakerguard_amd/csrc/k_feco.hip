@@ -44,6 +44,7 @@
 
 #include "sg_internal.h"
 #include "philox.h"
+#include "wave_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -154,10 +155,7 @@ __device__ __forceinline__ int sw_at(int row, int d) { return sw_slot<DPAD>(row,
 // adds instead of four trips through the LDS crossbar; steps 16 (and 32) go through ds_bpermute.
 template <int DPAD>
 __device__ __forceinline__ float row_tree_sum(float v) {
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
+    v = row16_sum_dpp(v);
     v = v + __shfl_xor(v, 16);
     if (DPAD == 64) v = v + __shfl_xor(v, 32);
     return v;

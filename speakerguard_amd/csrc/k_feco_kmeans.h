@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kFecoThreads) void FECO_KMEANS_KERNEL(const float* 
         }
     };
     // blockIdx.y = repeat: the same utterances clustered again from other random frames (EOT over the defense); repeat r
-    // uses key seed + r * 0xC2B2AE3D27D4EB4F and writes slot r * gridDim.x + utterance of every output.  row_wise: the repeats
+    // uses key seed + r * kRepKey and writes slot r * gridDim.x + utterance of every output.  row_wise: the repeats
     // have features of their own (a dithered front-end in front of the defense) -- repeat r reads that slot too
     // Two CUs per instance: the grid's z dimension is the half.  (Blocks go to the 8 XCDs round robin by linear index: with
     // the instances a multiple of 8 the two halves share an XCD -- a speed assumption only.  Halves as neighbours in x --
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kFecoThreads) void FECO_KMEANS_KERNEL(const float* 
     const float* x = feats + (row_wise ? slot : (size_t)bx) * F * D;
     __shared__ int pair_solo;
     if (tid == 0) pair_solo = 0;
-    seed += (uint64_t)blockIdx.y * 0xC2B2AE3D27D4EB4Full;
+    seed += (uint64_t)blockIdx.y * kRepKey;
     FECO_STAMP(4 * kFecoTraceIters + 2)
     for (int i = tid; i < al4(F); i += kFecoThreads) ids[i] = -1;  // the pad entries stay -1: no cluster
     if (fast_lists)

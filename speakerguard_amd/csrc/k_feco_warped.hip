@@ -16,7 +16,7 @@
 //     which stops at index 2;
 //   * random init: the k - 1 frames of lowest (Philox4x32-10(counter = (frame, 0, utterance lo, utterance hi), key) word 0,
 //     frame) among frames 1 .. F - 1, sorted, after 0 -- keyed like oracle/philox.py feco_random_init, with the global
-//     utterance index_base + u and key + r * 0xC2B2AE3D27D4EB4F for row r * rep_rows + u (EOT repeat r);
+//     utterance index_base + u and key + r * kRepKey for row r * rep_rows + u (EOT repeat r);
 //   * the initial boundaries must rise strictly from 0 (a TS init of a pathological input does not: the reference then
 //     takes means of empty slices, NaN); a row whose boundaries do not is refused (SG_ERR_ARG), it never yields NaN;
 //   * initial segment means (:88-107): the segment's frames summed in ascending frame order from 0.f, / (float)count;
@@ -49,7 +49,6 @@ constexpr int kWarpMaxD = 64;     // one lane per dimension
 constexpr size_t kWarpLdsMax = 150 * 1024;
 constexpr int kWarpBadInit = -1;  // sweeps[row]: initial boundaries not strictly increasing from 0
 constexpr int kWarpCapped = -2;   // sweeps[row]: still moving after the cap
-constexpr unsigned long long kWarpRepStride = 0xC2B2AE3D27D4EB4FULL;
 
 __host__ __device__ constexpr int wal4(int n) { return (n + 3) & ~3; }
 
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(64) void feco_warped_kernel(const float* __restrict
         // random init (:80-85): rank of frame f among frames 1 .. F-1 by (key, frame); the k - 1 lowest, in frame order
         const int rep = rep_rows > 0 ? row / rep_rows : 0;
         const long long utt = index_base + (rep_rows > 0 ? row - rep * rep_rows : row);
-        const unsigned long long rkey = key + (unsigned long long)rep * kWarpRepStride;
+        const unsigned long long rkey = key + (unsigned long long)rep * kRepKey;
         unsigned* keys = reinterpret_cast<unsigned*>(scr);
         for (int f = lane; f < wal4(F); f += 64)
             keys[f] = f < F ? philox4x32_10_w0(rkey, (uint32_t)f, 0u, (uint32_t)utt, (uint32_t)((unsigned long long)utt >> 32))

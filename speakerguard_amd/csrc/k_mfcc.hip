@@ -20,7 +20,9 @@
 // walks the stages in reverse; the gradient spectrum is formed in registers and transformed back by the TRANSPOSED network.
 // It writes per-frame sample gradients (B,F,400); frames_to_wave_kernel does the deterministic overlap-add.
 #include "sg_internal.h"
-#include "fft512t.h"
+#include "fft512.h"
+#include "philox.h"
+#include "wave_reduce.h"
 
 namespace sg {
 
@@ -28,7 +30,7 @@ constexpr int kMfccMaxBlocks = 512;  // 2 blocks (~60 KB LDS each) per CU x 256 
 
 // Round 6: the per-frame functions are templates over the transform's scalar type R.
 //   R = float  (default): the reference's own precision -- torchaudio 0.6's kaldi.mfcc is float32 end to end, torch.rfft
-//              included (model/xv_plda.py:114-148) -- on the transform-order / transposed-network pair of fft512t.h: the
+//              included (model/xv_plda.py:114-148) -- on the transform-order / transposed-network pair of fft512.h: the
 //              forward transform leaves bin k1 + 8 c + 64 d in registers of lane (k1, c), power, spectrum cache and the
 //              gradient spectrum are formed right there, and the TRANSPOSED inverse takes that layout and returns
 //              samples lane + 64 j in registers, where window, pre-emphasis adjoint (a whole-wave DPP shift), energy and DC
@@ -64,7 +66,6 @@ struct FrameLdsT {
 // lane's half filter, the DCT matrix in both orientations, window, twiddles): in registers they cost 55-60 VGPRs per lane and
 // held the kernels at 2 waves per SIMD -- latency-bound at ~40 % VALU and ~37 % LDS utilisation.  All of these reads are
 // lane-linear (conflict-free) and independent of the frame's data.
-static_assert(kMfccTw1 == kFftTw1 && kMfccTw2 == kFftTw2, "table sizes of fft512.h");
 template <typename R>
 struct TabLdsT : MfccLdsImage<R> {
     __device__ __forceinline__ const cx<R>* tw1c() const { return reinterpret_cast<const cx<R>*>(this->tw1); }
@@ -82,42 +83,10 @@ __device__ __forceinline__ void stage_tables(const MfccTables& t, TabLdsT<R>& tb
     __syncthreads();
 }
 
-
-// Sum over the 64 lanes, the same value in every lane: a butterfly inside each row of 16 lanes on DPP (quad permutes, then
-// the half-row and row mirrors pair the quads / halves), then the four row sums through scalar registers.  ~12 instructions
-// and no LDS traffic; the ds_bpermute butterfly of rounds 1-5 cost six dependent LDS round trips per sum.
-__device__ __forceinline__ float wave_sum(float v) {
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-// Philox4x32-10 counter-based generator (Salmon et al. 2011); one 32-bit draw per (key, counter).
-__device__ __forceinline__ uint32_t philox_u32(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
+// one Philox draw per (key, utterance, frame, sample)
 __device__ __forceinline__ float dither_draw(uint64_t seed, int64_t utt, int frame, int n, float dither) {
-    const uint32_t r = philox_u32(seed, (uint32_t)n, (uint32_t)frame, (uint32_t)utt, (uint32_t)((uint64_t)utt >> 32));
-    float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const uint32_t r = philox4x32_10_w0(seed, (uint32_t)n, (uint32_t)frame, (uint32_t)utt, (uint32_t)((uint64_t)utt >> 32));
+    float u = philox_unit24(r);
     u = fmaxf(u, kEps);
     // torchaudio 0.6.0 _get_window feeds the SAME uniform draw to both Box-Muller factors
     return sqrtf(-2.f * logf(u)) * cosf(6.283185307179586f * u) * dither;
@@ -155,13 +124,13 @@ __device__ __forceinline__ int opaque_zero() {
     return z;
 }
 
-// No implicit contraction in the per-frame arithmetic (as in fft512t.h): the same functions are instantiated in the forward
+// No implicit contraction in the per-frame arithmetic (as in fft512.h): the same functions are instantiated in the forward
 // kernel and in both backward kernels and must give the same bits there; every fused multiply-add is written out.
 #pragma clang fp contract(off)
 
 // MODE 0: full forward (writes the spectrum / mel cache when t.spec_cache is set); MODE 1: backward with a cache:
 // only the sample statistics are recomputed, spectrum and mel energies are read back (no FFT, no mel/DCT loops).
-// Xk[d] = the spectrum at bin (lane >> 3) + 8 (lane & 7) + 64 d ("transform order", fft512t.h), d < 4: the 256 bins that
+// Xk[d] = the spectrum at bin (lane >> 3) + 8 (lane & 7) + 64 d ("transform order", fft512.h), d < 4: the 256 bins that
 // exist, in registers.  The transform's input stays out of LDS as well: the windowed frame is real and zero beyond sample
 // 399, so pass 1 takes it as 7 values per lane.  The spectrum cache keeps a frame's bins in transform order (element
 // 64 d + lane): written and read back as whole 512-byte rows.
@@ -179,20 +148,21 @@ __device__ __forceinline__ void frame_forward(const MfccTables& t, const TabLdsT
             v = raw[i] * scale;
             if (DZ == 2) v += dz.noise_dev[((size_t)b * F + f) * kWin + n];
             else if (DZ == 1) {
-                // repeat r of the batched EOT passes draws from key seed + r * 0xC2B2AE3D27D4EB4F, like the r-th of the
+                // repeat r of the batched EOT passes draws from key seed + r * kRepKey, like the r-th of the
                 // sequential passes it replaces (sg_xv_pgd_run); a caller that materialised the repeats itself
                 // (EOT.py:29) names their length in dz.rep_rows, and a row slice of a larger call its offset in
                 // dz.row_base (speakerguard_hip.h, sg_dither): same draws however the work was cut
-                const int64_t g = dz.row_base + b;
                 const int64_t rlen = t.rep_utts > 0 ? t.rep_utts : dz.rep_rows;
-                const int64_t rep = rlen > 0 ? g / rlen : 0, utt = g - rep * rlen;
-                v += dither_draw(dz.seed + (uint64_t)rep * 0xC2B2AE3D27D4EB4Full, dz.index_base + utt, f, n, dz.dither);
+                uint64_t key;
+                int64_t utt;
+                noise_row_key(dz, b, rlen, &key, &utt);
+                v += dither_draw(key, utt, f, n, dz.dither);
             }
         }
         st.s[i] = v;
         sum += v;
     }
-    const float mean = wave_sum(sum) / (float)kWin;
+    const float mean = wave_sum_rows(sum) / (float)kWin;
     float e = 0.f;
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
@@ -202,7 +172,7 @@ __device__ __forceinline__ void frame_forward(const MfccTables& t, const TabLdsT
             e = __builtin_fmaf(st.s[i], st.s[i], e);
         }
     }
-    st.energy = wave_sum(e);
+    st.energy = wave_sum_rows(e);
     const size_t gfi = (size_t)b * F + f;
     if (MODE == 1) {
 #pragma unroll
@@ -394,7 +364,7 @@ __global__ __launch_bounds__(MfccCfg<R>::kWaves * 64, CACHED ? MfccCfg<R>::kMinB
             ds[i] = g;
             sum += g;
         }
-        const float mean = wave_sum(sum) / (float)kWin;
+        const float mean = wave_sum_rows(sum) / (float)kWin;
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             const int n = lane + 64 * i;

@@ -1,24 +1,9 @@
 // Small memory-bound kernels around the TDNN contractions: input range check, CMVN, statistics
 // pooling (+backward), the fused PGD update.
 #include "sg_internal.h"
+#include "wave_reduce.h"
 
 namespace sg {
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ---------------------------------------------------------------- check_input_range (model/utils.py:7-19)
 // range_type='origin' (xv_plda.py:48): if 0.9*max <= 1 and 0.9*min >= -1 the batch is in the
@@ -56,8 +41,8 @@ __global__ __launch_bounds__(kScaleThreads) void input_range_partial_kernel(cons
         mx = fmaxf(mx, v);
         mn = fminf(mn, v);
     }
-    mx = wave_max_f(mx);
-    mn = wave_min_f(mn);
+    mx = wave_max_xor(mx);
+    mn = wave_min_xor(mn);
     if ((threadIdx.x & 63) == 0) {
         smax[threadIdx.x >> 6] = mx;
         smin[threadIdx.x >> 6] = mn;
@@ -76,8 +61,8 @@ __global__ __launch_bounds__(kScaleThreads) void input_range_partial_kernel(cons
 
 __global__ __launch_bounds__(256) void input_range_final_kernel(const float* __restrict__ part, float* scale, int mode) {
     __shared__ float smax[4], smin[4];
-    float mx = wave_max_f(part[threadIdx.x]);
-    float mn = wave_min_f(part[kScaleBlocks + threadIdx.x]);
+    float mx = wave_max_xor(part[threadIdx.x]);
+    float mn = wave_min_xor(part[kScaleBlocks + threadIdx.x]);
     if ((threadIdx.x & 63) == 0) {
         smax[threadIdx.x >> 6] = mx;
         smin[threadIdx.x >> 6] = mn;

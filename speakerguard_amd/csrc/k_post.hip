@@ -5,23 +5,11 @@
 #include <cstdio>
 
 #include "sg_internal.h"
+#include "wave_reduce.h"
 
 using namespace sg;
 
 namespace {
-
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, T* scratch, Op op) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) scratch[wid] = v;
-    __syncthreads();
-    T r = scratch[0];
-    for (int i = 1; i < nw; ++i) r = op(r, scratch[i]);
-    return r;
-}
 
 // One block per utterance.
 //   PCM (reference attackMain.py:154-166 save_audio): if 0.9*max <= 1 and 0.9*min >= -1 (per utterance)
@@ -48,9 +36,9 @@ __global__ __launch_bounds__(1024) void wav_finalize_kernel(const float* __restr
     }
     auto fmx = [](float x, float y) { return fmaxf(x, y); };
     auto fmn = [](float x, float y) { return fminf(x, y); };
-    amax = block_reduce(amax, sf, fmx);
-    amin = block_reduce(amin, sf, fmn);
-    gmax = block_reduce(gmax, sf, fmx);
+    amax = block_reduce_xor(amax, sf, fmx);
+    amin = block_reduce_xor(amin, sf, fmn);
+    gmax = block_reduce_xor(gmax, sf, fmx);
     const bool scale_pcm = 0.9f * amax <= 1.f && 0.9f * amin >= -1.f;
     const bool a_raw = -1.f <= amax && amax <= 1.f;  // metric.preprocess keeps the signal as is
     const bool g_raw = -1.f <= gmax && gmax <= 1.f;
@@ -77,11 +65,11 @@ __global__ __launch_bounds__(1024) void wav_finalize_kernel(const float* __restr
     if (!g || !metrics) return;
     auto dadd = [](double x, double y) { return x + y; };
     auto ladd = [](long long x, long long y) { return x + y; };
-    s2 = block_reduce(s2, sd, dadd);
-    s1 = block_reduce(s1, sd, dadd);
-    sb = block_reduce(sb, sd, dadd);
-    linf = block_reduce(linf, sf, fmx);
-    l0 = block_reduce(l0, sl, ladd);
+    s2 = block_reduce_xor(s2, sd, dadd);
+    s1 = block_reduce_xor(s1, sd, dadd);
+    sb = block_reduce_xor(sb, sd, dadd);
+    linf = block_reduce_xor(linf, sf, fmx);
+    l0 = block_reduce_xor(l0, sl, ladd);
     if (threadIdx.x == 0) {
         double* m = metrics + (size_t)b * 5;
         m[0] = sqrt(s2);

@@ -311,7 +311,7 @@ sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float2* spec,
         }
     }
     // the row's peak and count
-    for (int d = 32; d >= 1; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d)), cnt += __shfl_xor(cnt, d);
+    for (int d = 32; d >= 1; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d)), cnt += __shfl_xor(cnt, d);  // both butterflies in one loop, order 32 .. 1
     if ((tid & 63) == 0) red_f[tid >> 6] = pk, red_i[tid >> 6] = cnt;
     __syncthreads();
     if (tid == 0) {

@@ -45,6 +45,7 @@
 #include <cstring>
 
 #include "sg_internal.h"
+#include "wave_reduce.h"
 
 using namespace sg;
 
@@ -99,7 +100,7 @@ __global__ void __launch_bounds__(1024) ssa_quantise_kernel(const float* x, int 
     int16_t* qr = xq + (size_t)blockIdx.x * T;
     float hi = -INFINITY, lo = INFINITY;
     for (int i = tid; i < T; i += nt) hi = fmaxf(hi, xr[i]), lo = fminf(lo, xr[i]);
-    for (int d = 32; d >= 1; d >>= 1) hi = fmaxf(hi, __shfl_xor(hi, d)), lo = fminf(lo, __shfl_xor(lo, d));
+    for (int d = 32; d >= 1; d >>= 1) hi = fmaxf(hi, __shfl_xor(hi, d)), lo = fminf(lo, __shfl_xor(lo, d));  // both butterflies in one loop, order 32 .. 1
     if ((tid & 63) == 0) red_hi[tid >> 6] = hi, red_lo[tid >> 6] = lo;
     __syncthreads();
     hi = red_hi[0], lo = red_lo[0];
@@ -119,7 +120,7 @@ __global__ void __launch_bounds__(kSsaThreads) ssa_cov_row_kernel(const int16_t*
     const int16_t* x = xq + (size_t)blockIdx.y * T;
     long long acc = 0;
     for (int p = tid; p < t; p += kSsaThreads) acc += (long long)((int)x[p] * (int)x[p + lag]);
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);  // order 32 .. 1 (wave_sum_xor selects other instructions for this loop)
     if ((tid & 63) == 0) red[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -313,7 +314,7 @@ __global__ void __launch_bounds__(64) ssa_taps_kernel(const double* P, int W, do
     const double* Pb = P + b * W * W;
     double acc = 0.0;
     for (int i = i_lo + (int)threadIdx.x; i <= i_hi; i += 64) acc += Pb[(size_t)i * W + i + d];
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    acc = wave_sum_xor(acc);
     if (threadIdx.x == 0) h[b * (2 * (size_t)W - 1) + blockIdx.x] = acc;
 }
 
@@ -357,7 +358,7 @@ __global__ void __launch_bounds__(kSsaThreads) ssa_edge_kernel(const int16_t* xq
         const double* Pi = Pb + (size_t)i * W;
         for (int l = tid; l < W; l += kSsaThreads) acc = fma((double)xu[l], Pi[l], acc);
     }
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    acc = wave_sum_xor(acc);
     if ((tid & 63) == 0) red[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {

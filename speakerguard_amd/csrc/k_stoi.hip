@@ -24,7 +24,7 @@
 //   stoi_segments_kernel  grid B: the segment statistics and the final sum.
 //
 // Determinism: no atomics, no implicit contraction (the only fused multiply-adds are the written-out ones of the transform's complex
-// products, fft512t.h), every reduction in ONE order:
+// products, fft512.h), every reduction in ONE order:
 //   resampler      output m = 5 u + p: acc = 0; for j = 0 .. 122: acc += G[p][j] * x[8 u - 58 + j] (terms outside the signal or the
 //                  filter are exact zeros).
 //   sum of 256     (frame energy) lane l: ((a[l] + a[l+64]) + a[l+128]) + a[l+192]; then s += s(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.
@@ -34,8 +34,9 @@
 #include <cmath>
 #include <cstring>
 
-#include "fft512t.h"
+#include "fft512.h"
 #include "sg_internal.h"
+#include "wave_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -74,16 +75,6 @@ struct StoiGeo {
     int Mmax;           // row stride of the band values (>= nF - 1)
     int resample;
 };
-
-__device__ __forceinline__ double st_sum64(double s) {
-    s = s + __shfl_xor(s, 32, 64);
-    s = s + __shfl_xor(s, 16, 64);
-    s = s + __shfl_xor(s, 8, 64);
-    s = s + __shfl_xor(s, 4, 64);
-    s = s + __shfl_xor(s, 2, 64);
-    s = s + __shfl_xor(s, 1, 64);
-    return s;
-}
 
 // pmax[row][sig][slice] = the maximum of one eighth of the row (-inf for an empty slice)
 __global__ __launch_bounds__(kStThreads) void stoi_scale_kernel(const float* __restrict__ benign, const float* __restrict__ adver, int T,
@@ -169,7 +160,7 @@ __global__ __launch_bounds__(kStThreads) void stoi_resample_kernel(const StoiTab
             const double v = fr[lane + 64 * j] * ws[lane + 64 * j];
             a[j] = v * v;
         }
-        const double s = st_sum64(((a[0] + a[1]) + a[2]) + a[3]);
+        const double s = wave_sum_xor_steps(((a[0] + a[1]) + a[2]) + a[3]);
         if (lane == 0) en[(size_t)row * g.nF + f] = 20.0 * log10(sqrt(s) + kStEps);
     }
 }
@@ -343,8 +334,7 @@ void st_build(StoiTab* t) {
         }
     for (int i = 0; i < kStFrame; ++i) t->win[i] = 0.5 + 0.5 * std::cos(pi * (double)(2 * (i + 1) - (kStFrame + 1)) / (kStFrame + 1));
     auto w512 = [&](int m) { return make_double2(std::cos(2.0 * pi * (m % 512) / 512.0), -std::sin(2.0 * pi * (m % 512) / 512.0)); };
-    for (int i = 0; i < kFftTw1; ++i) t->tw1[i] = w512((i / 64 + 1) * (i % 64));
-    for (int i = 0; i < kFftTw2; ++i) t->tw2[i] = i % 9 < 8 ? w512(8 * (i / 9) * (i % 9)) : make_double2(0.0, 0.0);
+    fft512_twiddle_tables(w512, reinterpret_cast<double*>(t->tw1), reinterpret_cast<double*>(t->tw2));
     t->clip = 1.0 + std::pow(10.0, 15.0 / 20.0);
     // band b: bins [argmin |f - 150 2^((2 b - 1) / 6)|, argmin |f - 150 2^((2 b + 1) / 6)|), f_k = k 10000 / 512, first minimum
     auto nearest = [&](double f) {

@@ -18,6 +18,7 @@
 
 #include "loss_device.h"
 #include "sg_internal.h"
+#include "wave_reduce.h"
 
 namespace sg {
 
@@ -36,23 +37,11 @@ constexpr int kTailParts = kTailThreads / 256;
 constexpr int kTailEnrCache = 4096;  // floats of enrolled embeddings kept in LDS (S x D <= this: 10 x 200 in the recipes)
 static_assert(kTailThreads == 2 * kEmb && kTailParts >= 2, "step 1 splits the fc1 slabs over two half-blocks");
 
-// Sum over the 64 lanes, the same value in every lane: DPP butterfly inside the rows of 16 lanes, the four row sums
-// through scalar registers (k_mfcc.hip wave_sum) -- no LDS round trips.
-__device__ __forceinline__ float tail_wave_sum(float v) {
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-// Block sum: sixteen wave sums, combined in wave order.  Ends with a barrier; valid on every thread.
+// Block sum: sixteen wave sums (wave_sum_rows, not the xor butterfly), combined in wave order STARTING FROM +0 (0.f + w0 + w1
+// ...: a -0 sum comes out as +0) -- neither is block_reduce_xor's order (wave_reduce.h), so this site keeps its own form.
+// Ends with a barrier; valid on every thread.
 __device__ __forceinline__ float block_sum(float v, float* red) {
-    v = tail_wave_sum(v);
+    v = wave_sum_rows(v);
     __syncthreads();  // (red may still be read by an earlier phase)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(TailModelDev m, cons
         const float l2pi = logf(2.f * 3.1415926f) * (float)D;  // plda.py:179 (cancels in the ratio)
         float s0 = 0.f;  // sum e5^2 / (psi + 1)
         for (int d = lane; d < D; d += 64) s0 += e5[d] * e5[d] * (1.f / (c_psi[d] + 1.f));
-        s0 = tail_wave_sum(s0);
+        s0 = wave_sum_rows(s0);
         const float without = -0.5f * (m.logdet_without + l2pi + s0);
         for (int s = wid; s < S; s += NT / 64) {
             float s1 = 0.f;
@@ -257,7 +246,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(TailModelDev m, cons
                 const float df = e5[d] - r * enr[(size_t)s * D + d];
                 s1 += df * df * (1.f / (1.f + r));
             }
-            s1 = tail_wave_sum(s1);
+            s1 = wave_sum_rows(s1);
             if (lane == 0) {
                 const float given = -0.5f * (m.logdet_given + l2pi + s1);
                 const float v = given - without;

@@ -39,6 +39,7 @@
 #include <cstdio>
 
 #include "philox.h"
+#include "wave_reduce.h"
 #include "sg_internal.h"
 
 // every sequence above names its roundings: nothing may be contracted behind its back (the chains use fmaf explicitly)
@@ -135,8 +136,8 @@ __global__ __launch_bounds__(kTdBlock) void td_ms_bwd_kernel(const float* __rest
 __device__ __forceinline__ float at_normal(uint64_t key, int64_t utt, int t) {
     uint32_t w1;
     const uint32_t w0 = philox4x32_10_w01(key, (uint32_t)t, kAtDomain, (uint32_t)utt, (uint32_t)((uint64_t)utt >> 32), &w1);
-    const float u0 = ((float)(w0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u0 = philox_unit24(w0);
+    const float u1 = philox_unit24(w1);
     return sqrtf(-2.f * logf(u0)) * cosf(6.283185307179586f * u1);
 }
 
@@ -146,25 +147,13 @@ struct AtNoise {
     int64_t index_base, row_base;
     int rep_rows;
 };
-// (key, utterance) of row b: sg_dither's derivation
+// (key, utterance) of row b: sg_dither's derivation, as noise_row_key of philox.h (kept in this form: these kernels were
+// compiled from it, and the shared function's statement order schedules them differently)
 __device__ __forceinline__ void at_row_key(const AtNoise& nz, int b, uint64_t* key, int64_t* utt) {
     const int64_t g = nz.row_base + b;
     const int64_t rep = nz.rep_rows > 0 ? g / nz.rep_rows : 0;
-    *key = nz.seed + (uint64_t)rep * 0xC2B2AE3D27D4EB4Full;
+    *key = nz.seed + (uint64_t)rep * kRepKey;
     *utt = nz.index_base + (g - rep * nz.rep_rows);
-}
-
-// the reduction tree of the header: the caller's per-thread partial (terms j, j + 1024, ... added in order) -> the row's sum
-// in every thread
-__device__ __forceinline__ float td_row_sum(float acc, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    float s = red[0];
-#pragma unroll
-    for (int w = 1; w < kTdRowThreads / 64; ++w) s = s + red[w];
-    return s;
 }
 
 // saved[b] = sigma[b], saved[B + b] = P[b]; one block per utterance
@@ -178,7 +167,7 @@ __global__ __launch_bounds__(kTdRowThreads) void td_at_power_kernel(const float*
         const float v = row[i] * c;
         acc = acc + v * v;
     }
-    const float P = td_row_sum(acc, red);
+    const float P = block_reduce_xor<kTdRowThreads / 64, false>(acc, red, OpSum());
     if (threadIdx.x == 0) {
         saved[b] = sqrtf(__fdiv_rn(P, snr));  // (sqrtf is the correctly rounded one here; __fsqrt_rn compiles to the bare 1-ulp instruction)
         saved[B + b] = P;
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(kTdRowThreads) void td_at_dot_kernel(const float* _
         const float n = nz.given ? nz.given[base + i] : at_normal(key, utt, i);
         acc = acc + g[base + i] * n;
     }
-    const float dot = td_row_sum(acc, red);
+    const float dot = block_reduce_xor<kTdRowThreads / 64, false>(acc, red, OpSum());
     if (threadIdx.x == 0) {
         const float sigma = saved[b], P = saved[B + b];
         saved[2 * B + b] = P == 0.f ? 0.f : __fdiv_rn(dot, ((float)T * snr) * sigma);

@@ -110,17 +110,12 @@ int build_tables(sg_ctx* ctx) {
     auto fill_image = [&](auto& img) {
         using R = std::remove_reference_t<decltype(img.tw1[0])>;
         std::memset(&img, 0, sizeof(img));
-        auto w512 = [&](int m, R* out) {  // W512^m from the half circle (W^(m + 256) = -W^m), rounded once to R
+        auto w512 = [&](int m) {  // W512^m from the half circle (W^(m + 256) = -W^m)
             const double2 w = tw[m & 255];
             const double f = (m & 256) ? -1.0 : 1.0;
-            out[0] = (R)(f * w.x);
-            out[1] = (R)(f * w.y);
+            return make_double2(f * w.x, f * w.y);
         };
-        for (int i = 0; i < kMfccTw1; ++i) w512((i / 64 + 1) * (i % 64), &img.tw1[2 * i]);
-        for (int i = 0; i < kMfccTw2; ++i) {
-            const int b = i / 9, c = i - 9 * b;
-            if (c < 8) w512(8 * b * c, &img.tw2[2 * i]);
-        }
+        fft512_twiddle_tables<R>(w512, img.tw1, img.tw2);
         for (int n = 0; n < kWin; ++n) img.window[n] = window[n];
         for (int i = 0; i < kMel * kCep; ++i) img.dct[i] = dct[i];
         for (int c = 0; c < kCep; ++c)

@@ -112,20 +112,15 @@ int an_build_tables(sg_ctx* ctx) {
         rc |= dev_upload(ctx, pool, &t.lane_melw, lmelw);
         rc |= dev_upload(ctx, pool, &t.lane_k0, lk0);
     }
-    {   // twiddle tables of the 512-point complex transform (W512^m = W1024^(2 m)), as fft512_fill_tables lays them out
+    {   // twiddle tables of the 512-point complex transform (W512^m = W1024^(2 m)), float64 and the same rounded once to float32
         auto w512 = [&](int m) {
             const double2 w = tw[(2 * (m & 255)) % (kAnFft / 2)];
             return (m & 256) ? make_double2(-w.x, -w.y) : w;
         };
-        std::vector<double2> t1(7 * 64), t2(72);
-        std::vector<float2> t1f(7 * 64), t2f(72);
-        for (int i = 0; i < 7 * 64; ++i) t1[i] = w512((i / 64 + 1) * (i % 64));
-        for (int i = 0; i < 72; ++i) {
-            const int b = i / 9, c = i - 9 * b;
-            t2[i] = c < 8 ? w512(8 * b * c) : make_double2(0.0, 0.0);
-        }
-        for (int i = 0; i < 7 * 64; ++i) t1f[i] = make_float2((float)t1[i].x, (float)t1[i].y);
-        for (int i = 0; i < 72; ++i) t2f[i] = make_float2((float)t2[i].x, (float)t2[i].y);
+        std::vector<double2> t1(kFftTw1), t2(kFftTw2);
+        std::vector<float2> t1f(kFftTw1), t2f(kFftTw2);
+        fft512_twiddle_tables(w512, reinterpret_cast<double*>(t1.data()), reinterpret_cast<double*>(t2.data()));
+        fft512_twiddle_tables(w512, reinterpret_cast<float*>(t1f.data()), reinterpret_cast<float*>(t2f.data()));
         rc |= dev_upload(ctx, pool, &t.tw1d, t1);
         rc |= dev_upload(ctx, pool, &t.tw2d, t2);
         rc |= dev_upload(ctx, pool, &t.tw1f, t1f);

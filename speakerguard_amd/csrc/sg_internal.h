@@ -52,6 +52,26 @@ struct DevBuf {
     operator T*() const { return ptr; }
 };
 
+// ---------------------------------------------------------------- the FFT-512's twiddle tables (fft512.h)
+// The one place that knows their layout: tw1[(j - 1) * 64 + lane] = W512^(j lane), j = 1 .. 7, and tw2[9 b + c] = W64^(b c) =
+// W512^(8 b c), b, c < 8, the pad entry (c = 8) zero; (re, im) pairs of T, forward sign.  w512(m) is the CALLER's float64
+// W512^m (a double2, m < 512) -- from a half-circle table or from cos / sin, which can differ in the last bit -- rounded once to T.
+constexpr int kFftTw1 = 7 * 64, kFftTw2 = 72;
+template <typename T, typename W>
+inline void fft512_twiddle_tables(W w512, T* tw1, T* tw2) {
+    auto put = [&](int m, T* out) {
+        const double2 w = w512(m);
+        out[0] = (T)w.x;
+        out[1] = (T)w.y;
+    };
+    for (int i = 0; i < kFftTw1; ++i) put((i / 64 + 1) * (i % 64), tw1 + 2 * i);
+    for (int i = 0; i < kFftTw2; ++i) {
+        const int b = i / 9, c = i - 9 * b;
+        if (c < 8) put(8 * b * c, tw2 + 2 * i);
+        else tw2[2 * i] = tw2[2 * i + 1] = (T)0;
+    }
+}
+
 // ---------------------------------------------------------------- AudioNet CSI-NE (model/audionet_csine.py)
 constexpr int kAnFft = 1024, kAnHop = 160, kAnWin = 800, kAnMel = 32, kAnBins = 513;  // Preprocessor.py:13-23
 constexpr int kAnConv = 7;                                                              // conv2 .. conv8
@@ -180,7 +200,7 @@ struct AnWorkspace {
 // The MFCC kernels' constant tables exactly as they sit in a block's LDS (k_mfcc.hip), built once on the host per transform
 // precision R and copied into LDS with 16-byte loads by every block (round 6; rounds 1-5 derived them per block from the raw
 // tables -- dependent global look-ups in front of the first frame).
-constexpr int kMfccTw1 = 7 * 64, kMfccTw2 = 72;  // = kFftTw1, kFftTw2 (fft512.h)
+constexpr int kMfccTw1 = kFftTw1, kMfccTw2 = kFftTw2;
 constexpr int kMelLaneBins = 24;  // >= bins per half mel filter (21 for 30 filters, 20-7600 Hz, 512-point FFT; host-checked)
 template <typename R>
 struct MfccLdsImage {
