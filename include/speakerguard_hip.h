@@ -247,6 +247,44 @@ int sg_fakebob_step(sg_ctx* ctx, float* x_dev, float* grad_dev, const float* pre
                     const float* lr_dev, const float* lower_dev, const float* upper_dev, int32_t n, int32_t T,
                     float momentum, float one_minus_momentum, int32_t grad_sign, void* stream);
 
+/* ---- SirenAttack's particle swarm, resident on the device (attack/SirenAttack.py:40-188; k_pso.hip states the whole
+ * contract).  State of a chunk of n <= 256 utterances with P <= 1024 particles, float32, each utterance in its own slot
+ * for the whole chunk: loc, vel, pbest_loc (n,P,T); gbest_loc (n,T); pbest (n,P); gbest (n).  x, lower, upper: (n,T).
+ * rows_host (n_active): the slots still attacked (consider_index), a HOST array like every `_host` argument: distinct, in
+ * 0 .. n-1, checked before any launch.  Per-row arrays (loss, improved, report, given draws) and the queries
+ * (n_active*P, T) = loc + x are dense in the order of that list.  Draws: `*_in` given -> used exactly as given; NULL ->
+ * Philox4x32-10, counter (t, particle, index_base + slot), key `key` (one key per draw number, from the host); words 0 / 1
+ * through ((w >> 8) + 0.5) / 2^24 give position / velocity (init) or r1 - 1e-5f / r2 - 1e-5f (move).
+ *
+ * sg_pso_init (:66-86), one launch.  epoch 0: pbest_loc = positions, U[lower, upper) per sample (pos_in: (n_active,P,T)),
+ * pbest = +inf.  epoch > 0: particle 0 takes location and value of particle best_index_host[k] (the first-index argmin of
+ * pbest, sg_pso_select's report), particles 1 .. P-1 are fresh (pos_in: (n_active,P-1,T)).  Then loc = pbest_loc,
+ * vel ~ U[-|lower-upper|, |lower-upper|) (vel_in: (n_active,P,T)), and the queries. */
+int sg_pso_init(sg_ctx* ctx, const float* x_dev, const float* lower_dev, const float* upper_dev, int32_t n, int32_t P,
+                int32_t T, const int32_t* rows_host, int32_t n_active, int32_t epoch, const int32_t* best_index_host,
+                uint64_t key, int64_t index_base, const float* pos_in_dev, const float* vel_in_dev, float* loc_dev,
+                float* vel_dev, float* pbest_loc_dev, float* pbest_dev, float* queries_dev, void* stream);
+
+/* :115-132, the scalar work, one small launch.  loss (n_active,P): pbest = loss where loss < pbest (strict), improved
+ * (n_active*P bytes) = that; gbest = min pbest where it is < gbest (strict).  report (3, n_active) floats: the row's gbest
+ * after the update; the first-index argmin of its new pbest; gbest_from = that argmin where gbest was updated, else -1
+ * (the integers are exact in a float).  The one read the host needs per iteration (:138-161). */
+int sg_pso_select(sg_ctx* ctx, const float* loss_dev, int32_t n, int32_t P, const int32_t* rows_host, int32_t n_active,
+                  float* pbest_dev, float* gbest_dev, uint8_t* improved_dev, float* report_dev, void* stream);
+
+/* :121, :131, :163-174, ONE streaming launch that touches each state element at most once.  For every row of the list (the
+ * active set sg_pso_select saw): pbest_loc = loc where improved; gbest_loc = the new pbest_loc of particle
+ * gbest_from_host[k] where that is >= 0.  Then, if do_move (iter < max_iter), for the rows with continue_host[k] != 0 (not
+ * found: gbest >= 0), in float32 without contraction: vel = (w vel + (c1 r1)(pbest_loc - loc)) + (c2 r2)(gbest_loc - loc),
+ * loc = min(max(loc + vel, lower), upper), and the next queries, dense over the continuing rows in list order (as are
+ * r1_in, r2_in: (n_continue,P,T)).  queries_dev may be NULL when nothing moves. */
+int sg_pso_move(sg_ctx* ctx, const float* x_dev, const float* lower_dev, const float* upper_dev, int32_t n, int32_t P,
+                int32_t T, const int32_t* rows_host, int32_t n_active, const int32_t* gbest_from_host,
+                const int32_t* continue_host, int32_t do_move, float w, float c1, float c2, uint64_t key,
+                int64_t index_base, const float* r1_in_dev, const float* r2_in_dev, const uint8_t* improved_dev,
+                float* loc_dev, float* vel_dev, float* pbest_loc_dev, float* gbest_loc_dev, float* queries_dev,
+                void* stream);
+
 /* ---- fused attack loop ----------------------------------------------------------------------
  * attack/FGSM.py:38-70 attack_batch for the xv_plda model: max_iter gradient steps plus the final
  * forward-only pass, entirely on the device (FGSM = max_iter 1, step_size epsilon). */

@@ -31,6 +31,7 @@ EXPORTS = (
     "sg_wav_spectrum", "sg_wav_spectrum_gate",
     "sg_ssa_window", "sg_ssa_decompose", "sg_ssa_reconstruct",
     "sg_wav_stoi", "sg_stoi_debug_tables",
+    "sg_pso_init", "sg_pso_select", "sg_pso_move",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -185,6 +186,10 @@ def load():
         "sg_nes_queries": (C.c_int, [vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i64, i32, vp, vp, vp, vp]),
         "sg_nes_grad": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_uint64, i64, i32, vp, i32, f32, i32, vp, vp]),
         "sg_fakebob_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp]),
+        "sg_pso_init": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, C.c_uint64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sg_pso_select": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "sg_pso_move": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, f32, f32, f32, C.c_uint64, i64, vp, vp, vp,
+                                  vp, vp, vp, vp, vp, vp]),
         "sg_an_load": (C.c_int, [vp, C.POINTER(AnWeights)]),
         "sg_an_num_frames": (i32, [i32]),
         "sg_an_logmel": (C.c_int, [vp, vp, i32, i32, vp, vp]),

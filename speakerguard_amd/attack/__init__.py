@@ -1,0 +1,1 @@
+from .SirenAttack import SirenAttack  # noqa: F401

@@ -1,5 +1,5 @@
 """What every engine-backed model shares: the native attack-state updates (C-ABI: sg_pgd_update, sg_cw2_step,
-sg_nes_queries, sg_nes_grad, sg_fakebob_step), which the attack classes call through the model so
+sg_nes_queries, sg_nes_grad, sg_fakebob_step, sg_pso_init / _select / _move), which the attack classes call through the model so
 that the only implementation in the product is the HIP one (tests substitute a CPU double), the noise
 bookkeeping, and the ONE marshalling path from a model's ``pgd_run*`` methods to its device-resident PGD
 loops (``_pgd_loop``)."""
@@ -296,6 +296,47 @@ class EngineOps:
         self.ctx.call("sg_nes_grad", N._ptr(loss), n, T, half, int(with_clean), C.c_uint64(seed), int(index_base), int(pair_base),
                       N._ptr(noise_in), int(accumulate), float(final_sigma), int(final_batches), N._ptr(grad), self._stream())
         return grad
+
+    # ---- SirenAttack's swarm (csrc/k_pso.hip).  `st`: attack.SirenAttack.SwarmState, the chunk's state tensors, every utterance
+    # in its slot; `rows`: the slots still attacked; x, lower, upper: (n, 1, T) of the whole chunk.
+    @staticmethod
+    def _i32(v):
+        return np.ascontiguousarray(np.asarray(v, dtype=np.int32))
+
+    def pso_init(self, st, x, lower, upper, rows, epoch, best_index, key, index_base=0, pos_in=None, vel_in=None):
+        """attack/SirenAttack.py:66-86 -> the epoch's first queries (len(rows) * P, 1, T)"""
+        n, P, T = st.loc.shape
+        rows, best_index = self._i32(rows), None if best_index is None else self._i32(best_index)
+        queries = torch.empty(len(rows) * P, 1, T, device=x.device, dtype=torch.float32)
+        self.ctx.call("sg_pso_init", N._ptr(x), N._ptr(lower), N._ptr(upper), n, P, T, rows.ctypes.data_as(C.c_void_p), len(rows),
+                      int(epoch), None if best_index is None else best_index.ctypes.data_as(C.c_void_p), C.c_uint64(key),
+                      int(index_base), N._ptr(pos_in), N._ptr(vel_in), N._ptr(st.loc), N._ptr(st.vel), N._ptr(st.pbest_loc),
+                      N._ptr(st.pbest), N._ptr(queries), self._stream())
+        return queries
+
+    def pso_select(self, st, loss, rows):
+        """:115-132 on loss (len(rows), P); ``st.improved`` keeps who improved for ``pso_move``.  Returns host arrays
+        (gbest of the rows, first-index argmin of their pbest, gbest_from): the iteration's one device-to-host read."""
+        n, P, _ = st.loc.shape
+        rows = self._i32(rows)
+        st.improved = torch.empty(len(rows) * P, device=loss.device, dtype=torch.uint8)
+        report = torch.empty(3, len(rows), device=loss.device, dtype=torch.float32)
+        self.ctx.call("sg_pso_select", N._ptr(loss), n, P, rows.ctypes.data_as(C.c_void_p), len(rows), N._ptr(st.pbest),
+                      N._ptr(st.gbest), N._ptr(st.improved), N._ptr(report), self._stream())
+        report = report.cpu().numpy()
+        return report[0].copy(), report[1].astype(np.int32), report[2].astype(np.int32)
+
+    def pso_move(self, st, x, lower, upper, rows, gbest_from, cont, do_move, w, c1, c2, key, index_base=0, r1_in=None, r2_in=None):
+        """:121, :131, :163-174 in one launch -> the next queries (rows that continue * P, 1, T), None when nothing moves"""
+        n, P, T = st.loc.shape
+        rows, gbest_from, cont = self._i32(rows), self._i32(gbest_from), self._i32(cont)
+        n_cont = int(np.count_nonzero(cont)) if do_move else 0
+        queries = torch.empty(n_cont * P, 1, T, device=x.device, dtype=torch.float32) if n_cont else None
+        self.ctx.call("sg_pso_move", N._ptr(x), N._ptr(lower), N._ptr(upper), n, P, T, rows.ctypes.data_as(C.c_void_p), len(rows),
+                      gbest_from.ctypes.data_as(C.c_void_p), cont.ctypes.data_as(C.c_void_p), int(bool(do_move)), float(w), float(c1),
+                      float(c2), C.c_uint64(key), int(index_base), N._ptr(r1_in), N._ptr(r2_in), N._ptr(st.improved), N._ptr(st.loc),
+                      N._ptr(st.vel), N._ptr(st.pbest_loc), N._ptr(st.gbest_loc), N._ptr(queries), self._stream())
+        return queries
 
     def fakebob_step(self, x, grad, prev_grad, lr, lower, upper, momentum, grad_sign):
         """attack/FAKEBOB.py:93-104; grad and x are updated in place."""

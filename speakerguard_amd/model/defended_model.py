@@ -240,3 +240,12 @@ class defended_model:
 
     def fakebob_step(self, *a, **k):
         return self.base_model.fakebob_step(*a, **k)
+
+    def pso_init(self, *a, **k):
+        return self.base_model.pso_init(*a, **k)
+
+    def pso_select(self, *a, **k):
+        return self.base_model.pso_select(*a, **k)
+
+    def pso_move(self, *a, **k):
+        return self.base_model.pso_move(*a, **k)
