@@ -903,6 +903,65 @@ int sg_xv_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
                        uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
                        float* loss_trace_dev, int64_t* decision_trace_dev, void* stream);
 
+/* ---- GMM / i-vector / PLDA system (reference model/iv_plda.py), FORWARD ONLY (csrc/k_ivector.hip) -------------------------
+ * raw MFCC (the first 24 cepstra of sg_xv_mfcc's 30: same mel bank, lifter and energy) -> delta + delta-delta (window 3,
+ * replicate edges, 72 columns) -> sliding 300-frame CMVN -> full-covariance GMM posteriors (no Gaussian pruning) ->
+ * Baum-Welch statistics n (C), f (C, 72) -> i-vector w = L^-1 lin with L = I + sum_c n_c M_c^T Sigma_c^-1 M_c and
+ * lin = sum_c M_c^T Sigma_c^-1 f_c (+ offset on entry 0, taken off w[0] again) -> mean subtraction, LDA, length
+ * normalisation, PLDA transform and scores, decision.  The gradient is not built: there is no backward entry.
+ * An utterance's result is one fixed sequence of operations: it depends neither on B, nor on the row's place in the call, nor
+ * on how the library cuts a large call into chunks (the workspace holds at most 64 utterances and 256 MiB of log-likelihoods).
+ * All pointers of sg_iv_weights are HOST fp32 in the reference's layouts. */
+#define SG_IV_FLAG_WAV 0   /* x: (B,1,T) waveform                                  */
+#define SG_IV_FLAG_RAW 1   /* x: (B,F,24) raw MFCC                                 */
+#define SG_IV_FLAG_DELTA 2 /* x: (B,F,72) raw + delta + delta-delta                */
+#define SG_IV_FLAG_CMVN 3  /* x: (B,F,72) CMVN-normalised                          */
+typedef struct sg_iv_weights {
+    int32_t C;                    /* Gaussians, 1 .. 4096                                                     */
+    int32_t R;                    /* i-vector dimension, 1 .. 1024                                            */
+    int32_t D;                    /* LDA / PLDA dimension, 1 .. 512                                           */
+    int32_t S;                    /* enrolled speakers, 1 .. 1024                                             */
+    const float* gconsts;         /* (C)          _iv_plda/gmm.py <GCONSTS>                                   */
+    const float* means_invcovars; /* (C, 72)      <MEANS_INVCOVARS>                                           */
+    const float* invcovars;       /* (C, 72, 72)  <INV_COVARS>, full symmetric matrices                       */
+    const float* extractor;       /* (C, 72, R)   _iv_plda/ivector_extract.py <M>                             */
+    const float* sigma_inv;       /* (C, 72, 72)  <SigmaInv>, full symmetric matrices                         */
+    float ivector_offset;         /* <IvectorOffset>                                                          */
+    const float* emb_mean;        /* (R)                                                                      */
+    const float* lda;             /* (D, R + 1) last column = offset (iv_plda.py:423-435)                     */
+    const float* plda_mean;       /* (D)                                                                      */
+    const float* plda_transform;  /* (D, D)                                                                   */
+    const float* plda_psi;        /* (D)                                                                      */
+    const float* enroll;          /* (S, D) processed enrolment embeddings                                    */
+    float threshold;              /* -INFINITY for CSI                                                        */
+} sg_iv_weights;
+/* Packs the model for the kernels (float64 on the host, rounded once): W_c = [mi_c ; -S_c,ii / 2 ; -S_c,ij (i < j)],
+ * V_c = M_c^T Sigma_c^-1 and the upper triangle of U_c = V_c M_c.  SG_ERR_ARG: a NULL pointer, a size outside the bounds above,
+ * a non-finite entry, or an invcovars / sigma_inv matrix that is not symmetric (|a_ij - a_ji| > 1e-6 max(|a_ij|, |a_ji|)). */
+int sg_iv_load(sg_ctx* ctx, const sg_iv_weights* w);
+/* as sg_xv_set_enroll / sg_xv_enroll_override, for the i-vector model's table (S, D) */
+int sg_iv_set_enroll(sg_ctx* ctx, const float* enroll_host, int32_t S, float threshold);
+int sg_iv_enroll_override(sg_ctx* ctx, const float* enroll_dev, int32_t S);
+/* add_delta + cmvn (iv_plda.py:248-377) in one launch: raw (B, F, ld) device rows of which the first 24 columns are read
+ * (ld = 30: sg_xv_mfcc's output, ld = 24: a caller's), delta_dev (B, F, 72) or NULL, cmvn_dev (B, F, 72) or NULL.
+ * SG_ERR_ARG before any launch: a NULL input, both outputs NULL, B outside 1 .. 2^20, F outside 1 .. 65535, ld outside 24 .. 4096. */
+int sg_iv_delta_cmvn(sg_ctx* ctx, const float* raw_dev, int32_t B, int32_t F, int32_t ld, float* delta_dev, float* cmvn_dev,
+                     void* stream);
+/* FullGMM.Zeroth_First_Stats (gmm.py:166-171) of CMVN features (B, F, 72): zeroth_dev (B, C), first_dev (B, C, 72). */
+int sg_iv_stats(sg_ctx* ctx, const float* cmvn_dev, int32_t B, int32_t F, float* zeroth_dev, float* first_dev, void* stream);
+/* ivectorExtractor.Extractivector (ivector_extract.py:98-114): (B, C), (B, C, 72) -> ivector_dev (B, R) */
+int sg_iv_extract(sg_ctx* ctx, const float* zeroth_dev, const float* first_dev, int32_t B, float* ivector_dev, void* stream);
+/* model.make_decision / score / embedding.  flag: SG_IV_FLAG_*; T_or_F: samples (flag 0, >= 400) or frames.  Any output may be
+ * NULL: decisions (B) int64, scores (B, S), emb (B, D) processed embedding, ivector (B, R) the raw i-vector.
+ * SG_ERR_STATE without a model; SG_ERR_ARG before any launch: x NULL, B outside 1 .. 2^20, a flag outside 0 .. 3, T < 400 or
+ * T > 2^24, F outside 1 .. 65535. */
+int sg_iv_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, int32_t flag, const sg_dither* dither,
+                  int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* ivector_dev, void* stream);
+/* sg_iv_forward plus the per-utterance loss of `loss` (y_dev (B) int64 labels); no gradient argument: not built. */
+int sg_iv_loss(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
+               const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

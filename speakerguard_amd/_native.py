@@ -32,6 +32,8 @@ EXPORTS = (
     "sg_ssa_window", "sg_ssa_decompose", "sg_ssa_reconstruct",
     "sg_wav_stoi", "sg_stoi_debug_tables",
     "sg_pso_init", "sg_pso_select", "sg_pso_move",
+    "sg_iv_load", "sg_iv_set_enroll", "sg_iv_enroll_override", "sg_iv_delta_cmvn", "sg_iv_stats", "sg_iv_extract",
+    "sg_iv_forward", "sg_iv_loss",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -121,6 +123,15 @@ class ResampleStage(C.Structure):
 
 class WavResample(C.Structure):
     _fields_ = [("down", ResampleStage), ("up", ResampleStage), ("same_size", C.c_int32)]
+
+
+class IvWeights(C.Structure):
+    """sg_iv_weights (the entry takes it as a plain pointer: byref(IvWeights))"""
+    _fields_ = [("C", C.c_int32), ("R", C.c_int32), ("D", C.c_int32), ("S", C.c_int32),
+                ("gconsts", C.c_void_p), ("means_invcovars", C.c_void_p), ("invcovars", C.c_void_p), ("extractor", C.c_void_p),
+                ("sigma_inv", C.c_void_p), ("ivector_offset", C.c_float), ("emb_mean", C.c_void_p), ("lda", C.c_void_p),
+                ("plda_mean", C.c_void_p), ("plda_transform", C.c_void_p), ("plda_psi", C.c_void_p), ("enroll", C.c_void_p),
+                ("threshold", C.c_float)]
 
 
 class _WavStageU(C.Union):
@@ -231,6 +242,14 @@ def load():
         "sg_ssa_window": (i32, [i32]),
         "sg_ssa_decompose": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "sg_ssa_reconstruct": (C.c_int, [vp, vp, vp, C.POINTER(i32), i32, i32, vp, vp, vp]),
+        "sg_iv_load": (C.c_int, [vp, vp]),  # (the weights: byref(IvWeights))
+        "sg_iv_set_enroll": (C.c_int, [vp, vp, i32, f32]),
+        "sg_iv_enroll_override": (C.c_int, [vp, vp, i32]),
+        "sg_iv_delta_cmvn": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "sg_iv_stats": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
+        "sg_iv_extract": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+        "sg_iv_forward": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(Dither), vp, vp, vp, vp, vp]),
+        "sg_iv_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither), vp, vp, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

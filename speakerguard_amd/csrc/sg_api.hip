@@ -850,6 +850,8 @@ void sg_destroy(sg_ctx* ctx) {
     ctx->stoi_cache.clear();
     free_pool(ctx->an_ws.allocs);  // (leaked until round 4: found by the sanitizer build's leak check, `make asan`)
     free_pool(ctx->xv.allocs);
+    free_pool(ctx->iv.allocs);
+    free_pool(ctx->iv_ws.allocs);
     free_pool(ctx->model_allocs);
     if (ctx->err_host) (void)hipHostFree(ctx->err_host);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

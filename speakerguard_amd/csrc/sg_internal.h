@@ -336,6 +336,72 @@ struct DevTableCache {
     }
 };
 
+// ---------------------------------------------------------------- GMM / i-vector / PLDA system (k_ivector.hip, sg_api_ivector.hip)
+constexpr int kIvCep = 24;                        // cepstra read from a raw row (iv_plda.py:230)
+constexpr int kIvDim = 72;                        // raw + delta + delta-delta
+constexpr int kIvK = kIvDim + kIvDim * (kIvDim + 1) / 2;  // 2700: z = [x ; x_i x_j (i <= j)]
+constexpr int kIvMaxC = 4096, kIvMaxR = 1024, kIvMaxD = 512;
+constexpr int kIvLinSlice = 16;                   // components per partial sum of lin (a constant of the arithmetic): 64 left the
+                                                  // launch at 256 blocks of one long dependent chain each, 2.7 ms at C 2048, R 400, B 64
+constexpr int kIvChunkMax = 64;                   // utterances per chunk of a call, at most
+// packed index of (i, j), i <= j, in the upper triangle of an n x n matrix stored row by row
+inline size_t iv_tri(int i, int j, int n) { return (size_t)i * n - (size_t)i * (i - 1) / 2 + (j - i); }
+// position of the product x_i x_j (i <= j < 72) in z, after the 72 linear terms
+inline int iv_zpos(int i, int j) { return kIvDim + (int)iv_tri(i, j, kIvDim); }
+
+struct IvModel {
+    bool loaded = false;
+    int C = 0, Cp = 0;          // Gaussians, rounded up to a multiple of 64 (the loglik kernel's wave tile)
+    int R = 0, P = 0, Pp = 0;   // i-vector dimension, R (R + 1) / 2, P rounded up to a multiple of 256
+    int D = 0, S = 0;
+    float offset = 0.f, threshold = 0.f, logdet_given = 0.f, logdet_without = 0.f;
+    float* gconst = nullptr;    // [C]
+    float* W = nullptr;         // [kIvK][Cp] k-major, zero columns past C
+    uint16_t* pairs = nullptr;  // [kIvK]: i | j << 8 with z_k = x_i x_j, x_72 = 1 (the linear terms)
+    float* Vt = nullptr;        // [C * 72][R]: V_c^T, V_c = M_c^T Sigma_c^-1
+    float* U = nullptr;         // [C][Pp]: upper triangle of V_c M_c, zero past P
+    float* emb_mean = nullptr;  // [R]
+    float* lda_t = nullptr;     // [R + 1][D] (row R: the offset column)
+    float* plda_mean = nullptr; // [D]
+    float* plda_pt = nullptr;   // [D][D] transposed
+    float* plda_psi = nullptr;  // [D]
+    float* enroll = nullptr;    // [S][D]
+    int enroll_cap = 0;
+    const float* enroll_override = nullptr;
+    int S_override = 0;
+    std::vector<void*> allocs;
+};
+// chunk buffers, grown on demand before the first launch of a call
+struct IvWorkspace {
+    DevBuf<float> scale, raw, delta, cmvn, ll, rowmax, rowsum, n, f, ivec;
+    DevBuf<double> Lmat, linpart;
+    std::vector<void*> allocs;
+};
+// utterances per chunk for F frames and C Gaussians: a pure function (the host double walks it)
+inline int iv_chunk_rows(int F, int C) {
+    const size_t per_utt = (size_t)F * C * sizeof(float);
+    const size_t fit = ((size_t)256 << 20) / (per_utt ? per_utt : 1);
+    return (int)std::max<size_t>(1, std::min<size_t>(kIvChunkMax, fit));
+}
+struct IvDeltaScales { float s1[7], s2[13]; };  // get_scales(window 3, order 2), iv_plda.py:277-293, in its float32 order
+IvDeltaScales iv_delta_scales();
+// What sg_iv_load derives from the reference's arrays, on the host in float64 rounded once: W [kIvK][Cp], Vt [C * 72][R],
+// U [C][Pp], pairs [kIvK].  false + text: a non-finite or asymmetric matrix.
+bool iv_pack_model(const sg_iv_weights* w, int Cp, int Pp, std::vector<float>* W, std::vector<uint16_t>* pairs, std::vector<float>* Vt,
+                   std::vector<float>* U, std::string* why);
+hipError_t launch_iv_delta_cmvn(const float* raw, int ld, int B, int F, float* delta_ws, float* delta_out, float* cmvn_out,
+                                hipStream_t s);
+hipError_t launch_iv_stats(const IvModel& m, const float* cmvn, int B, int F, float* ll, float* rowmax, float* rowsum, float* n,
+                           float* f, hipStream_t s);
+hipError_t launch_iv_extract(const IvModel& m, const float* n, const float* f, int B, double* Lmat, double* linpart, float* ivec,
+                             hipStream_t s);
+struct IvTailArgs {
+    const float* ivec; int B;
+    const int64_t* y; sg_loss_spec loss; const float* coef;  // coef: this chunk's first row of loss.coef_dev, or null
+    float* emb; float* scores; int64_t* decisions; float* loss_out;
+};
+hipError_t launch_iv_tail(const IvModel& m, const IvTailArgs& a, hipStream_t s);
+
 }  // namespace sg
 
 struct sg_ctx {
@@ -378,6 +444,8 @@ struct sg_ctx {
     bool an_tables_ready = false;
     sg::AnModel an;
     sg::AnWorkspace an_ws;
+    sg::IvModel iv;                  // the GMM / i-vector system (sg_api_ivector.hip) ...
+    sg::IvWorkspace iv_ws;           // ... and its chunk buffers
     std::vector<void*> model_allocs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // Stage trace (sg_trace_begin / sg_trace_end): while on, every launch of the x-vector pass sequences is bracketed by a
