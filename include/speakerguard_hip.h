@@ -903,12 +903,12 @@ int sg_xv_pgd_run_feco(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, cons
                        uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
                        float* loss_trace_dev, int64_t* decision_trace_dev, void* stream);
 
-/* ---- GMM / i-vector / PLDA system (reference model/iv_plda.py), FORWARD ONLY (csrc/k_ivector.hip) -------------------------
+/* ---- GMM / i-vector / PLDA system (reference model/iv_plda.py), both directions (csrc/k_ivector.hip, k_ivector_bwd.hip) ----
  * raw MFCC (the first 24 cepstra of sg_xv_mfcc's 30: same mel bank, lifter and energy) -> delta + delta-delta (window 3,
  * replicate edges, 72 columns) -> sliding 300-frame CMVN -> full-covariance GMM posteriors (no Gaussian pruning) ->
  * Baum-Welch statistics n (C), f (C, 72) -> i-vector w = L^-1 lin with L = I + sum_c n_c M_c^T Sigma_c^-1 M_c and
  * lin = sum_c M_c^T Sigma_c^-1 f_c (+ offset on entry 0, taken off w[0] again) -> mean subtraction, LDA, length
- * normalisation, PLDA transform and scores, decision.  The gradient is not built: there is no backward entry.
+ * normalisation, PLDA transform and scores, decision.  sg_iv_loss_grad runs the hand-coded adjoint of that chain.
  * An utterance's result is one fixed sequence of operations: it depends neither on B, nor on the row's place in the call, nor
  * on how the library cuts a large call into chunks (the workspace holds at most 64 utterances and 256 MiB of log-likelihoods).
  * All pointers of sg_iv_weights are HOST fp32 in the reference's layouts. */
@@ -957,10 +957,35 @@ int sg_iv_extract(sg_ctx* ctx, const float* zeroth_dev, const float* first_dev, 
  * T > 2^24, F outside 1 .. 65535. */
 int sg_iv_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, int32_t flag, const sg_dither* dither,
                   int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* ivector_dev, void* stream);
-/* sg_iv_forward plus the per-utterance loss of `loss` (y_dev (B) int64 labels); no gradient argument: not built. */
+/* sg_iv_forward plus the per-utterance loss of `loss` (y_dev (B) int64 labels); no gradient argument: sg_iv_loss_grad. */
 int sg_iv_loss(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
                const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
                void* stream);
+/* sg_iv_loss plus grad_dev = d loss_b / d x, the shape of x at every flag: (B, T), (B, F, 24), (B, F, 72), (B, F, 72).  The
+ * adjoint of the tail (the length normalisation's norm a constant, as the reference's .item()), of the solve (two triangular
+ * solves on the forward's Cholesky factor, float64), of the assembly (U and V^T streamed once per 16 rows), of the statistics
+ * and the softmax, of the log-likelihoods (the forward's contraction transposed, on the matrix cores, folded against x without
+ * writing it out), of CMVN and deltas, and at flag 0 the MFCC adjoint of sg_xv_mfcc_backward with the forward's scale and
+ * dither keys.  No float atomics; every sum of an utterance runs in an order fixed by C, R and F alone: a row's gradient is
+ * bit-identical whatever B, its place in the call or the chunk it falls into.  A chunk's backward runs right after its
+ * forward; the gradient's buffers (a second (frames, C) buffer among them) are grown by this entry and the backward stage
+ * entries only.  decisions, scores and loss are bit-equal to sg_iv_loss's.  Refusals as sg_iv_loss, and grad_dev NULL. */
+int sg_iv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
+                    const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+                    float* grad_dev, void* stream);
+/* The backward's stages alone (parity tests), each after re-running its forward stage on the given inputs:
+ * sg_iv_extract_backward: statistics (B, C), (B, C, 72) and d loss / d i-vector (B, R) -> d_zeroth (B, C), d_first (B, C, 72);
+ * sg_iv_stats_backward: CMVN features (B, F, 72) and d_zeroth, d_first -> d_cmvn (B, F, 72);
+ * sg_iv_delta_cmvn_backward: dout (B, F, 72) = d cmvn (from_flag 3) or d delta (from_flag 2) -> d_delta (B, F, 72) (from_flag 3
+ * only; may be NULL) and d_raw (B, F, 24) (may be NULL with from_flag 3).
+ * SG_ERR_STATE without a model (the first two); SG_ERR_ARG before any launch: a NULL argument, B outside 1 .. 2^20, F outside
+ * 1 .. 65535, another from_flag, no output, a d_delta output with from_flag 2. */
+int sg_iv_extract_backward(sg_ctx* ctx, const float* zeroth_dev, const float* first_dev, const float* d_ivector_dev, int32_t B,
+                           float* d_zeroth_dev, float* d_first_dev, void* stream);
+int sg_iv_stats_backward(sg_ctx* ctx, const float* cmvn_dev, int32_t B, int32_t F, const float* d_zeroth_dev, const float* d_first_dev,
+                         float* d_cmvn_dev, void* stream);
+int sg_iv_delta_cmvn_backward(sg_ctx* ctx, const float* dout_dev, int32_t from_flag, int32_t B, int32_t F, float* d_delta_dev,
+                              float* d_raw_dev, void* stream);
 
 #ifdef __cplusplus
 }

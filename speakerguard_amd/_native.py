@@ -34,6 +34,7 @@ EXPORTS = (
     "sg_pso_init", "sg_pso_select", "sg_pso_move",
     "sg_iv_load", "sg_iv_set_enroll", "sg_iv_enroll_override", "sg_iv_delta_cmvn", "sg_iv_stats", "sg_iv_extract",
     "sg_iv_forward", "sg_iv_loss",
+    "sg_iv_loss_grad", "sg_iv_extract_backward", "sg_iv_stats_backward", "sg_iv_delta_cmvn_backward",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -250,6 +251,10 @@ def load():
         "sg_iv_extract": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "sg_iv_forward": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(Dither), vp, vp, vp, vp, vp]),
         "sg_iv_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither), vp, vp, vp, vp]),
+        "sg_iv_loss_grad": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither), vp, vp, vp, vp, vp]),
+        "sg_iv_extract_backward": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
+        "sg_iv_stats_backward": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
+        "sg_iv_delta_cmvn_backward": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "sg_feco_warped": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_uint64, C.c_int64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -89,7 +89,8 @@ class FGSM(Attack):
         loop re-keys the noise (``feco_loop_rekeys``: xv_plda, whose loop keys dither and random init by (step, repeat)): with a
         dithered front-end or ``init='random'`` it keeps the step loop unless ``fuse_randomised_feco`` is set; the deterministic
         configuration is bit-equal on both routes and takes the loop by default.  AudioNet's loop does not re-key.  The base
-        model says what it offers by having the method."""
+        model says what it offers by having the method; one that has the methods only to refuse them (iv_plda) says
+        ``device_loops = False`` and keeps the step loop."""
         m = self.model
         defense = getattr(m, 'defense', None)
         base = getattr(m, 'base_model', m if defense is None else None)
@@ -123,7 +124,7 @@ class FGSM(Attack):
                         route = 'pgd_run_defended_feco', (chain, feco)
                 elif not chain and level in getattr(base, 'feco_loop_levels', (1,)):
                     route = _Route('pgd_run_feco', (feco,), level=level)
-        if route is None or not hasattr(base, route[0]):
+        if route is None or not hasattr(base, route[0]) or not getattr(base, 'device_loops', True):
             return None
         return route if isinstance(route, _Route) else _Route(*route)
 

@@ -1,4 +1,5 @@
-// GMM / i-vector / PLDA system (reference model/iv_plda.py, _iv_plda/gmm.py, _iv_plda/ivector_extract.py), forward only.
+// GMM / i-vector / PLDA system (reference model/iv_plda.py, _iv_plda/gmm.py, _iv_plda/ivector_extract.py): the forward, and the
+// tail's adjoint behind its forward (iv_tail_kernel); the rest of the backward is k_ivector_bwd.hip.
 // Every formula and every summation order of the file, stage by stage.  An utterance's numbers are one fixed sequence of
 // operations: no sum below depends on the batch size, on the row's place in the call or on the chunk it falls into.
 //
@@ -262,7 +263,8 @@ __global__ __launch_bounds__(256) void iv_assemble_lin_kernel(const float* __res
 
 constexpr int kChNb = 4, kChThreads = 256;
 __global__ __launch_bounds__(kChThreads) void iv_solve_kernel(double* __restrict__ Lmat, int Pp, const double* __restrict__ linpart, int NS,
-                                                              int B, int R, float offset, float* __restrict__ ivec) {
+                                                              int B, int R, float offset, float* __restrict__ ivec,
+                                                              double* __restrict__ solved) {
     __shared__ double pan[kIvMaxR * kChNb];
     __shared__ double vec[kIvMaxR];
     __shared__ double red[kChThreads / 64];
@@ -331,7 +333,10 @@ __global__ __launch_bounds__(kChThreads) void iv_solve_kernel(double* __restrict
         if (tid == 0) vec[j] = (vec[j] - sum) / col[0];
         __syncthreads();
     }
-    for (int i = tid; i < R; i += NT) ivec[(size_t)b * R + i] = (float)(i == 0 ? vec[i] - (double)offset : vec[i]);
+    for (int i = tid; i < R; i += NT) {
+        ivec[(size_t)b * R + i] = (float)(i == 0 ? vec[i] - (double)offset : vec[i]);
+        if (solved) solved[(size_t)b * R + i] = vec[i];  // s = w + offset e0, for the backward's dL = -lambda s^T
+    }
 }
 
 struct IvTailDev {
@@ -343,7 +348,7 @@ constexpr int kTlThreads = 256;
 __global__ __launch_bounds__(kTlThreads) void iv_tail_kernel(IvTailDev m, const float* __restrict__ ivec, const int64_t* __restrict__ y,
                                                              sg_loss_spec ls, const float* __restrict__ coef, float* __restrict__ emb_out,
                                                              float* __restrict__ scores_out, int64_t* __restrict__ dec_out,
-                                                             float* __restrict__ loss_out) {
+                                                             float* __restrict__ loss_out, float* __restrict__ dw_out) {
     __shared__ float e1[kIvMaxR];
     __shared__ float e2[kIvMaxD], e4[kIvMaxD], e5[kIvMaxD], c_psi[kIvMaxD];
     __shared__ float sc[kLossMaxS], dsc[kLossMaxS];
@@ -363,7 +368,7 @@ __global__ __launch_bounds__(kTlThreads) void iv_tail_kernel(IvTailDev m, const 
         e2[d] = acc;
         n2 += acc * acc;
     }
-    const float ratio = sqrtD / sqrtf(block_reduce_xor<NT / 64, true>(n2, red, OpSum()));  // norm detached: forward only anyway
+    const float ratio = sqrtD / sqrtf(block_reduce_xor<NT / 64, true>(n2, red, OpSum()));  // a constant in the backward (.item())
     for (int d = tid; d < D; d += NT) e2[d] = e2[d] * ratio - m.plda_mean[d];
     __syncthreads();
     // PLDA transform + normalisation factor, plda.py:73-97
@@ -413,6 +418,48 @@ __global__ __launch_bounds__(kTlThreads) void iv_tail_kernel(IvTailDev m, const 
                                             coef ? coef + (size_t)b * S : nullptr);
         if (dec_out) dec_out[b] = dec;
         if (loss_out) loss_out[b] = loss;
+    }
+    if (!dw_out) return;
+    __syncthreads();
+    // The adjoint of the tail (k_tail.hip steps 9-13 on an R-vector), float32, every sum in index order per output:
+    //   d e5 = sum_s dsc_s (-(e5 - r enroll_s) / (1 + r) + e5 / (psi + 1)),
+    //   d e4 = fac d e5 - (d e5 . e4) (fac / q) e4 / (psi + 1)      (the normalisation factor is differentiated, plda.py:92-97)
+    //   d e2 = ratio P^T d e4                                       (the length normalisation's norm is a CONSTANT: .item())
+    //   d w  = A^T d e2                                             (A: the LDA matrix without its offset column)
+    float* dv = e5;  // every thread reads e5 at its own d below, then writes d e4 there
+    float dotp = 0.f;
+    float g_own[(kIvMaxD + NT - 1) / NT];
+    {
+        int slot = 0;
+        for (int d = tid; d < D; d += NT, ++slot) {
+            const float psi = c_psi[d];
+            const float rr = psi / (psi + 1.f);
+            const float iv1 = 1.f / (1.f + rr), iv0 = 1.f / (psi + 1.f);
+            float g = 0.f;
+            for (int s = 0; s < S; ++s) {
+                const float w = dsc[s];
+                if (w != 0.f) g += w * (-(e5[d] - rr * m.enroll[(size_t)s * D + d]) * iv1 + e5[d] * iv0);
+            }
+            g_own[slot] = g;
+            dotp += g * e4[d];
+        }
+    }
+    const float dot = block_reduce_xor<NT / 64, true>(dotp, red, OpSum());
+    {
+        int slot = 0;
+        for (int d = tid; d < D; d += NT, ++slot) dv[d] = (fac * g_own[slot] - dot * (fac / q) * e4[d] / (c_psi[d] + 1.f)) * ratio;
+    }
+    __syncthreads();
+    for (int j = tid; j < D; j += NT) {  // P^T: plda_pt holds P transposed, [j][d] = P[d][j]
+        float acc = 0.f;
+        for (int d = 0; d < D; ++d) acc += m.plda_pt[(size_t)j * D + d] * dv[d];
+        e2[j] = acc;
+    }
+    __syncthreads();
+    for (int k = tid; k < R; k += NT) {
+        float acc = 0.f;
+        for (int d = 0; d < D; ++d) acc += m.lda_t[(size_t)k * D + d] * e2[d];
+        dw_out[(size_t)b * R + k] = acc;
     }
 }
 
@@ -524,11 +571,11 @@ hipError_t launch_iv_stats(const IvModel& m, const float* cmvn, int B, int F, fl
 }
 
 hipError_t launch_iv_extract(const IvModel& m, const float* n, const float* f, int B, double* Lmat, double* linpart, float* ivec,
-                             hipStream_t s) {
+                             hipStream_t s, double* solved) {
     const int NS = (m.C + kIvLinSlice - 1) / kIvLinSlice, G = (B + kAsmG - 1) / kAsmG;
     hipLaunchKernelGGL(iv_assemble_L_kernel, dim3(m.Pp / 256, G), dim3(256), 0, s, m.U, m.Pp, m.C, n, B, Lmat);
     hipLaunchKernelGGL(iv_assemble_lin_kernel, dim3((m.R + 255) / 256, NS, G), dim3(256), 0, s, m.Vt, m.R, m.C, f, B, linpart);
-    hipLaunchKernelGGL(iv_solve_kernel, dim3(B), dim3(kChThreads), 0, s, Lmat, m.Pp, linpart, NS, B, m.R, m.offset, ivec);
+    hipLaunchKernelGGL(iv_solve_kernel, dim3(B), dim3(kChThreads), 0, s, Lmat, m.Pp, linpart, NS, B, m.R, m.offset, ivec, solved);
     return hipGetLastError();
 }
 
@@ -540,7 +587,7 @@ hipError_t launch_iv_tail(const IvModel& x, const IvTailArgs& a, hipStream_t s) 
     m.enroll = x.enroll_override ? x.enroll_override : x.enroll;
     m.R = x.R; m.D = x.D; m.S = S; m.threshold = x.threshold; m.logdet_given = x.logdet_given; m.logdet_without = x.logdet_without;
     hipLaunchKernelGGL(iv_tail_kernel, dim3(a.B), dim3(kTlThreads), 0, s, m, a.ivec, a.y, a.loss, a.coef, a.emb, a.scores, a.decisions,
-                       a.loss_out);
+                       a.loss_out, a.dw);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // C-ABI entry points of the GMM / i-vector / PLDA system (include/speakerguard_hip.h, kernels: k_ivector.hip): model load
-// (the packing of k_ivector.hip's tables), the chunk workspace, the stage entries and the forward pass.  Forward only.
+// (the packing of k_ivector.hip's tables), the chunk workspace, the stage entries, the forward pass and the gradient
+// (k_ivector_bwd.hip): a chunk's backward runs right after its forward, on the chunk's buffers.
 #include <cmath>
 #include <cstring>
 
@@ -35,7 +36,7 @@ int iv_check_dims(sg_ctx* ctx, const char* who, int B, int TF, int flag, IvDims*
 }
 
 // the chunk buffers of a call of `chunk` utterances x F frames (and T samples when the MFCC runs); grown before any launch
-int iv_ensure_workspace(sg_ctx* ctx, int chunk, int F, bool wav, hipStream_t s) {
+int iv_ensure_workspace(sg_ctx* ctx, int chunk, int F, bool wav, hipStream_t s, bool grad = false) {
     IvWorkspace& w = ctx->iv_ws;
     const IvModel& m = ctx->iv;
     const size_t rows = (size_t)chunk * F;
@@ -53,12 +54,28 @@ int iv_ensure_workspace(sg_ctx* ctx, int chunk, int F, bool wav, hipStream_t s) 
     if (!rc) rc = dev_grow(ctx, w.allocs, &w.ivec, (size_t)chunk * m.R, s);
     if (!rc) rc = dev_grow(ctx, w.allocs, &w.Lmat, (size_t)chunk * m.Pp, s);
     if (!rc) rc = dev_grow(ctx, w.allocs, &w.linpart, (size_t)NS * chunk * m.R, s);
+    if (!grad) return rc;
+    // what only the gradient keeps: the solved vector, lambda, the adjoint statistics, a second (frames, Cp) buffer for
+    // dgamma / dll, and the feature gradients on the way to the caller's flag
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.solved, (size_t)chunk * m.R, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.lam, (size_t)chunk * m.R, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dw, (size_t)chunk * m.R, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dnpart, (size_t)iv_dn_slices(m.P) * chunk * m.C, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dn, (size_t)chunk * m.C, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.df, (size_t)chunk * m.C * kIvDim, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dg, rows * m.Cp, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dxpart, kIvDxSplit * rows * kIvDim, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.dcmvn, rows * kIvDim, s);
+    if (!rc) rc = dev_grow(ctx, w.allocs, &w.ddelta, rows * kIvDim, s);
+    if (!rc && wav) rc = dev_grow(ctx, w.allocs, &w.draw, rows * kCep, s);
+    if (!rc && wav) rc = dev_grow(ctx, w.allocs, &w.dframes, rows * kWin, s);
     return rc;
 }
 
 // one forward: the whole call's scale decision first (model/utils.py:7-19), then chunk after chunk
 int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B, int TF, int flag, const sg_loss_spec* loss,
-           const sg_dither* dither, int64_t* dec, float* scores, float* emb, float* ivec_out, float* loss_out, hipStream_t s) {
+           const sg_dither* dither, int64_t* dec, float* scores, float* emb, float* ivec_out, float* loss_out, hipStream_t s,
+           float* grad = nullptr) {
     IvDims d;
     int rc = iv_check_dims(ctx, who, B, TF, flag, &d);
     if (rc) return rc;
@@ -66,7 +83,8 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
     if (loss && loss->loss == SG_LOSS_LINEAR && !loss->coef_dev) return fail(ctx, SG_ERR_ARG, "%s: SG_LOSS_LINEAR needs coef_dev", who);
     if (loss && loss->loss != SG_LOSS_LINEAR && !y) return fail(ctx, SG_ERR_ARG, "%s: y is NULL", who);
     SG_HIP(hipSetDevice(ctx->device));
-    if ((rc = iv_ensure_workspace(ctx, d.chunk, d.F, flag == SG_IV_FLAG_WAV, s))) return rc;
+    if (grad && !loss) return fail(ctx, SG_ERR_ARG, "%s: loss is NULL", who);
+    if ((rc = iv_ensure_workspace(ctx, d.chunk, d.F, flag == SG_IV_FLAG_WAV, s, grad != nullptr))) return rc;
     IvWorkspace& w = ctx->iv_ws;
     const IvModel& m = ctx->iv;
     const int S = m.enroll_override ? m.S_override : m.S;
@@ -76,8 +94,8 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
         const size_t row_floats = flag == SG_IV_FLAG_WAV ? (size_t)d.T : (size_t)d.F * (flag == SG_IV_FLAG_RAW ? kIvCep : kIvDim);
         const float* xc = x + (size_t)b0 * row_floats;
         const float* cm = w.cmvn;
+        sg_dither dz{};
         if (flag == SG_IV_FLAG_WAV) {
-            sg_dither dz{};
             if (dither) dz = *dither;
             dz.row_base += b0;  // the chunk is a slice of the call: same noise as in one piece
             if (dz.noise_dev) dz.noise_dev += (size_t)b0 * d.F * kWin;
@@ -92,7 +110,7 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
             cm = xc;
         }
         SG_HIP(launch_iv_stats(m, cm, nb, d.F, w.ll, w.rowmax, w.rowsum, w.n, w.f, s));
-        SG_HIP(launch_iv_extract(m, w.n, w.f, nb, w.Lmat, w.linpart, w.ivec, s));
+        SG_HIP(launch_iv_extract(m, w.n, w.f, nb, w.Lmat, w.linpart, w.ivec, s, grad ? w.solved.ptr : nullptr));
         if (ivec_out) SG_HIP(hipMemcpyAsync(ivec_out + (size_t)b0 * m.R, w.ivec, (size_t)nb * m.R * sizeof(float), hipMemcpyDeviceToDevice, s));
         IvTailArgs t{};
         t.ivec = w.ivec; t.B = nb;
@@ -105,7 +123,25 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
         t.scores = scores ? scores + (size_t)b0 * S : nullptr;
         t.decisions = dec ? dec + b0 : nullptr;
         t.loss_out = (loss && loss_out) ? loss_out + b0 : nullptr;
+        t.dw = grad ? w.dw.ptr : nullptr;
         SG_HIP(launch_iv_tail(m, t, s));
+        if (!grad) continue;
+        // the chunk's backward, on the state its forward left: the factor in Lmat, ll, the row maxima and sums
+        float* gc = grad + (size_t)b0 * row_floats;
+        SG_HIP(launch_iv_extract_bwd(m, w.dw, nb, w.Lmat, w.solved, w.lam, w.dnpart, w.dn, w.df, s));
+        SG_HIP(launch_iv_stats_bwd(m, cm, nb, d.F, w.ll, w.rowmax, w.rowsum, w.dn, w.df, w.dg, w.dxpart,
+                                   flag == SG_IV_FLAG_CMVN ? gc : w.dcmvn.ptr, s));
+        if (flag == SG_IV_FLAG_DELTA) {
+            SG_HIP(launch_iv_delta_cmvn_bwd(w.dcmvn, true, nb, d.F, gc, nullptr, 0, s));
+        } else if (flag == SG_IV_FLAG_RAW) {
+            SG_HIP(launch_iv_delta_cmvn_bwd(w.dcmvn, true, nb, d.F, w.ddelta, gc, kIvCep, s));
+        } else if (flag == SG_IV_FLAG_WAV) {
+            // d raw zero-padded to the MFCC's 30 columns, then the launches of sg_xv_mfcc_backward with the forward's scale and
+            // dither keys (the entry itself sizes its scratch from the x-vector model's workspace: this one is the chunk's own)
+            SG_HIP(launch_iv_delta_cmvn_bwd(w.dcmvn, true, nb, d.F, w.ddelta, w.draw, kCep, s));
+            SG_HIP(launch_mfcc_bwd(ctx->tab, xc, nb, d.T, d.F, w.scale, &dz, w.draw, w.dframes, s));
+            SG_HIP(launch_frames_to_wave(w.dframes, nb, d.T, d.F, 1, nullptr, gc, nullptr, nullptr, nullptr, 0.f, 1, s));
+        }
     }
     return SG_OK;
 }
@@ -274,6 +310,86 @@ int sg_iv_loss(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B,
     if (!loss) return fail(ctx, SG_ERR_ARG, "sg_iv_loss: loss is NULL");
     return iv_run(ctx, "sg_iv_loss", x_dev, y_dev, B, T_or_F, flag, loss, dither, decisions_dev, scores_dev, nullptr, nullptr, loss_dev,
                   (hipStream_t)stream);
+}
+
+int sg_iv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
+                    const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+                    float* grad_dev, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    if (!loss) return fail(ctx, SG_ERR_ARG, "sg_iv_loss_grad: loss is NULL");
+    if (!grad_dev) return fail(ctx, SG_ERR_ARG, "sg_iv_loss_grad: grad is NULL");
+    return iv_run(ctx, "sg_iv_loss_grad", x_dev, y_dev, B, T_or_F, flag, loss, dither, decisions_dev, scores_dev, nullptr, nullptr,
+                  loss_dev, (hipStream_t)stream, grad_dev);
+}
+
+int sg_iv_extract_backward(sg_ctx* ctx, const float* zeroth_dev, const float* first_dev, const float* d_ivector_dev, int32_t B,
+                           float* d_zeroth_dev, float* d_first_dev, void* stream) {
+    IvDims d;
+    int rc = iv_check_dims(ctx, "sg_iv_extract_backward", B, 1, SG_IV_FLAG_CMVN, &d);
+    if (rc) return rc;
+    if (!zeroth_dev || !first_dev || !d_ivector_dev || !d_zeroth_dev || !d_first_dev)
+        return fail(ctx, SG_ERR_ARG, "sg_iv_extract_backward: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    SG_HIP(hipSetDevice(ctx->device));
+    const int chunk = std::min(B, kIvChunkMax);
+    if ((rc = iv_ensure_workspace(ctx, chunk, 1, false, s, true))) return rc;
+    IvWorkspace& w = ctx->iv_ws;
+    const IvModel& m = ctx->iv;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = std::min(chunk, B - b0);
+        const size_t oc = (size_t)b0 * m.C;
+        SG_HIP(launch_iv_extract(m, zeroth_dev + oc, first_dev + oc * kIvDim, nb, w.Lmat, w.linpart, w.ivec, s, w.solved));
+        SG_HIP(launch_iv_extract_bwd(m, d_ivector_dev + (size_t)b0 * m.R, nb, w.Lmat, w.solved, w.lam, w.dnpart, d_zeroth_dev + oc,
+                                     d_first_dev + oc * kIvDim, s));
+    }
+    return SG_OK;
+}
+
+int sg_iv_stats_backward(sg_ctx* ctx, const float* cmvn_dev, int32_t B, int32_t F, const float* d_zeroth_dev, const float* d_first_dev,
+                         float* d_cmvn_dev, void* stream) {
+    IvDims d;
+    int rc = iv_check_dims(ctx, "sg_iv_stats_backward", B, F, SG_IV_FLAG_CMVN, &d);
+    if (rc) return rc;
+    if (!cmvn_dev || !d_zeroth_dev || !d_first_dev || !d_cmvn_dev) return fail(ctx, SG_ERR_ARG, "sg_iv_stats_backward: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    SG_HIP(hipSetDevice(ctx->device));
+    if ((rc = iv_ensure_workspace(ctx, d.chunk, d.F, false, s, true))) return rc;
+    IvWorkspace& w = ctx->iv_ws;
+    const IvModel& m = ctx->iv;
+    for (int b0 = 0; b0 < B; b0 += d.chunk) {
+        const int nb = std::min(d.chunk, B - b0);
+        const size_t of = (size_t)b0 * F * kIvDim, oc = (size_t)b0 * m.C;
+        SG_HIP(launch_iv_stats(m, cmvn_dev + of, nb, F, w.ll, w.rowmax, w.rowsum, w.n, w.f, s));
+        SG_HIP(launch_iv_stats_bwd(m, cmvn_dev + of, nb, F, w.ll, w.rowmax, w.rowsum, d_zeroth_dev + oc, d_first_dev + oc * kIvDim, w.dg,
+                                   w.dxpart, d_cmvn_dev + of, s));
+    }
+    return SG_OK;
+}
+
+int sg_iv_delta_cmvn_backward(sg_ctx* ctx, const float* dout_dev, int32_t from_flag, int32_t B, int32_t F, float* d_delta_dev,
+                              float* d_raw_dev, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    if (from_flag != SG_IV_FLAG_CMVN && from_flag != SG_IV_FLAG_DELTA)
+        return fail(ctx, SG_ERR_ARG, "sg_iv_delta_cmvn_backward: from_flag must be 3 (d cmvn) or 2 (d delta)");
+    const bool from_cmvn = from_flag == SG_IV_FLAG_CMVN;
+    if (!dout_dev || (!d_delta_dev && !d_raw_dev) || (!from_cmvn && (d_delta_dev || !d_raw_dev)))
+        return fail(ctx, SG_ERR_ARG, "sg_iv_delta_cmvn_backward: NULL input, no output, or a d delta output asked of a d delta input");
+    if (B < 1 || B > (1 << 20) || F < 1 || F > 65535)
+        return fail(ctx, SG_ERR_ARG, "sg_iv_delta_cmvn_backward: B must be 1 .. 2^20, F 1 .. 65535");
+    hipStream_t s = (hipStream_t)stream;
+    SG_HIP(hipSetDevice(ctx->device));
+    // as in sg_iv_delta_cmvn: the kernel reads its d delta rows back, so they need a home even when the caller wants d raw only
+    IvWorkspace& w = ctx->iv_ws;
+    const int chunk = std::min<int64_t>(B, std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)F * kIvDim * 4)));
+    int rc = (d_delta_dev || !from_cmvn) ? SG_OK : dev_grow(ctx, w.allocs, &w.ddelta, (size_t)chunk * F * kIvDim, s);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = std::min(chunk, B - b0);
+        const size_t o = (size_t)b0 * F;
+        float* home = !from_cmvn ? nullptr : d_delta_dev ? d_delta_dev + o * kIvDim : w.ddelta.ptr;
+        SG_HIP(launch_iv_delta_cmvn_bwd(dout_dev + o * kIvDim, from_cmvn, nb, F, home, d_raw_dev ? d_raw_dev + o * kIvCep : nullptr, kIvCep, s));
+    }
+    return SG_OK;
 }
 
 }  // extern "C"

@@ -375,6 +375,9 @@ struct IvModel {
 struct IvWorkspace {
     DevBuf<float> scale, raw, delta, cmvn, ll, rowmax, rowsum, n, f, ivec;
     DevBuf<double> Lmat, linpart;
+    // the gradient's buffers (sg_iv_loss_grad and the backward stage entries only: a decision query never grows them)
+    DevBuf<float> dw, dn, df, dg, dxpart, dcmvn, ddelta, draw, dframes;
+    DevBuf<double> solved, lam, dnpart;
     std::vector<void*> allocs;
 };
 // utterances per chunk for F frames and C Gaussians: a pure function (the host double walks it)
@@ -393,14 +396,32 @@ hipError_t launch_iv_delta_cmvn(const float* raw, int ld, int B, int F, float* d
                                 hipStream_t s);
 hipError_t launch_iv_stats(const IvModel& m, const float* cmvn, int B, int F, float* ll, float* rowmax, float* rowsum, float* n,
                            float* f, hipStream_t s);
+// solved (B, R) float64 or null: the solved vector s = w + offset e0, kept for the backward (dL = -lambda s^T); Lmat then holds
+// the Cholesky factor G (the solve factors in place), which the backward's two triangular solves read
 hipError_t launch_iv_extract(const IvModel& m, const float* n, const float* f, int B, double* Lmat, double* linpart, float* ivec,
-                             hipStream_t s);
+                             hipStream_t s, double* solved = nullptr);
 struct IvTailArgs {
     const float* ivec; int B;
     const int64_t* y; sg_loss_spec loss; const float* coef;  // coef: this chunk's first row of loss.coef_dev, or null
     float* emb; float* scores; int64_t* decisions; float* loss_out;
+    float* dw = nullptr;  // (B, R) d loss / d i-vector, or null: forward only
 };
 hipError_t launch_iv_tail(const IvModel& m, const IvTailArgs& a, hipStream_t s);
+// ---- the backward (k_ivector_bwd.hip); every launcher runs on the buffers of the chunk whose forward just ran
+constexpr int kIvDnSlice = 8192;  // packed-triangle entries per partial sum of d n (a constant of the arithmetic, like kIvLinSlice)
+inline int iv_dn_slices(int P) { return (P + kIvDnSlice - 1) / kIvDnSlice; }
+// dw (B, R) float32 -> lam = L^-1 dw (float64) by two triangular solves on the factor in Lmat; Lmat then holds dLsym
+// (-(lam_i s_j + lam_j s_i), -lam_i s_i on the diagonal, zero past P); d n (B, C) and d f (B, C, 72) from U and Vt
+hipError_t launch_iv_extract_bwd(const IvModel& m, const float* dw, int B, double* Lmat, const double* solved, double* lam, double* dnpart,
+                                 float* dn, float* df, hipStream_t s);
+// d n, d f -> d ll (written to dg, row stride Cp, zero past C) and dx (B F, 72) = both terms of step 5; dxpart: kIvDxSplit x
+// (B F, 72), the partial sums of the log-likelihood term
+constexpr int kIvDxSplit = 4;
+hipError_t launch_iv_stats_bwd(const IvModel& m, const float* cmvn, int B, int F, const float* ll, const float* rowmax, const float* rowsum,
+                               const float* dn, const float* df, float* dg, float* dxpart, float* dx, hipStream_t s);
+// dout: d cmvn (from_cmvn) or d delta -> ddelta (B, F, 72; written when from_cmvn, else read from dout) and draw (B, F, ld) with
+// columns 24 .. ld - 1 zero, or null
+hipError_t launch_iv_delta_cmvn_bwd(const float* dout, bool from_cmvn, int B, int F, float* ddelta, float* draw, int ld, hipStream_t s);
 
 }  // namespace sg
 

@@ -1,13 +1,17 @@
-"""GMM i-vector + PLDA speaker model on the HIP engine, FORWARD ONLY.
+"""GMM i-vector + PLDA speaker model on the HIP engine; the gradient is opt-in (``white_box=True``).
 
 Host-side mirror of reference model/iv_plda.py: same constructor files, same method names and argument meaning, same
 ``allowed_flags`` / ``range_type`` / ``threshold`` / ``spk_ids`` attributes.  All arithmetic runs in
-``libspeakerguard_hip.so`` (csrc/k_ivector.hip); torch only owns the tensors.
+``libspeakerguard_hip.so`` (csrc/k_ivector.hip, csrc/k_ivector_bwd.hip); torch only owns the tensors.
 
-What is built is the decision path -- ``make_decision`` / ``score`` / ``forward`` / ``embedding`` / ``compute_feat`` and
-``loss_grad(want_grad=False)`` -- which is all the black-box attacks (FAKEBOB / NES, SirenAttack, Kenan)
-ask of a model.  The hand-coded gradient through the softmax, the statistics and the linear solve is NOT built:
-``loss_grad(want_grad=True)`` and ``pgd_run*`` raise ``NotImplementedError``, so FGSM / PGD / CW cannot run on this model.
+The default model is the decision path -- ``make_decision`` / ``score`` / ``forward`` / ``embedding`` / ``compute_feat`` and
+``loss_grad(want_grad=False)`` -- which is all the black-box attacks (FAKEBOB / NES, SirenAttack, Kenan) ask of a model; on it
+``loss_grad(want_grad=True)`` raises ``NotImplementedError``.  ``iv_plda(..., white_box=True)`` / ``from_weights(...,
+white_box=True)`` enables the hand-coded gradient (``sg_iv_loss_grad``: the adjoint of the tail, the solve, the assembly, the
+statistics and softmax, the log-likelihoods, CMVN, deltas and the MFCC) at every flag, so FGSM / PGD / CWinf / CW2 run on it
+through their step loop.  It is opt-in because a white-box model keeps per-chunk state a decision query should not pay for:
+the solved vector and lambda in float64 and a second (frames, C) buffer.  There is no device-resident loop: ``pgd_run*`` raise
+on every instance and ``device_loops = False`` sends the attacks to the step loop over ``loss_grad`` / ``pgd_update``.
 
 Differences a caller can observe, all deliberate: ``dither`` / ``dither_seed`` are constructor arguments keyed exactly as in
 ``xv_plda`` (default 1.0 like the reference, which draws from the global torch RNG); ``gmm_frame_bs`` is accepted and
@@ -126,9 +130,10 @@ class iv_plda(EngineOps):
     allowed_flags = [0, 1, 2, 3]  # 0: wav; 1: raw feat; 2: delta feat; 3: cmvn feat (iv_plda.py:75-77)
     range_type = "origin"
     _feat_widths = {1: IV_CEPS, 2: IV_DIM, 3: IV_DIM}
+    device_loops = False  # no pgd_run*: attack.FGSM._device_route sends every attack to the step loop
 
     def __init__(self, fgmm_file, extractor_file, plda_file, mean_file, transform_mat_file, model_file=None, threshold=None,
-                 device="cuda:0", gmm_frame_bs=200, dither=1.0, dither_seed=0):
+                 device="cuda:0", gmm_frame_bs=200, dither=1.0, dither_seed=0, white_box=False):
         weights = dict(parse_fgmm_file(fgmm_file))
         weights.update(parse_ie_file(extractor_file))
         weights["plda_mean"], weights["plda_transform"], weights["plda_psi"] = parse_plda_file(plda_file)
@@ -137,12 +142,14 @@ class iv_plda(EngineOps):
         spk_ids = None
         if model_file is not None:
             spk_ids, self.z_norm_means, self.z_norm_stds, weights["enroll"] = parse_enroll_model_file(model_file)
+        self._white_box = bool(white_box)
         self._init(weights, threshold, device, dither, dither_seed, spk_ids)
 
     @classmethod
-    def from_weights(cls, weights, threshold=None, device="cuda:0", dither=1.0, dither_seed=0):
+    def from_weights(cls, weights, threshold=None, device="cuda:0", dither=1.0, dither_seed=0, white_box=False):
         """Build from in-memory arrays (see speakerguard_amd.synth.make_iv_weights)."""
         self = cls.__new__(cls)
+        self._white_box = bool(white_box)
         self._init(weights, threshold, device, dither, dither_seed, None)
         return self
 
@@ -339,13 +346,17 @@ class iv_plda(EngineOps):
 
     # ------------------------------------------------------------------ engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):
-        """make_decision + per-example loss in one native call -> (decisions, scores, loss, None).  Forward only:
-        ``want_grad=True`` raises (the gradient through the posteriors, the statistics and the solve is not built)."""
-        if want_grad:
+        """make_decision + per-example loss (+ d loss / d x, the shape of x, on a ``white_box=True`` model) in one native call
+        -> (decisions, scores, loss, grad or None).  On the default model ``want_grad=True`` raises."""
+        if want_grad and not getattr(self, "_white_box", False):
             raise NotImplementedError(_NO_GRAD % "loss_grad(want_grad=True)")
-        x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, False)
+        x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)
         dz = self._dither(dither_noise, dither_seed)
         spec = loss_spec.native()
+        if want_grad:
+            self.ctx.call("sg_iv_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), C.byref(dz),
+                          *[N._ptr(t) for t in outs], self._stream())
+            return outs
         self.ctx.call("sg_iv_loss", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), C.byref(dz),
                       *[N._ptr(t) for t in outs[:3]], self._stream())
         return outs
