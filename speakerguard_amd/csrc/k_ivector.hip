@@ -41,6 +41,7 @@
 #include <cmath>
 
 #include "loss_device.h"
+#include "plda_device.h"
 #include "sg_internal.h"
 #include "wave_reduce.h"
 
@@ -387,30 +388,8 @@ __global__ __launch_bounds__(kTlThreads) void iv_tail_kernel(IvTailDev m, const 
     }
     __syncthreads();
     // PLDA scores: one wave per enrolled speaker, plda.py:140-190 (k_tail.hip step 5)
-    {
-        const int lane = tid & 63, wid = tid >> 6;
-        const float l2pi = logf(2.f * 3.1415926f) * (float)D;
-        float s0 = 0.f;
-        for (int d = lane; d < D; d += 64) s0 += e5[d] * e5[d] * (1.f / (c_psi[d] + 1.f));
-        s0 = wave_sum_rows(s0);
-        const float without = -0.5f * (m.logdet_without + l2pi + s0);
-        for (int s = wid; s < S; s += NT / 64) {
-            float s1 = 0.f;
-            for (int d = lane; d < D; d += 64) {
-                const float psi = c_psi[d];
-                const float rr = psi / (psi + 1.f);
-                const float df = e5[d] - rr * m.enroll[(size_t)s * D + d];
-                s1 += df * df * (1.f / (1.f + rr));
-            }
-            s1 = wave_sum_rows(s1);
-            if (lane == 0) {
-                const float v = -0.5f * (m.logdet_given + l2pi + s1) - without;
-                sc[s] = v;
-                dsc[s] = 0.f;
-                if (scores_out) scores_out[(size_t)b * S + s] = v;
-            }
-        }
-    }
+    plda_llr_scores<NT>(e5, c_psi, m.enroll, D, S, m.logdet_given, m.logdet_without, sc, dsc,
+                        scores_out ? scores_out + (size_t)b * S : nullptr);
     __syncthreads();
     if (tid == 0) {
         int64_t dec = 0;
@@ -432,14 +411,7 @@ __global__ __launch_bounds__(kTlThreads) void iv_tail_kernel(IvTailDev m, const 
     {
         int slot = 0;
         for (int d = tid; d < D; d += NT, ++slot) {
-            const float psi = c_psi[d];
-            const float rr = psi / (psi + 1.f);
-            const float iv1 = 1.f / (1.f + rr), iv0 = 1.f / (psi + 1.f);
-            float g = 0.f;
-            for (int s = 0; s < S; ++s) {
-                const float w = dsc[s];
-                if (w != 0.f) g += w * (-(e5[d] - rr * m.enroll[(size_t)s * D + d]) * iv1 + e5[d] * iv0);
-            }
+            const float g = plda_de5_term(e5, c_psi, m.enroll, dsc, D, S, d);
             g_own[slot] = g;
             dotp += g * e4[d];
         }
@@ -580,12 +552,12 @@ hipError_t launch_iv_extract(const IvModel& m, const float* n, const float* f, i
 }
 
 hipError_t launch_iv_tail(const IvModel& x, const IvTailArgs& a, hipStream_t s) {
-    const int S = x.enroll_override ? x.S_override : x.S;
-    if (x.R > kIvMaxR || x.D > kIvMaxD || S > kLossMaxS || S < 1) return hipErrorInvalidValue;
+    const PldaBackend& be = x.be;
     IvTailDev m;
-    m.emb_mean = x.emb_mean; m.lda_t = x.lda_t; m.plda_mean = x.plda_mean; m.plda_pt = x.plda_pt; m.plda_psi = x.plda_psi;
-    m.enroll = x.enroll_override ? x.enroll_override : x.enroll;
-    m.R = x.R; m.D = x.D; m.S = S; m.threshold = x.threshold; m.logdet_given = x.logdet_given; m.logdet_without = x.logdet_without;
+    plda_backend_active(be, &m.enroll, &m.S);
+    if (x.R > kIvMaxR || be.D > kIvMaxD || m.S > kLossMaxS || m.S < 1) return hipErrorInvalidValue;
+    m.emb_mean = x.emb_mean; m.lda_t = x.lda_t; m.plda_mean = be.plda_mean; m.plda_pt = x.plda_pt; m.plda_psi = be.plda_psi;
+    m.R = x.R; m.D = be.D; m.threshold = be.threshold; m.logdet_given = be.logdet_given; m.logdet_without = be.logdet_without;
     hipLaunchKernelGGL(iv_tail_kernel, dim3(a.B), dim3(kTlThreads), 0, s, m, a.ivec, a.y, a.loss, a.coef, a.emb, a.scores, a.decisions,
                        a.loss_out, a.dw);
     return hipGetLastError();

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "loss_device.h"
+#include "plda_device.h"
 #include "sg_internal.h"
 #include "wave_reduce.h"
 
@@ -231,31 +232,8 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(TailModelDev m, cons
     __syncthreads();
     TSTAMP(5)
     // 5. PLDA scores: one wave per enrolled speaker
-    {
-        const int lane = tid & 63, wid = tid >> 6;
-        const float l2pi = logf(2.f * 3.1415926f) * (float)D;  // plda.py:179 (cancels in the ratio)
-        float s0 = 0.f;  // sum e5^2 / (psi + 1)
-        for (int d = lane; d < D; d += 64) s0 += e5[d] * e5[d] * (1.f / (c_psi[d] + 1.f));
-        s0 = wave_sum_rows(s0);
-        const float without = -0.5f * (m.logdet_without + l2pi + s0);
-        for (int s = wid; s < S; s += NT / 64) {
-            float s1 = 0.f;
-            for (int d = lane; d < D; d += 64) {
-                const float psi = c_psi[d];
-                const float r = psi / (psi + 1.f);
-                const float df = e5[d] - r * enr[(size_t)s * D + d];
-                s1 += df * df * (1.f / (1.f + r));
-            }
-            s1 = wave_sum_rows(s1);
-            if (lane == 0) {
-                const float given = -0.5f * (m.logdet_given + l2pi + s1);
-                const float v = given - without;
-                sc[s] = v;
-                dsc[s] = 0.f;
-                if (scores_out) scores_out[(size_t)b * S + s] = v;
-            }
-        }
-    }
+    plda_llr_scores<NT>(e5, c_psi, enr, D, S, m.logdet_given, m.logdet_without, sc, dsc,
+                        scores_out ? scores_out + (size_t)b * S : nullptr);
     __syncthreads();
     TSTAMP(6)
     // 6-8. decision, loss, d loss / d scores
@@ -290,14 +268,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(TailModelDev m, cons
     // 9. d/d e5 of the score combination
     float dotp = 0.f;
     for (int d = tid; d < D; d += NT) {
-        const float psi = c_psi[d];
-        const float r = psi / (psi + 1.f);
-        const float iv1 = 1.f / (1.f + r), iv0 = 1.f / (psi + 1.f);
-        float g = 0.f;
-        for (int s = 0; s < S; ++s) {
-            const float w = dsc[s];
-            if (w != 0.f) g += w * (-(e5[d] - r * enr[(size_t)s * D + d]) * iv1 + e5[d] * iv0);
-        }
+        const float g = plda_de5_term(e5, c_psi, enr, dsc, D, S, d);
         dv[d] = g;
         dotp += g * e4[d];
     }
@@ -318,14 +289,14 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(TailModelDev m, cons
 
 hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const XvModel& x = *a.m;
-    const int S = x.enroll_override ? x.S_override : x.S;  // per-call enroll_embs= (iv_plda.py:155-165)
-    if (x.D > kMaxD || S > kMaxS || S < 1) return hipErrorInvalidValue;
+    const PldaBackend& be = x.be;
     TailModelDev m;
-    m.fc1_b = x.fc1_b; m.emb_mean = x.emb_mean; m.lda = x.lda; m.lda_t = x.lda_t; m.plda_mean = x.plda_mean;
-    m.plda_p = x.plda_p; m.plda_pt = x.plda_pt; m.plda_psi = x.plda_psi; m.pa = x.pa;
-    m.enroll = x.enroll_override ? x.enroll_override : x.enroll;
-    m.D = x.D; m.Dp = x.Dp; m.S = S; m.threshold = x.threshold;
-    m.logdet_given = x.logdet_given; m.logdet_without = x.logdet_without;
+    plda_backend_active(be, &m.enroll, &m.S);  // per-call enroll_embs= (iv_plda.py:155-165)
+    if (be.D > kMaxD || m.S > kMaxS || m.S < 1) return hipErrorInvalidValue;
+    m.fc1_b = x.fc1_b; m.emb_mean = x.emb_mean; m.lda = x.lda; m.lda_t = x.lda_t; m.plda_mean = be.plda_mean;
+    m.plda_p = x.plda_p; m.plda_pt = x.plda_pt; m.plda_psi = be.plda_psi; m.pa = x.pa;
+    m.D = be.D; m.Dp = x.Dp; m.threshold = be.threshold;
+    m.logdet_given = be.logdet_given; m.logdet_without = be.logdet_without;
     // tuning aid: SG_TAIL_TRACE=1 prints the phase timestamps (100 MHz) of block 0 after every launch (synchronises)
     static const bool tr_on = sg_tune_env("SG_TAIL_TRACE") != nullptr;
     static PerDeviceScratch tr_buf;

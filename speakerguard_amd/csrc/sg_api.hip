@@ -400,11 +400,8 @@ int run_mfcc_adjoint(sg_ctx* ctx, const float* x, const PassDims& d, const sg_di
         tab.mel_cache = w.mel_cache;
     }
     tab.rep_utts = d.Bu;
-    const int utts = d.Bu > 0 ? d.Bu : d.B;
-    SG_STAGE(SG_STAGE_MFCC_BWD, launch_mfcc_bwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.dfeats_raw, w.dframes, s));
-    SG_STAGE(SG_STAGE_OVERLAP_ADD, launch_frames_to_wave(w.dframes, utts, d.T, d.F, d.B / utts, grad_acc_in, grad_out, x_update,
-                                                         lower, upper, step, grad_sign, s));
-    return SG_OK;
+    return mfcc_adjoint(ctx, tab, x, d.B, d.T, d.F, w.scale, dz, w.dfeats_raw, w.dframes, d.Bu > 0 ? d.B / d.Bu : 1, grad_acc_in,
+                        grad_out, x_update, lower, upper, step, grad_sign, true, s);
 }
 
 // after the tail produced ws.demb: chain back to the caller's input level
@@ -687,6 +684,18 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
 
 // ---- the chain of the defended device loops (declared in sg_internal.h: sg_api_audionet.hip runs it too)
 namespace sg {
+
+int mfcc_adjoint(sg_ctx* ctx, const MfccTables& tab, const float* x, int B, int T, int F, const float* scale, const sg_dither* dz,
+                 const float* dfeats, float* dframes, int reps, const float* acc_in, float* grad_out, float* x_io, const float* lower,
+                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s) {
+    if (staged) trace_mark(ctx, SG_STAGE_MFCC_BWD, s, 0);
+    SG_HIP(launch_mfcc_bwd(tab, x, B, T, F, scale, dz, dfeats, dframes, s));
+    if (staged) trace_mark(ctx, SG_STAGE_MFCC_BWD, s, 1);
+    if (staged) trace_mark(ctx, SG_STAGE_OVERLAP_ADD, s, 0);
+    SG_HIP(launch_frames_to_wave(dframes, B / reps, T, F, reps, acc_in, grad_out, x_io, lower, upper, step, grad_sign, s));
+    if (staged) trace_mark(ctx, SG_STAGE_OVERLAP_ADD, s, 1);
+    return SG_OK;
+}
 
 int ensure_def_workspace(sg_ctx* ctx, int rows, int T, int n_out, int n_saved, bool rep, hipStream_t s) {
     DefWorkspace& dw = ctx->def_ws;
@@ -1017,29 +1026,15 @@ int sg_xv_load(sg_ctx* ctx, const sg_xv_weights* w) {
                 for (int i = 0; i < kEmb; ++i) pa[(size_t)d * kLdaLd + i] = (float)row[i];
             }
         }
-        double ldg = 0.0, ldw = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double psi = w->plda_psi[d];
-            ldg += std::log(1.0 + psi / (psi + 1.0));
-            ldw += std::log(psi + 1.0);
-        }
-        m.logdet_given = (float)ldg;
-        m.logdet_without = (float)ldw;
         rc |= dev_upload(ctx, pool, &m.emb_mean, std::vector<float>(w->emb_mean, w->emb_mean + kEmb));
         rc |= dev_upload(ctx, pool, &m.lda, lda);
         rc |= dev_upload(ctx, pool, &m.lda_t, ldat);
-        rc |= dev_upload(ctx, pool, &m.plda_mean, std::vector<float>(w->plda_mean, w->plda_mean + D));
         rc |= dev_upload(ctx, pool, &m.plda_p, p);
         rc |= dev_upload(ctx, pool, &m.plda_pt, pt);
         rc |= dev_upload(ctx, pool, &m.pa, pa);
-        rc |= dev_upload(ctx, pool, &m.plda_psi, std::vector<float>(w->plda_psi, w->plda_psi + D));
-        rc |= dev_upload(ctx, pool, &m.enroll, std::vector<float>(w->enroll, w->enroll + (size_t)S * D));
+        rc |= plda_backend_load(ctx, pool, &m.be, w->plda_mean, w->plda_psi, w->enroll, D, S, w->threshold);
     }
     if (rc) return fail(ctx, SG_ERR_HIP, "model upload failed: %s", ctx->err.c_str());
-    m.D = D;
-    m.S = S;
-    m.enroll_cap = S;
-    m.threshold = w->threshold;
     m.loaded = true;
     return SG_OK;
 }
@@ -1047,35 +1042,13 @@ int sg_xv_load(sg_ctx* ctx, const sg_xv_weights* w) {
 int sg_xv_set_enroll(sg_ctx* ctx, const float* enroll_host, int32_t S, float threshold) {
     if (!ctx || !ctx->xv.loaded) return fail(ctx, SG_ERR_STATE, "no model loaded");
     if (S < 1 || S > 1024) return fail(ctx, SG_ERR_ARG, "S must be 1..1024");
-    XvModel& m = ctx->xv;
-    if (enroll_host) {
-        SG_HIP(hipSetDevice(ctx->device));
-        SG_HIP(hipDeviceSynchronize());  // earlier passes may still read the table
-        if (S > m.enroll_cap) {  // grow: the old table goes back to the allocator, nothing accumulates
-            float* fresh = nullptr;
-            int rc = dev_alloc(ctx, m.allocs, &fresh, (size_t)S * m.D);
-            if (rc) return rc;
-            for (size_t i = 0; i < m.allocs.size(); ++i)
-                if (m.allocs[i] == m.enroll) {
-                    (void)hipFree(m.enroll);
-                    m.allocs.erase(m.allocs.begin() + i);
-                    break;
-                }
-            m.enroll = fresh;
-            m.enroll_cap = S;
-        }
-        SG_HIP(hipMemcpy(m.enroll, enroll_host, (size_t)S * m.D * sizeof(float), hipMemcpyHostToDevice));
-        m.S = S;
-    }
-    m.threshold = threshold;
-    return SG_OK;
+    return plda_backend_set_enroll(ctx, &ctx->xv.be, ctx->xv.allocs, enroll_host, S, threshold);
 }
 
 int sg_xv_enroll_override(sg_ctx* ctx, const float* enroll_dev, int32_t S) {
     if (!ctx || !ctx->xv.loaded) return fail(ctx, SG_ERR_STATE, "no model loaded");
     if (enroll_dev && (S < 1 || S > 1024)) return fail(ctx, SG_ERR_ARG, "S must be 1..1024");
-    ctx->xv.enroll_override = enroll_dev;
-    ctx->xv.S_override = enroll_dev ? S : 0;
+    plda_backend_override(&ctx->xv.be, enroll_dev, S);
     return SG_OK;
 }
 
@@ -1108,11 +1081,8 @@ int sg_xv_mfcc_backward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, c
     PassDims d;
     int rc = check_dims(ctx, B, T, SG_FLAG_WAV, &d);  // sizes the per-frame gradient scratch
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    Workspace& w = ctx->ws;
-    SG_HIP(launch_mfcc_bwd(ctx->tab, x_dev, d.B, d.T, d.F, scale_dev, dither, dfeats_dev, w.dframes, s));
-    SG_HIP(launch_frames_to_wave(w.dframes, d.B, d.T, d.F, 1, nullptr, grad_dev, nullptr, nullptr, nullptr, 0.f, 1, s));
-    return SG_OK;
+    return mfcc_adjoint(ctx, ctx->tab, x_dev, d.B, d.T, d.F, scale_dev, dither, dfeats_dev, ctx->ws.dframes, 1, nullptr, grad_dev, nullptr,
+                        nullptr, nullptr, 0.f, 1, false, (hipStream_t)stream);
 }
 
 int sg_xv_cmvn_backward(sg_ctx* ctx, const float* dout_dev, int32_t B, int32_t F, float* din_dev, void* stream) {

@@ -87,7 +87,9 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
     if ((rc = iv_ensure_workspace(ctx, d.chunk, d.F, flag == SG_IV_FLAG_WAV, s, grad != nullptr))) return rc;
     IvWorkspace& w = ctx->iv_ws;
     const IvModel& m = ctx->iv;
-    const int S = m.enroll_override ? m.S_override : m.S;
+    const float* enroll;
+    int S;
+    plda_backend_active(m.be, &enroll, &S);
     if (flag == SG_IV_FLAG_WAV && (rc = sg_input_scale(ctx, x, (int64_t)B * d.T, w.scale, s))) return rc;
     for (int b0 = 0; b0 < B; b0 += d.chunk) {
         const int nb = std::min(d.chunk, B - b0);
@@ -119,7 +121,7 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
             t.loss = *loss;
             t.coef = loss->coef_dev ? loss->coef_dev + (size_t)b0 * S : nullptr;
         }
-        t.emb = emb ? emb + (size_t)b0 * m.D : nullptr;
+        t.emb = emb ? emb + (size_t)b0 * m.be.D : nullptr;
         t.scores = scores ? scores + (size_t)b0 * S : nullptr;
         t.decisions = dec ? dec + b0 : nullptr;
         t.loss_out = (loss && loss_out) ? loss_out + b0 : nullptr;
@@ -136,11 +138,12 @@ int iv_run(sg_ctx* ctx, const char* who, const float* x, const int64_t* y, int B
         } else if (flag == SG_IV_FLAG_RAW) {
             SG_HIP(launch_iv_delta_cmvn_bwd(w.dcmvn, true, nb, d.F, w.ddelta, gc, kIvCep, s));
         } else if (flag == SG_IV_FLAG_WAV) {
-            // d raw zero-padded to the MFCC's 30 columns, then the launches of sg_xv_mfcc_backward with the forward's scale and
-            // dither keys (the entry itself sizes its scratch from the x-vector model's workspace: this one is the chunk's own)
+            // d raw zero-padded to the MFCC's 30 columns, then the MFCC adjoint with the forward's scale and dither keys, on the
+            // chunk's own frame buffer
             SG_HIP(launch_iv_delta_cmvn_bwd(w.dcmvn, true, nb, d.F, w.ddelta, w.draw, kCep, s));
-            SG_HIP(launch_mfcc_bwd(ctx->tab, xc, nb, d.T, d.F, w.scale, &dz, w.draw, w.dframes, s));
-            SG_HIP(launch_frames_to_wave(w.dframes, nb, d.T, d.F, 1, nullptr, gc, nullptr, nullptr, nullptr, 0.f, 1, s));
+            if ((rc = mfcc_adjoint(ctx, ctx->tab, xc, nb, d.T, d.F, w.scale, &dz, w.draw, w.dframes, 1, nullptr, gc, nullptr, nullptr,
+                                   nullptr, 0.f, 1, false, s)))
+                return rc;
         }
     }
     return SG_OK;
@@ -175,12 +178,6 @@ int sg_iv_load(sg_ctx* ctx, const sg_iv_weights* w) {
         for (int k = 0; k <= R; ++k) ldat[(size_t)k * D + d] = w->lda[(size_t)d * (R + 1) + k];
         for (int j = 0; j < D; ++j) pt[(size_t)j * D + d] = w->plda_transform[(size_t)d * D + j];
     }
-    double ldg = 0.0, ldw = 0.0;
-    for (int d = 0; d < D; ++d) {
-        const double psi = w->plda_psi[d];
-        ldg += std::log(1.0 + psi / (psi + 1.0));
-        ldw += std::log(psi + 1.0);
-    }
     int rc = SG_OK;
     rc |= dev_upload(ctx, pool, &m.gconst, std::vector<float>(w->gconsts, w->gconsts + C));
     rc |= dev_upload(ctx, pool, &m.W, W);
@@ -189,16 +186,11 @@ int sg_iv_load(sg_ctx* ctx, const sg_iv_weights* w) {
     rc |= dev_upload(ctx, pool, &m.U, U);
     rc |= dev_upload(ctx, pool, &m.emb_mean, std::vector<float>(w->emb_mean, w->emb_mean + R));
     rc |= dev_upload(ctx, pool, &m.lda_t, ldat);
-    rc |= dev_upload(ctx, pool, &m.plda_mean, std::vector<float>(w->plda_mean, w->plda_mean + D));
     rc |= dev_upload(ctx, pool, &m.plda_pt, pt);
-    rc |= dev_upload(ctx, pool, &m.plda_psi, std::vector<float>(w->plda_psi, w->plda_psi + D));
-    rc |= dev_upload(ctx, pool, &m.enroll, std::vector<float>(w->enroll, w->enroll + (size_t)S * D));
+    rc |= plda_backend_load(ctx, pool, &m.be, w->plda_mean, w->plda_psi, w->enroll, D, S, w->threshold);
     if (rc) return fail(ctx, SG_ERR_HIP, "sg_iv_load: model upload failed: %s", ctx->err.c_str());
-    m.C = C; m.Cp = Cp; m.R = R; m.P = P; m.Pp = Pp; m.D = D; m.S = S; m.enroll_cap = S;
+    m.C = C; m.Cp = Cp; m.R = R; m.P = P; m.Pp = Pp;
     m.offset = w->ivector_offset;
-    m.threshold = w->threshold;
-    m.logdet_given = (float)ldg;
-    m.logdet_without = (float)ldw;
     m.loaded = true;
     return SG_OK;
 }
@@ -206,35 +198,13 @@ int sg_iv_load(sg_ctx* ctx, const sg_iv_weights* w) {
 int sg_iv_set_enroll(sg_ctx* ctx, const float* enroll_host, int32_t S, float threshold) {
     if (!ctx || !ctx->iv.loaded) return fail(ctx, SG_ERR_STATE, "no i-vector model loaded");
     if (S < 1 || S > 1024) return fail(ctx, SG_ERR_ARG, "S must be 1..1024");
-    IvModel& m = ctx->iv;
-    if (enroll_host) {
-        SG_HIP(hipSetDevice(ctx->device));
-        SG_HIP(hipDeviceSynchronize());  // earlier passes may still read the table
-        if (S > m.enroll_cap) {
-            float* fresh = nullptr;
-            int rc = dev_alloc(ctx, m.allocs, &fresh, (size_t)S * m.D);
-            if (rc) return rc;
-            for (size_t i = 0; i < m.allocs.size(); ++i)
-                if (m.allocs[i] == m.enroll) {
-                    (void)hipFree(m.enroll);
-                    m.allocs.erase(m.allocs.begin() + i);
-                    break;
-                }
-            m.enroll = fresh;
-            m.enroll_cap = S;
-        }
-        SG_HIP(hipMemcpy(m.enroll, enroll_host, (size_t)S * m.D * sizeof(float), hipMemcpyHostToDevice));
-        m.S = S;
-    }
-    m.threshold = threshold;
-    return SG_OK;
+    return plda_backend_set_enroll(ctx, &ctx->iv.be, ctx->iv.allocs, enroll_host, S, threshold);
 }
 
 int sg_iv_enroll_override(sg_ctx* ctx, const float* enroll_dev, int32_t S) {
     if (!ctx || !ctx->iv.loaded) return fail(ctx, SG_ERR_STATE, "no i-vector model loaded");
     if (enroll_dev && (S < 1 || S > 1024)) return fail(ctx, SG_ERR_ARG, "S must be 1..1024");
-    ctx->iv.enroll_override = enroll_dev;
-    ctx->iv.S_override = enroll_dev ? S : 0;
+    plda_backend_override(&ctx->iv.be, enroll_dev, S);
     return SG_OK;
 }
 

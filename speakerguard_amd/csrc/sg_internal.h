@@ -231,11 +231,25 @@ struct MfccTables {          // device pointers
                              // repeats share the waveform row, repeat r draws its dither from key seed + r * 0xC2B2AE3D27D4EB4F
 };
 
-struct XvModel {
-    bool loaded = false;
+// The PLDA back end both speaker models score with (plda_backend.hip; the kernels' side: plda_device.h).  The transform
+// matrices stay with their model: their layouts differ.
+struct PldaBackend {
     int D = 0, S = 0;
     float threshold = 0.f;
     float logdet_given = 0.f, logdet_without = 0.f;  // sum log(1 + psi/(psi+1)), sum log(psi+1)
+    float* plda_mean = nullptr; // [D]
+    float* plda_psi = nullptr;  // [D]
+    float* enroll = nullptr;    // [S][D]
+    int enroll_cap = 0;         // speakers the enroll buffer holds (plda_backend_set_enroll reuses it)
+    // per-call override of the enrolled set (iv_plda.py:155-165 enroll_embs=): a caller-owned device table that the
+    // next passes score against; the model's own set is untouched
+    const float* enroll_override = nullptr;
+    int S_override = 0;
+};
+
+struct XvModel {
+    bool loaded = false;
+    PldaBackend be;
     // folded TDNN weights, GEMM layouts
     float* wf[kLayers] = {};    // forward  [taps*CinPad][CoutPad]
     float* wb[kLayers] = {};    // backward [taps*CoutPad][CinPad]
@@ -249,17 +263,9 @@ struct XvModel {
     int Dp = 0;                 // D rounded up to a multiple of 4 (row stride of the transposed / PLDA matrices below)
     float* lda = nullptr;       // [D][kLdaLd]: the (D, 513) LDA matrix, rows padded to 516 floats (16-byte aligned rows)
     float* lda_t = nullptr;     // [513][Dp], zero-padded columns
-    float* plda_mean = nullptr; // [D]
     float* plda_p = nullptr;    // [D][Dp], zero-padded columns
     float* plda_pt = nullptr;   // [D][Dp] transposed, zero-padded columns
     float* pa = nullptr;        // [D][kLdaLd]: (P A)[d][i], i < 512 -- the backward's P^T and LDA^T as one product (float64 product, rounded once)
-    float* plda_psi = nullptr;  // [D]
-    float* enroll = nullptr;    // [S][D]
-    int enroll_cap = 0;         // speakers the enroll buffer holds (sg_xv_set_enroll reuses it)
-    // per-call override of the enrolled set (iv_plda.py:155-165 enroll_embs=): a caller-owned device table that the
-    // next passes score against; the model's own set is untouched
-    const float* enroll_override = nullptr;
-    int S_override = 0;
     std::vector<void*> allocs;  // device memory owned by this model (freed on reload / destroy)
 };
 
@@ -353,8 +359,8 @@ struct IvModel {
     bool loaded = false;
     int C = 0, Cp = 0;          // Gaussians, rounded up to a multiple of 64 (the loglik kernel's wave tile)
     int R = 0, P = 0, Pp = 0;   // i-vector dimension, R (R + 1) / 2, P rounded up to a multiple of 256
-    int D = 0, S = 0;
-    float offset = 0.f, threshold = 0.f, logdet_given = 0.f, logdet_without = 0.f;
+    PldaBackend be;
+    float offset = 0.f;
     float* gconst = nullptr;    // [C]
     float* W = nullptr;         // [kIvK][Cp] k-major, zero columns past C
     uint16_t* pairs = nullptr;  // [kIvK]: i | j << 8 with z_k = x_i x_j, x_72 = 1 (the linear terms)
@@ -362,13 +368,7 @@ struct IvModel {
     float* U = nullptr;         // [C][Pp]: upper triangle of V_c M_c, zero past P
     float* emb_mean = nullptr;  // [R]
     float* lda_t = nullptr;     // [R + 1][D] (row R: the offset column)
-    float* plda_mean = nullptr; // [D]
     float* plda_pt = nullptr;   // [D][D] transposed
-    float* plda_psi = nullptr;  // [D]
-    float* enroll = nullptr;    // [S][D]
-    int enroll_cap = 0;
-    const float* enroll_override = nullptr;
-    int S_override = 0;
     std::vector<void*> allocs;
 };
 // chunk buffers, grown on demand before the first launch of a call
@@ -558,6 +558,22 @@ int dev_grow(sg_ctx* ctx, std::vector<void*>& pool, DevBuf<T>* buf, size_t need,
     buf->cap = need;
     return SG_OK;
 }
+// ---- the PLDA back end of a speaker model (plda_backend.hip); `pool`: the model's allocations
+// the two log-determinants (float64 sums, rounded once) and the uploads of plda_mean, plda_psi and the enrolled table
+int plda_backend_load(sg_ctx* ctx, std::vector<void*>& pool, PldaBackend* be, const float* plda_mean, const float* plda_psi,
+                      const float* enroll, int D, int S, float threshold);
+// a new enrolled table (waits for the device, grows the buffer and frees the old one when S exceeds it) and / or threshold
+int plda_backend_set_enroll(sg_ctx* ctx, PldaBackend* be, std::vector<void*>& pool, const float* enroll_host, int S, float threshold);
+inline void plda_backend_override(PldaBackend* be, const float* enroll_dev, int S) {
+    be->enroll_override = enroll_dev;
+    be->S_override = enroll_dev ? S : 0;
+}
+// the table and the count a launch scores against: the per-call override, else the model's own
+inline void plda_backend_active(const PldaBackend& be, const float** enroll, int* S) {
+    *enroll = be.enroll_override ? be.enroll_override : be.enroll;
+    *S = be.enroll_override ? be.S_override : be.S;
+}
+
 // A new entry (key and blob filled in; the cache owns it from here on) goes to the device on `s` and into `cache`, which holds
 // `cap` entries: when it is full, the oldest leaves once nothing enqueued can still read it -- the upload is enqueued first,
 // then the stream is waited for, the one case that waits.  On any failure the entry and its device memory are released.  `of`
@@ -833,6 +849,11 @@ hipError_t launch_mfcc_bwd(const MfccTables& t, const float* x, int B, int T, in
 hipError_t launch_frames_to_wave(const float* dframes, int B, int T, int F, int R, const float* acc_in, float* grad_out,
                                  float* x_io, const float* lower, const float* upper, float step, int grad_sign,
                                  hipStream_t s);
+// The two launches above as the one MFCC adjoint (sg_api.hip): dfeats (B, F, 30) -> dframes (the caller's buffer) -> d loss / d x,
+// the B rows being `reps` repeats of B / reps utterances.  `staged`: the launches carry their SG_STAGE tags (the x-vector pass)
+int mfcc_adjoint(sg_ctx* ctx, const MfccTables& tab, const float* x, int B, int T, int F, const float* scale, const sg_dither* dz,
+                 const float* dfeats, float* dframes, int reps, const float* acc_in, float* grad_out, float* x_io, const float* lower,
+                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s);
 hipError_t launch_pgd_update(float* x, const float* g, const float* lo, const float* hi, int64_t n,
                              float step, int grad_sign, hipStream_t s);
 // planes (G, n): the cotangents of G EOT repeats; total = ((carry +) p0 + p1) + ... in float32, in that order.  sum_out != null:

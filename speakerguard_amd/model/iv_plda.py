@@ -18,14 +18,13 @@ Differences a caller can observe, all deliberate: ``dither`` / ``dither_seed`` a
 ignored (the log-likelihoods are one contraction, chunked by the library); there is no Gaussian pruning, as in the reference.
 """
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
 from .. import _native as N
-from ._engine_ops import EngineOps, _f32
-from .xv_plda import parse_enroll_model_file, parse_mean_file, parse_plda_file, parse_transform_mat_file
+from ._engine_ops import _f32
+from ._plda_model import PldaModel, parse_enroll_model_file, parse_mean_file, parse_plda_file, parse_transform_mat_file
 
 BITS = 16
 IV_CEPS, IV_DIM = 24, 72
@@ -126,11 +125,13 @@ def parse_ie_file(path):
     return out
 
 
-class iv_plda(EngineOps):
+class iv_plda(PldaModel):
+    """The back end, the enrolled speakers and the scoring API: ``PldaModel``."""
     allowed_flags = [0, 1, 2, 3]  # 0: wav; 1: raw feat; 2: delta feat; 3: cmvn feat (iv_plda.py:75-77)
-    range_type = "origin"
     _feat_widths = {1: IV_CEPS, 2: IV_DIM, 3: IV_DIM}
     device_loops = False  # no pgd_run*: attack.FGSM._device_route sends every attack to the step loop
+    _entry, _fourth = "sg_iv", "want_ivector"  # the fourth output: the raw i-vector (B, R)
+    _fourth_width = property(lambda self: self.ivector_dim)
 
     def __init__(self, fgmm_file, extractor_file, plda_file, mean_file, transform_mat_file, model_file=None, threshold=None,
                  device="cuda:0", gmm_frame_bs=200, dither=1.0, dither_seed=0, white_box=False):
@@ -155,49 +156,20 @@ class iv_plda(EngineOps):
 
     def _init(self, weights, threshold, device, dither, dither_seed, spk_ids):
         hp = self._open(device)  # host arrays must outlive sg_iv_load
-        self.threshold = threshold if threshold else -np.inf  # iv_plda.py:73
-        self.dither = float(dither)
-        self.dither_seed = int(dither_seed)
-        self._draw = 0
         ext = _f32(weights["extractor"])
         Cn, dim, R = ext.shape
         if dim != IV_DIM or _f32(weights["means_invcovars"]).shape != (Cn, IV_DIM):
             raise ValueError("the engine's i-vector front-end is 24 cepstra + deltas: feature dimension must be %d" % IV_DIM)
-        lda = _f32(weights["lda"])
-        D = lda.shape[0]
-        if lda.shape[1] != R + 1:
-            raise ValueError("transform matrix must be (D, %d): LDA with offset column (iv_plda.py:430)" % (R + 1))
-        enroll = weights.get("enroll")
-        self._has_enroll = enroll is not None
-        if enroll is None:
-            enroll = np.zeros((1, D), np.float32)  # scoring then needs enroll_embs= at call time
-        enroll = _f32(enroll).reshape(-1, D)
         w = N.IvWeights()
-        w.C, w.R, w.D, w.S = Cn, R, D, enroll.shape[0]
+        self._init_backend(weights, w, threshold, dither, dither_seed, spk_ids, R, hp)
+        w.C, w.R = Cn, R
         w.gconsts, w.means_invcovars = hp(weights["gconsts"]), hp(weights["means_invcovars"])
         w.invcovars, w.extractor, w.sigma_inv = hp(weights["invcovars"]), hp(ext), hp(weights["sigma_inv"])
         w.ivector_offset = float(weights["ivector_offset"])
-        w.emb_mean, w.lda = hp(weights["emb_mean"]), hp(lda)
-        w.plda_mean, w.plda_transform, w.plda_psi = hp(weights["plda_mean"]), hp(weights["plda_transform"]), hp(weights["plda_psi"])
-        w.enroll = hp(enroll)
-        w.threshold = float(self.threshold) if np.isfinite(self.threshold) else -math.inf
         self.ctx.call("sg_iv_load", C.byref(w))
-        self.num_gaussians, self.ivector_dim, self.dim = Cn, R, D
-        self.num_spks = enroll.shape[0]
-        self.spk_ids = spk_ids if spk_ids is not None else [str(i) for i in range(self.num_spks)]
-        self.enroll_embs = torch.from_numpy(enroll).to(self.device)
-        self.emb_mean = torch.from_numpy(_f32(weights["emb_mean"])).to(self.device)
-        self.transform_mat = torch.from_numpy(lda).to(self.device)
+        self.num_gaussians, self.ivector_dim = Cn, R
 
     # ------------------------------------------------------------------ plumbing
-    def eval(self):
-        return self
-
-    def to(self, device):
-        if torch.device(device) != self.device and torch.device(device).index not in (None, self.device.index):
-            raise N.NativeError("the engine context is bound to %s" % self.device)
-        return self
-
     def _prep(self, x, flag):
         assert flag in self.allowed_flags
         x = x.to(self.device, torch.float32).contiguous()
@@ -208,54 +180,12 @@ class iv_plda(EngineOps):
         assert x.dim() == 3 and x.shape[2] == width, "flag-%d input must be (B, F, %d)" % (flag, width)
         return x, x.shape[0], x.shape[1]
 
-    def _dither(self, noise=None, seed=None):
-        d = N.Dither()
-        d.dither = self.dither
-        d.index_base, d.row_base, d.rep_rows = self.row_keys()
-        d.noise_dev = None if noise is None else noise.data_ptr()
-        if seed is not None:
-            d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-            return d
-        d.seed = self.noise_seed(self.dither_seed, self._draw)
-        self._draw += 1  # every forward draws fresh noise, like the reference's global RNG
-        return d
-
-    def set_enroll(self, enroll_embs=None, threshold=None):
-        """Replace the enrolled speakers and/or the decision threshold on the device."""
-        if threshold is not None:
-            self.threshold = threshold
-        thr = float(self.threshold) if np.isfinite(self.threshold) else -math.inf
-        if enroll_embs is not None:
-            e = _f32(enroll_embs).reshape(-1, self.dim)
-            self.ctx.call("sg_iv_set_enroll", e.ctypes.data_as(C.c_void_p), e.shape[0], thr)
-            self.enroll_embs = torch.from_numpy(e).to(self.device)
-            self.num_spks = e.shape[0]
-            self._has_enroll = True
-        else:
-            self.ctx.call("sg_iv_set_enroll", None, self.num_spks, thr)
-
-    def _enroll_for_call(self, enroll_embs):
-        if enroll_embs is None:
-            if not self._has_enroll:
-                raise AssertionError("no enrolled speakers: pass enroll_embs (iv_plda.py:162-163)")
-            return None
-        if not isinstance(enroll_embs, torch.Tensor):
-            enroll_embs = torch.from_numpy(_f32(enroll_embs))
-        return enroll_embs.to(self.device, torch.float32).reshape(-1, self.dim).contiguous()
-
     # ------------------------------------------------------------------ reference API
     def compute_feat(self, x, flag=1, dither_noise=None):
         """wav (B,1,T) -> raw (B,F,24) / delta (B,F,72) / CMVN (B,F,72) features; iv_plda.py:86-109.  The 24-cepstrum MFCC
         is the first 24 columns of the x-vector front-end's 30 (same mel bank, lifter by column index, c0 <- energy)."""
         assert flag in (1, 2, 3)
-        x, B, T = self._prep(x, 0)
-        F = N.load().sg_xv_num_frames(T)
-        scale = torch.empty(1, device=self.device, dtype=torch.float32)
-        feats = torch.empty(B, F, 30, device=self.device, dtype=torch.float32)
-        s = self._stream()
-        self.ctx.call("sg_input_scale", N._ptr(x), x.numel(), N._ptr(scale), s)
-        dz = self._dither(dither_noise)
-        self.ctx.call("sg_xv_mfcc", N._ptr(x), B, T, N._ptr(scale), C.byref(dz), N._ptr(feats), s)
+        feats, _ = self._mfcc(x, dither_noise)
         raw = feats[:, :, :IV_CEPS].contiguous()
         return raw if flag == 1 else self.comput_feat_from_feat(raw, 1, flag)
 
@@ -302,47 +232,9 @@ class iv_plda(EngineOps):
         self.ctx.call("sg_iv_extract", N._ptr(zeroth), N._ptr(first), B, N._ptr(w), self._stream())
         return w
 
-    def _forward(self, x, flag, want_emb=False, want_ivector=False, dither_noise=None, enroll=None, dither_seed=None):
-        x, B, TF = self._prep(x, flag)
-        n_spk = self.num_spks if enroll is None else enroll.shape[0]
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, n_spk, device=self.device, dtype=torch.float32)
-        emb = torch.empty(B, self.dim, device=self.device, dtype=torch.float32) if want_emb else None
-        ivec = torch.empty(B, self.ivector_dim, device=self.device, dtype=torch.float32) if want_ivector else None
-        dz = self._dither(dither_noise, dither_seed)
-        if enroll is not None:
-            self.ctx.call("sg_iv_enroll_override", N._ptr(enroll), enroll.shape[0])
-        try:
-            self.ctx.call("sg_iv_forward", N._ptr(x), B, TF, flag, C.byref(dz), N._ptr(dec), N._ptr(scores), N._ptr(emb),
-                          N._ptr(ivec), self._stream())
-        finally:
-            if enroll is not None:
-                self.ctx.call("sg_iv_enroll_override", None, 0)
-                enroll.record_stream(torch.cuda.current_stream(self.device))
-        return dec, scores, emb, ivec
-
-    def embedding(self, x, flag=0):
-        return self._forward(x, flag, want_emb=True)[2]
-
     def ivector(self, x, flag=0):
         """the raw i-vector (B,R), before mean subtraction / LDA / PLDA (parity tests)"""
         return self._forward(x, flag, want_ivector=True)[3]
-
-    def forward(self, x, flag=0, return_emb=False, enroll_embs=None, dither_seed=None):
-        enroll = self._enroll_for_call(enroll_embs)
-        _, scores, emb, _ = self._forward(x, flag, want_emb=return_emb, enroll=enroll, dither_seed=dither_seed)
-        return (scores, emb) if return_emb else scores
-
-    __call__ = forward
-
-    def score(self, x, flag=0, enroll_embs=None):
-        return self.forward(x, flag=flag, enroll_embs=enroll_embs)
-
-    def make_decision(self, x, flag=0, enroll_embs=None):
-        """-> (decisions int64 (B,), scores (B, n_spk)); iv_plda.py:182-194."""
-        enroll = self._enroll_for_call(enroll_embs)
-        dec, scores, _, _ = self._forward(x, flag, enroll=enroll)
-        return dec, scores
 
     # ------------------------------------------------------------------ engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):

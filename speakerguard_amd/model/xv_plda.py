@@ -18,68 +18,24 @@ Differences a caller can observe, all deliberate:
     outputs of ``make_decision`` carry no autograd graph.
 """
 import ctypes as C
-import math
 import types
 
-import numpy as np
 import torch
 
 from .. import _native as N
-from ._engine_ops import EngineOps, _f32
+from ._plda_model import (PldaModel, parse_enroll_model_file, parse_mean_file, parse_plda_file,  # noqa: F401 (re-exported)
+                          parse_transform_mat_file)
 
 BITS = 16
 _TDNN = ("tdnn1", "tdnn2", "tdnn3", "tdnn4", "tdnn5")
 
 
-# ---------------------------------------------------------------------------- file parsers
-def parse_mean_file(path):
-    """Kaldi text vector `` [ v0 v1 ... ]`` (format read at reference model/utils.py:50-60)."""
-    with open(path) as f:
-        toks = f.readline().split()
-    return np.array([float(t) for t in toks[1:-1]], dtype=np.float32)
-
-
-def parse_transform_mat_file(path):
-    """Kaldi text matrix: `` [`` then one row per line, last row closed by ``]`` (model/utils.py:63-80)."""
-    rows = []
-    with open(path) as f:
-        for line in f.readlines()[1:]:
-            toks = line.replace("]", " ").split()
-            if toks:
-                rows.append([float(t) for t in toks])
-    return np.array(rows, dtype=np.float32)
-
-
-def parse_plda_file(path):
-    """Kaldi text PLDA: ``<Plda> [ mean ]``, matrix, `` [ psi ]`` (model/_xv_plda/plda.py:27-49)."""
-    with open(path) as f:
-        lines = f.readlines()
-    mean = np.array([float(t) for t in lines[0].split()[2:-1]], dtype=np.float32)
-    D = mean.shape[0]
-    rows = []
-    for line in lines[2:2 + D]:
-        rows.append([float(t) for t in line.replace("]", " ").split()])
-    psi = np.array([float(t) for t in lines[2 + D].split()[1:-1]], dtype=np.float32)
-    return mean, np.array(rows, dtype=np.float32), psi
-
-
-def parse_enroll_model_file(path):
-    """Rows ``id path znorm_mean znorm_std``; each path holds a (1, D) tensor (model/utils.py:21-47)."""
-    info = np.loadtxt(path, dtype=str, comments=None)
-    if info.ndim == 1:
-        info = info[np.newaxis, :]
-    spk_ids = list(info[:, 0])
-    z_means = info[:, 2].astype(np.float32)
-    z_stds = info[:, 3].astype(np.float32)
-    embs = [torch.load(p, map_location="cpu").reshape(1, -1).float().numpy() for p in info[:, 1]]
-    return spk_ids, z_means, z_stds, np.concatenate(embs, 0)
-
-
-class xv_plda(EngineOps):
+class xv_plda(PldaModel):
+    """The back end, the enrolled speakers and the scoring API: ``PldaModel``."""
     allowed_flags = [0, 1, 2]  # 0: wav; 1: raw feat; 2: cmvn feat (xv_plda.py:45-47)
-    range_type = "origin"
     _feat_width = 30
     _debug_activation = "sg_xv_debug_activation"
+    _entry, _fourth, _fourth_width = "sg_xv", "want_tdnn", 512  # the fourth output: fc1's output before the mean subtraction
 
     def __init__(self, extractor_file, plda_file, mean_file, transform_mat_file, model_file=None,
                  threshold=None, device="cuda:0", dither=1.0, dither_seed=0):
@@ -102,10 +58,6 @@ class xv_plda(EngineOps):
 
     def _init(self, weights, threshold, device, dither, dither_seed, spk_ids):
         hp = self._open(device)  # host arrays must outlive sg_xv_load
-        self.threshold = threshold if threshold else -np.inf  # xv_plda.py:41
-        self.dither = float(dither)
-        self.dither_seed = int(dither_seed)
-        self._draw = 0
         sd = weights["state_dict"]
         w = N.XvWeights()
         for l, name in enumerate(_TDNN):
@@ -114,34 +66,11 @@ class xv_plda(EngineOps):
             w.bn_mean[l] = hp(sd["bn_" + name + ".running_mean"])
             w.bn_var[l] = hp(sd["bn_" + name + ".running_var"])
         w.fc1_weight, w.fc1_bias = hp(sd["fc1.weight"]), hp(sd["fc1.bias"])
-        lda = _f32(weights["lda"])
-        D = lda.shape[0]
-        if lda.shape[1] != 513:
-            raise ValueError("transform matrix must be (D, 513): LDA with offset column (iv_plda.py:430)")
-        enroll = weights.get("enroll")
-        if enroll is None:
-            enroll = np.zeros((1, D), np.float32)  # scoring then needs enroll_embs= at call time
-            self._has_enroll = False
-        else:
-            self._has_enroll = True
-        enroll = _f32(enroll).reshape(-1, D)
-        w.emb_mean, w.lda = hp(weights["emb_mean"]), hp(lda)
-        w.plda_mean, w.plda_transform, w.plda_psi = hp(weights["plda_mean"]), hp(weights["plda_transform"]), hp(weights["plda_psi"])
-        w.enroll = hp(enroll)
-        w.D, w.S, w.bn_eps = D, enroll.shape[0], 1e-5
-        w.threshold = float(self.threshold) if np.isfinite(self.threshold) else -math.inf
+        w.bn_eps = 1e-5
+        self._init_backend(weights, w, threshold, dither, dither_seed, spk_ids, 512, hp)
         self.ctx.call("sg_xv_load", C.byref(w))
-        self.dim = D
-        self.num_spks = enroll.shape[0]
-        self.spk_ids = spk_ids if spk_ids is not None else [str(i) for i in range(self.num_spks)]
-        self.enroll_embs = torch.from_numpy(enroll).to(self.device)
-        self.emb_mean = torch.from_numpy(_f32(weights["emb_mean"])).to(self.device)
-        self.transform_mat = torch.from_numpy(lda).to(self.device)
 
     # ------------------------------------------------------------------ plumbing
-    def eval(self):
-        return self
-
     def configure_frontend(self, fft_bits=32):
         """Precision of the MFCC's 512-point transforms on the engine (sg_xv_configure): 32 = float32, the reference's own
         (torchaudio 0.6's kaldi.mfcc is float32 end to end, xv_plda.py:114-148) and the default; 64 = float64 transforms
@@ -149,81 +78,18 @@ class xv_plda(EngineOps):
         self.ctx.call("sg_xv_configure", int(fft_bits))
         return self
 
-    def to(self, device):
-        if torch.device(device) != self.device and torch.device(device).index not in (None, self.device.index):
-            raise N.NativeError("the engine context is bound to %s" % self.device)
-        return self
-
-    def next_dither_seed(self):
-        """Draws the generator key the next pass would use (and advances the draw counter like that pass would)."""
-        key = self.noise_seed(self.dither_seed, self._draw)
-        self._draw += 1
-        return key
-
-    def _dither(self, noise=None, seed=None):
-        d = N.Dither()
-        d.dither = self.dither
-        # global utterance index of row 0, offset inside the full call (shard.QueryShardedModel), rows per EOT repeat
-        d.index_base, d.row_base, d.rep_rows = self.row_keys()
-        d.noise_dev = None if noise is None else noise.data_ptr()
-        if seed is not None:  # explicit generator key (tests re-play the fused loop's per-pass seeds)
-            d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-            return d
-        d.seed = self.noise_seed(self.dither_seed, self._draw)
-        self._draw += 1  # every forward draws fresh noise, like the reference's global RNG
-        return d
-
-    def set_enroll(self, enroll_embs=None, threshold=None):
-        """Replace the enrolled speakers and/or the decision threshold on the device."""
-        if threshold is not None:
-            self.threshold = threshold
-        thr = float(self.threshold) if np.isfinite(self.threshold) else -math.inf
-        if enroll_embs is not None:
-            e = _f32(enroll_embs).reshape(-1, self.dim)
-            self.ctx.call("sg_xv_set_enroll", e.ctypes.data_as(C.c_void_p), e.shape[0], thr)
-            self.enroll_embs = torch.from_numpy(e).to(self.device)
-            self.num_spks = e.shape[0]
-            self._has_enroll = True
-        else:
-            self.ctx.call("sg_xv_set_enroll", None, self.num_spks, thr)
-
-    def _enroll_for_call(self, enroll_embs):
-        """Device table (S, D) for a per-call ``enroll_embs=`` override, or None for the model's own set."""
-        if enroll_embs is None:
-            if not self._has_enroll:
-                raise AssertionError("no enrolled speakers: pass enroll_embs (iv_plda.py:162-163)")
-            return None
-        if not isinstance(enroll_embs, torch.Tensor):
-            enroll_embs = torch.from_numpy(_f32(enroll_embs))
-        return enroll_embs.to(self.device, torch.float32).reshape(-1, self.dim).contiguous()
-
     # ------------------------------------------------------------------ reference API
     def compute_feat(self, x, flag=1, dither_noise=None):
         """wav (B,1,T) -> raw MFCC (flag 1) or CMVN features (flag 2); xv_plda.py:51-67."""
         assert flag in (1, 2)
-        x, B, T = self._prep(x, 0)
-        F = N.load().sg_xv_num_frames(T)
-        scale = torch.empty(1, device=self.device, dtype=torch.float32)
-        feats = torch.empty(B, F, 30, device=self.device, dtype=torch.float32)
-        s = self._stream()
-        self.ctx.call("sg_input_scale", N._ptr(x), x.numel(), N._ptr(scale), s)
-        dz = self._dither(dither_noise)
-        self.ctx.call("sg_xv_mfcc", N._ptr(x), B, T, N._ptr(scale), C.byref(dz), N._ptr(feats), s)
+        feats, _ = self._mfcc(x, dither_noise)
         return feats if flag == 1 else self.comput_feat_from_feat(feats, 1, 2)
 
     # ---- front-end stages with their backward (used when a feature-level defense sits between them) ----
     def frontend_forward(self, x, dither_seed=None):
         """wav (B,1,T) -> (raw MFCC (B,F,30), saved) with the state the backward needs (same scale, same dither).
         `dither_seed`: explicit generator key of this pass's dither (tests replay the device loop's per-pass keys)."""
-        x, B, T = self._prep(x, 0)
-        F = N.load().sg_xv_num_frames(T)
-        scale = torch.empty(1, device=self.device, dtype=torch.float32)
-        feats = torch.empty(B, F, 30, device=self.device, dtype=torch.float32)
-        s = self._stream()
-        self.ctx.call("sg_input_scale", N._ptr(x), x.numel(), N._ptr(scale), s)
-        dz = self._dither(None, dither_seed)
-        self.ctx.call("sg_xv_mfcc", N._ptr(x), B, T, N._ptr(scale), C.byref(dz), N._ptr(feats), s)
-        return feats, (x, scale, dz)
+        return self._mfcc(x, dither_seed=dither_seed)
 
     def frontend_backward(self, saved, dfeats):
         """d loss / d raw MFCC (B,F,30) -> d loss / d wav (B,1,T)."""
@@ -251,46 +117,6 @@ class xv_plda(EngineOps):
 
     def cmvn(self, feats):
         return self.comput_feat_from_feat(feats)
-
-    def _forward(self, x, flag, want_emb=False, want_tdnn=False, dither_noise=None, enroll=None, dither_seed=None):
-        x, B, TF = self._prep(x, flag)
-        n_spk = self.num_spks if enroll is None else enroll.shape[0]
-        dec = torch.empty(B, device=self.device, dtype=torch.int64)
-        scores = torch.empty(B, n_spk, device=self.device, dtype=torch.float32)
-        emb = torch.empty(B, self.dim, device=self.device, dtype=torch.float32) if want_emb else None
-        temb = torch.empty(B, 512, device=self.device, dtype=torch.float32) if want_tdnn else None
-        dz = self._dither(dither_noise, dither_seed)
-        if enroll is not None:
-            self.ctx.call("sg_xv_enroll_override", N._ptr(enroll), enroll.shape[0])
-        try:
-            self.ctx.call("sg_xv_forward", N._ptr(x), B, TF, flag, C.byref(dz), N._ptr(dec), N._ptr(scores), N._ptr(emb),
-                          N._ptr(temb), self._stream())
-        finally:
-            if enroll is not None:
-                self.ctx.call("sg_xv_enroll_override", None, 0)
-                enroll.record_stream(torch.cuda.current_stream(self.device))  # the pass may still be reading it
-        return dec, scores, emb, temb
-
-    def embedding(self, x, flag=0):
-        return self._forward(x, flag, want_emb=True)[2]
-
-    def forward(self, x, flag=0, return_emb=False, enroll_embs=None, dither_seed=None):
-        """`dither_seed`: explicit generator key of this pass's dither (a caller that scores an input and then asks
-        ``loss_grad`` for the gradient of the SAME noise realisation passes one key to both: defended_model 'average')."""
-        enroll = self._enroll_for_call(enroll_embs)
-        _, scores, emb, _ = self._forward(x, flag, want_emb=return_emb, enroll=enroll, dither_seed=dither_seed)
-        return (scores, emb) if return_emb else scores
-
-    __call__ = forward
-
-    def score(self, x, flag=0, enroll_embs=None):
-        return self.forward(x, flag=flag, enroll_embs=enroll_embs)
-
-    def make_decision(self, x, flag=0, enroll_embs=None):
-        """-> (decisions int64 (B,), scores (B, n_spk)); iv_plda.py:182-194."""
-        enroll = self._enroll_for_call(enroll_embs)
-        dec, scores, _, _ = self._forward(x, flag, enroll=enroll)
-        return dec, scores
 
     def tdnn_activation(self, layer):
         """ReLU output of TDNN layer 1..5 from the last pass, (B, F_l, C_l) channel-last (parity tests)."""

@@ -657,6 +657,23 @@ int main(int argc, char** argv) {
     EXPECT(sg_sync(ctx, nullptr) == SG_OK);
     sg_destroy(ctx);
     EXPECT(hipdouble_live_allocs() == 0);  // everything the context allocated through the runtime was released
+
+    // ---- the enrol path shared with the i-vector model, from a model loaded with one speaker (CMVN features in: 40 frames)
+    {
+        XvModel one(D, 1);
+        sg_ctx* c1 = nullptr;
+        EXPECT(sg_create(0, &c1) == SG_OK && c1 && sg_xv_load(c1, &one.desc) == SG_OK);
+        if (c1) {
+            hipdouble_set_launch_hook(record_launch);
+            g_on_launch = see_tail;
+            std::vector<float> cm = rnd((size_t)2 * 40 * 30, 210), sc3((size_t)2 * 3);
+            walk_enrol_path(c1, sg_xv_set_enroll, sg_xv_enroll_override, [&] {
+                return sg_xv_forward(c1, cm.data(), 2, 40, SG_FLAG_CMVN, nullptr, dec.data(), sc3.data(), nullptr, nullptr, nullptr);
+            }, D, one.enroll.data(), one.ppsi.data());
+            sg_destroy(c1);
+        }
+        EXPECT(hipdouble_live_allocs() == 0);
+    }
     if (g_fail) {
         std::fprintf(stderr, "%d expectation(s) failed\n", g_fail);
         return 1;

@@ -120,6 +120,74 @@ struct AnModel {
     }
 };
 
+// ---- the enrol path both speaker models share (csrc/plda_backend.hip), walked through one model's public entries.  What a tail
+// kernel was handed is read off its first argument, the model block it takes by value: mirrors of TailModelDev (k_tail.hip)
+// and IvTailDev (k_ivector.hip), the enrolled table being the last pointer of each.
+struct XvTailBlock { const float* p[10]; int D, S, Dp; float threshold, logdet_given, logdet_without; };
+struct IvTailBlock { const float* p[6]; int R, D, S; float threshold, logdet_given, logdet_without; };
+struct TailSeen { const float* enroll = nullptr; int S = 0; float threshold = 0.f, logdet_given = 0.f, logdet_without = 0.f; long launches = 0; };
+static TailSeen g_tail;
+static void see_tail(const Launch& l, void** args) {
+    const std::string k = kernel_name(l.name);
+    if (k == "tail_kernel") {
+        const XvTailBlock& m = *static_cast<const XvTailBlock*>(args[0]);
+        g_tail.enroll = m.p[8]; g_tail.S = m.S; g_tail.threshold = m.threshold;
+        g_tail.logdet_given = m.logdet_given; g_tail.logdet_without = m.logdet_without; ++g_tail.launches;
+    } else if (k == "iv_tail_kernel") {
+        const IvTailBlock& m = *static_cast<const IvTailBlock*>(args[0]);
+        g_tail.enroll = m.p[5]; g_tail.S = m.S; g_tail.threshold = m.threshold;
+        g_tail.logdet_given = m.logdet_given; g_tail.logdet_without = m.logdet_without; ++g_tail.launches;
+    }
+}
+// On a context whose model was just loaded with ONE enrolled speaker (table enroll1, D columns, psi as loaded): `forward` runs one
+// small pass that writes n_scores scores per row for as many speakers as are active (room for 3).  The launch hook must reach see_tail.
+template <typename SetEnroll, typename Override, typename Forward>
+static void walk_enrol_path(sg_ctx* ctx, SetEnroll set_enroll, Override enroll_override, Forward forward, int D, const float* enroll1,
+                            const float* psi) {
+    const auto same_rows = [&](const float* table, int S) { return g_tail.enroll && !std::memcmp(g_tail.enroll, table, (size_t)S * D * 4); };
+    double ldg = 0.0, ldw = 0.0;
+    for (int d = 0; d < D; ++d) {
+        ldg += std::log(1.0 + (double)psi[d] / ((double)psi[d] + 1.0));
+        ldw += std::log((double)psi[d] + 1.0);
+    }
+    const float want_g = (float)ldg, want_w = (float)ldw;
+    const auto pass = [&](const float* table, int S, float thr) {
+        const long before = g_tail.launches;
+        EXPECT(forward() == SG_OK && g_tail.launches == before + 1);
+        EXPECT(g_tail.S == S && same_rows(table, S) && g_tail.threshold == thr);
+        EXPECT(!std::memcmp(&g_tail.logdet_given, &want_g, 4) && !std::memcmp(&g_tail.logdet_without, &want_w, 4));
+    };
+    const std::vector<float> three = rnd((size_t)3 * D, 201), two = rnd((size_t)2 * D, 202), other = rnd((size_t)3 * D, 203);
+    // 1. as loaded: one speaker
+    pass(enroll1, 1, -INFINITY);
+    const long live = hipdouble_live_allocs();
+    // 2. three speakers: a new table, the old one released
+    EXPECT(set_enroll(ctx, three.data(), 3, 0.5f) == SG_OK && hipdouble_live_allocs() == live);
+    pass(three.data(), 3, 0.5f);
+    const float* own = g_tail.enroll;
+    // 3. two speakers: the same buffer
+    EXPECT(set_enroll(ctx, two.data(), 2, 0.25f) == SG_OK && hipdouble_live_allocs() == live);
+    pass(two.data(), 2, 0.25f);
+    EXPECT(g_tail.enroll == own);
+    // 4. the threshold alone
+    EXPECT(set_enroll(ctx, nullptr, 2, 1.5f) == SG_OK && hipdouble_live_allocs() == live);
+    pass(two.data(), 2, 1.5f);
+    EXPECT(g_tail.enroll == own);
+    // 5. refused counts: the text, and nothing changed
+    for (int bad : {0, 1025}) {
+        EXPECT(set_enroll(ctx, three.data(), bad, 9.f) == SG_ERR_ARG && std::string(sg_last_error(ctx)) == "S must be 1..1024");
+        EXPECT(enroll_override(ctx, three.data(), bad) == SG_ERR_ARG && std::string(sg_last_error(ctx)) == "S must be 1..1024");
+    }
+    pass(two.data(), 2, 1.5f);
+    // 6. a per-call override: the caller's table as it is, then the model's own again
+    EXPECT(enroll_override(ctx, other.data(), 3) == SG_OK && hipdouble_live_allocs() == live);
+    pass(other.data(), 3, 1.5f);
+    EXPECT(g_tail.enroll == other.data());
+    EXPECT(enroll_override(ctx, nullptr, 0) == SG_OK);
+    pass(two.data(), 2, 1.5f);
+    EXPECT(g_tail.enroll == own && hipdouble_live_allocs() == live);
+}
+
 // a time-domain stage of a defended loop's chain
 static sg_wav_stage td(int kind, float param, uint64_t seed = 0) {
     sg_wav_stage st{};

@@ -42,6 +42,7 @@ static const uint16_t* g_pairs = nullptr;
 static int g_Cp = 0, g_Pp = 0;
 static void on_launch(const Launch& l, void** args) {
     g_seen.push_back(l);
+    see_tail(l, args);
     const std::string k = kernel_name(l.name);
     if (k == "iv_loglik_kernel") {
         g_W = *static_cast<const float* const*>(args[2]);
@@ -252,6 +253,20 @@ int main() {
 
     sg_destroy(ctx);
     EXPECT(hipdouble_live_allocs() == 0);
+
+    // ---- the enrol path shared with the x-vector model, from a model loaded with one speaker
+    {
+        IvModel one(C, R, D, 1);
+        sg_ctx* c1 = nullptr;
+        EXPECT(sg_create(0, &c1) == SG_OK && c1 && sg_iv_load(c1, &one.desc) == SG_OK);
+        if (c1) {
+            walk_enrol_path(c1, sg_iv_set_enroll, sg_iv_enroll_override, [&] {
+                return sg_iv_forward(c1, feats.data(), 2, F, 3, nullptr, dec.data(), scores.data(), nullptr, nullptr, nullptr);
+            }, D, one.enroll.data(), one.ppsi.data());
+            sg_destroy(c1);
+        }
+        EXPECT(hipdouble_live_allocs() == 0);
+    }
     if (g_fail) return 1;
     std::fprintf(stderr, "iv_asan_driver: ok (%ld kernel launches issued against the host double)\n", hipdouble_launches());
     return 0;

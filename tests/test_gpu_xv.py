@@ -1179,3 +1179,67 @@ def test_backend_dimensions_not_multiples_of_four(dev, D, n_spk):
     np.testing.assert_allclose(got, want, rtol=0, atol=2e-4 * gs)
     log("back-end D=%d, %d speakers: scores max err %.2e of %.1f; d loss / d raw feats max err / max %.2e" % (
         D, n_spk, np.abs(scores.cpu().numpy() - oscores.numpy()).max(), sc, np.abs(got - want).max() / gs))
+
+
+# ---- the PLDA back end at its corner shapes (tests/plda_cases.py): D = 150, S = 1, 27 / 28 (table in LDS or not), 64 / 65 (wave /
+# block form of the loss); one model of 65 speakers, a case enrols the first S
+@pytest.fixture(scope="module")
+def backend_case(dev):
+    import plda_cases as P
+    from speakerguard_amd.model.xv_plda import xv_plda
+    w = P.xv_weights()
+    return w, xv_plda.from_weights(w, device=dev, dither=0.0), torch.from_numpy(P.waveforms()).to(dev)
+
+
+@pytest.mark.parametrize("S", [1, 27, 28, 64, 65])
+def test_backend_corner_shapes_against_float64_scores(backend_case, S):
+    """scores against the float64 log-likelihood ratio of the model's OWN returned embedding under the score rule of
+    tests/truth.py (the yard: the same recomputation in float32), decisions = the float64 arg-max outside the tie margin"""
+    import plda_cases as P
+    w, m, x = backend_case
+    m.set_enroll(w["enroll"][:S])
+    dec, scores, emb, _ = m._forward(x, 0, want_emb=True)
+    emb = emb.cpu().numpy()
+    truth = P.llr(emb, w["enroll"][:S], w["plda_psi"])
+    yard = P.llr(emb, w["enroll"][:S], w["plda_psi"], np.float32).astype(np.float64)
+    err, bound = np.abs(scores.cpu().numpy().astype(np.float64) - truth).max(1), P.xv_score_bound(truth, yard)
+    log("back-end corner D=%d S=%d: score err %s, bound %s, margin %s" % (P.D, S, err, bound, P.top_two_margin(truth)))
+    assert scores.shape == (P.B, S) and np.isfinite(emb).all() and (err <= bound).all(), (err, bound)
+    clear = P.top_two_margin(truth) > bound
+    assert clear.mean() >= 0.9 and (dec.cpu().numpy()[clear] == truth.argmax(1)[clear]).all()
+
+
+@pytest.mark.parametrize("S", [1, 27, 28, 64, 65])
+def test_backend_corner_shapes_override_and_reenrol_bit_for_bit(backend_case, S):
+    """test_enroll_embs_argument_is_a_per_call_override at every corner count: a permuted subset through ``enroll_embs=`` gives
+    the matching columns of the full-table scores, and a smaller table enrolled and the full one enrolled again the first ones"""
+    import plda_cases as P
+    w, m, x = backend_case
+    full = w["enroll"][:S]
+    m.set_enroll(full)
+    sc0 = m.score(x)
+    idx = P.subset(S)
+    sub = m.score(x, enroll_embs=torch.from_numpy(full[idx].copy()).to(x.device))
+    assert sub.shape == (P.B, len(idx)) and torch.equal(sub, sc0[:, torch.from_numpy(idx).to(x.device)])
+    assert m.num_spks == S and torch.equal(m.score(x), sc0)
+    m.set_enroll(full[:max(1, S // 2)])
+    assert m.score(x).shape == (P.B, max(1, S // 2))
+    m.set_enroll(full)
+    assert torch.equal(m.score(x), sc0)
+
+
+@pytest.mark.parametrize("S", [1, 65])
+@pytest.mark.parametrize("loss_name", ["Entropy", "Margin"])
+def test_backend_corner_shapes_gradient_is_row_invariant(backend_case, loss_name, S):
+    """loss_grad from the waveform: finite, and three rows in one call bit-equal to the same rows one at a time"""
+    import plda_cases as P
+    from speakerguard_amd.attack.utils import resolve_loss
+    w, m, x = backend_case
+    m.set_enroll(w["enroll"][:S])
+    spec, _ = resolve_loss(loss_name, targeted=False, task='CSI', threshold=None, clip_max=False)
+    y = (torch.arange(P.B) % S).to(x.device)
+    dec, sc, loss, grad = m.loss_grad(x, y, spec, flag=0)
+    assert torch.isfinite(grad).all() and torch.isfinite(loss).all() and grad.shape == x.shape
+    for i in range(P.B):
+        d1, s1, l1, g1 = m.loss_grad(x[i:i + 1], y[i:i + 1], spec, flag=0)
+        assert torch.equal(g1, grad[i:i + 1]) and torch.equal(s1, sc[i:i + 1]) and torch.equal(l1, loss[i:i + 1]) and torch.equal(d1, dec[i:i + 1])
