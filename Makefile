@@ -40,7 +40,8 @@ ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefi
               -fno-omit-frame-pointer -Iinclude -Wall -Wno-unused-function
 ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 DRIVERS    := abi_asan_driver defended_asan_driver an_defended_asan_driver xv_feco_asan_driver feco_cos_asan_driver \
-              ds_asan_driver spectrum_asan_driver ssa_asan_driver stoi_asan_driver pso_asan_driver iv_asan_driver iv_grad_asan_driver
+              ds_asan_driver spectrum_asan_driver ssa_asan_driver stoi_asan_driver pso_asan_driver iv_asan_driver iv_grad_asan_driver \
+              feco_wide_asan_driver
 ASAN_EXES  := $(addprefix $(ASAN_DIR)/,$(DRIVERS))
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(HDRS)

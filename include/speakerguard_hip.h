@@ -180,6 +180,8 @@ int sg_xv_cmvn(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, float*
  * iv_plda.py:296-377): needed when something sits BETWEEN the stages, i.e. a feature-level defense
  * (model/defended_model.py:46-65 process_sequential with a flag-1 or flag-2 defense).
  * sg_xv_mfcc_backward: d loss/d raw MFCC (B,F,30) -> d loss/d waveform (B,T); same scale / dither as the forward.
+ *   It needs a loaded model for its frame scratch: the x-vector model's workspace or, on a context that holds an i-vector
+ *   model only (whose 24 cepstra are the first of the 30; the caller zero-pads), the i-vector workspace's.
  * sg_xv_cmvn_backward: d loss/d CMVN features -> d loss/d raw features, (B,F,30) both. */
 int sg_xv_mfcc_backward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, const float* scale_dev,
                         const sg_dither* dither, const float* dfeats_dev, float* grad_dev, void* stream);
@@ -574,6 +576,22 @@ int sg_feco_kmeans_compress_metric(sg_ctx* ctx, const float* feats_dev, int32_t 
                                    int32_t max_iter, int32_t metric, int32_t random_init, uint64_t seed, int64_t index_base,
                                    int32_t reps, int32_t row_wise, int32_t* assign_dev, float* out_dev, int32_t* counts_dev,
                                    void* stream);
+/* sg_feco_kmeans_compress for WIDE frames, 65 <= D <= 128 (iv_plda's delta and CMVN features, 72 columns): the entries above
+ * keep refusing D > 64.  Arguments as sg_feco_kmeans_compress without `reps` (one launch per EOT repeat is the caller's):
+ * assign (B,F), out (B,k,D), counts (B,k); out / counts equal sg_feco_compress of the returned ids bit for bit, and
+ * sg_feco_compress / sg_feco_compress_backward(_reps), which have no width cap, serve the wide form unchanged.
+ * Determinism contract "version 2, wide" (k_feco_wide.hip header): version 2 with the padded width 128 -- same centring, same
+ * initial frames (even, or seeded with the Philox keys of sg_feco_kmeans_seeded), same stop rule, update and tie rule, the
+ * ids of the last assignment step; n_j = the butterfly s[d] += s[d ^ 1], s[d ^ 2], ... s[d ^ 64] over 128 zero-padded lanes of
+ * the rounded squares, h_j = -0.5f * n_j, score(i, j) = ONE fp32 fmaf chain from h_j over the dimensions in the contraction
+ * order (groups of 8 ascending, inside a group 0, 4, 1, 5, 2, 6, 3, 7), padded with zeros to 128.
+ * One 512-thread block per utterance; the frames stay in global memory, the centroid rows ((k + 31) & ~31 rows of
+ * 8 ceil(D / 8) + 4 floats) and the lists must fit 150 KB of LDS: D = 72 at ratio 0.5 runs up to F = 833.
+ * SG_ERR_ARG before any launch: a NULL pointer, B <= 0, D outside 65 .. 128, k outside 1 .. F, max_iter <= 0, a shape past the
+ * LDS budget ("utterance too long for one block"). */
+int sg_feco_kmeans_compress_wide(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
+                                 int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base,
+                                 int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream);
 
 /* FeCo with warped k-means (defense/feature_level.py:53-165 warped_kmeans / wk_compute): the F frames of each row cut into
  * k contiguous segments, the boundaries moved frame by frame while the squared error falls, out (B,k,D) = the final

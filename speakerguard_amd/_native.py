@@ -35,6 +35,7 @@ EXPORTS = (
     "sg_iv_load", "sg_iv_set_enroll", "sg_iv_enroll_override", "sg_iv_delta_cmvn", "sg_iv_stats", "sg_iv_extract",
     "sg_iv_forward", "sg_iv_loss",
     "sg_iv_loss_grad", "sg_iv_extract_backward", "sg_iv_stats_backward", "sg_iv_delta_cmvn_backward",
+    "sg_feco_kmeans_compress_wide",
 )
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
@@ -228,6 +229,7 @@ def load():
                                                      vp]),
         "sg_xv_pgd_run_feco": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(FecoParams), i32, vp, vp, vp,
                                          vp, vp, vp, vp]),
+        "sg_feco_kmeans_compress_wide": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_int64, vp, vp, vp, vp]),
         "sg_feco_compress": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "sg_feco_compress_backward": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         "sg_wav_defense_forward": (C.c_int, [vp, C.POINTER(WavDefense), vp, i32, i32, vp, vp, vp]),

@@ -1078,6 +1078,20 @@ int sg_xv_cmvn(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, float*
 int sg_xv_mfcc_backward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T, const float* scale_dev,
                         const sg_dither* dither, const float* dfeats_dev, float* grad_dev, void* stream) {
     if (!x_dev || !dfeats_dev || !grad_dev) return fail(ctx, SG_ERR_ARG, "bad argument");
+    if (ctx && !ctx->xv.loaded && ctx->iv.loaded) {
+        // The i-vector model shares this front end (its 24 cepstra are the first of the 30) and has no x-vector workspace: the
+        // adjoint runs on the i-vector workspace's frame buffer, as in sg_iv_loss_grad at flag 0 (iv_plda.frontend_backward).
+        if (B < 1 || T < kWin) return fail(ctx, SG_ERR_ARG, "bad argument");
+        if (int h = sg_health(ctx)) return h;
+        SG_HIP(hipSetDevice(ctx->device));
+        int rc = build_tables(ctx);
+        if (rc) return rc;
+        const int F = num_frames(T);
+        IvWorkspace& w = ctx->iv_ws;
+        if ((rc = dev_grow(ctx, w.allocs, &w.dframes, (size_t)B * F * kWin, (hipStream_t)stream))) return rc;
+        return mfcc_adjoint(ctx, ctx->tab, x_dev, B, T, F, scale_dev, dither, dfeats_dev, w.dframes, 1, nullptr, grad_dev, nullptr, nullptr,
+                            nullptr, 0.f, 1, false, (hipStream_t)stream);
+    }
     PassDims d;
     int rc = check_dims(ctx, B, T, SG_FLAG_WAV, &d);  // sizes the per-frame gradient scratch
     if (rc) return rc;

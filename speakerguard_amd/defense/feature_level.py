@@ -31,6 +31,8 @@ from .. import _native as N
 from ..metric.metric import _context
 from ..model._engine_ops import REP_KEY_STRIDE
 
+WIDE_MIN_D = 65  # from this width on the L2 clustering is sg_feco_kmeans_compress_wide (csrc/k_feco_wide.hip; up to 128)
+
 
 class FeCoDefense:
     # the reference's `force` flag follows the size of the MODEL CALL (feature_level.py:33: feat.shape[0] > 1): a call with
@@ -98,6 +100,10 @@ class FeCoDefense:
                     ctx.call("sg_feco_kmeans_compress_metric", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, N.SG_FECO_COS,
                              int(self.init == 'random'), C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF),
                              int(index_base + u), 1, 0, N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
+                elif D >= WIDE_MIN_D:  # 65 .. 128 columns (iv_plda's levels 2 and 3): the wide kernel, same keys
+                    ctx.call("sg_feco_kmeans_compress_wide", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, int(self.init == 'random'),
+                             C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF), int(index_base + u),
+                             N._ptr(ids[sl]), N._ptr(out[sl]), N._ptr(counts[sl]), s)
                 else:
                     ctx.call("sg_feco_kmeans_compress", N._ptr(feat[sl]), nb, F, D, k, self.max_iter, int(self.init == 'random'),
                              C.c_uint64((key + rep * REP_KEY_STRIDE) & 0xFFFFFFFFFFFFFFFF), int(index_base + u), 1,

@@ -147,14 +147,17 @@ class defended_model:
                                       'adaptive_attack.BPDA.BPDA(f, sub_f) around any input-level transform)')
         n = len(self.defense)  # :75 divides by len(self.defense)
         x = x.to(bm.device, torch.float32).contiguous()
-        feats = saved_front = cm = None
-        if any(f >= 1 for f, _ in branches):
-            feats, saved_front = bm.frontend_forward(x)  # one front-end pass serves every feature-level branch
-        if any(f == 2 for f, _ in branches):
-            cm = bm.comput_feat_from_feat(feats, ori_flag=1, des_flag=2)
+        # one front-end pass serves every feature-level branch; the levels above 1 are the base model's own steps
+        # (comput_feat_from_feat), up to the highest level that holds a branch
+        level_feats, saved_front = {}, None
+        top = max(f for f, _ in branches)
+        if top >= 1:
+            level_feats[1], saved_front = bm.frontend_forward(x)
+            for f in range(2, top + 1):
+                level_feats[f] = bm.comput_feat_from_feat(level_feats[f - 1], ori_flag=f - 1, des_flag=f)
         tape, mean = [], None
         for flag, d in branches:
-            out, sv = self._fwd(d, x if flag == 0 else (feats if flag == 1 else cm))
+            out, sv = self._fwd(d, x if flag == 0 else level_feats[flag])
             # a waveform-level branch runs the (dithered) front-end inside the model: ONE noise realisation serves its
             # scores here and its gradient below, like the single autograd graph of the reference (EOT.py:32-35)
             key = bm.next_dither_seed() if flag == 0 and hasattr(bm, 'next_dither_seed') else None
@@ -172,8 +175,8 @@ class defended_model:
             if flag == 0:
                 grad = gi if grad is None else grad + gi
             else:
-                if flag == 2:
-                    gi = bm.cmvn_backward(gi)
+                for f in range(flag, 1, -1):  # down to the raw features, one level at a time
+                    gi = bm.feat_from_feat_backward(gi, f - 1, f)
                 dfeat = gi if dfeat is None else dfeat + gi  # the front-end is linear in its cotangent: one adjoint below
         if dfeat is not None:
             gw = bm.frontend_backward(saved_front, dfeat)
@@ -181,13 +184,14 @@ class defended_model:
         return decisions, mean, loss, grad
 
     def _loss_grad_through_defenses(self, x, y, loss_spec):
-        """wav -> MFCC -> [flag-1 defenses] -> CMVN -> [flag-2 defenses] -> TDNN ... -> loss, and back.
+        """wav -> [flag-0 defenses] -> front-end -> [flag-1 defenses] -> next level -> [its defenses] ... -> loss, and back.
 
         The order is process_sequential's (:52-63).  Each stage's backward is the native one: the model's own
         loss_grad from the last defended level, the defenses' ``bwd``, CMVN / MFCC backward in between."""
         bm = self.base_model
+        levels = sorted(self.flag2defense.keys())
         chainable = (self.order == sequential and hasattr(bm, 'frontend_forward')
-                     and all(hasattr(d, 'fwd') and hasattr(d, 'bwd') for f in (0, 1, 2) for d in self.flag2defense.get(f, [])))
+                     and all(hasattr(d, 'fwd') and hasattr(d, 'bwd') for f in levels for d in self.flag2defense[f]))
         if not chainable:
             raise NotImplementedError('gradient through this defense configuration is not built: needs a native base '
                                       'model, sequential order, and defenses exposing fwd/bwd (FeCoDefense at the feature '
@@ -197,34 +201,42 @@ class defended_model:
         for d in self.flag2defense.get(0, []):
             x, sv = self._fwd(d, x)
             tape0.append((d, sv))
-        if not self.flag2defense.get(1) and not self.flag2defense.get(2):
+        defended = [f for f in levels if f >= 1 and self.flag2defense[f]]
+        if not defended:
             # nothing sits between front-end and network: one native call from the (defended) waveform
             decisions, scores, loss, g = bm.loss_grad(x, y, loss_spec, flag=0, want_grad=True)
             for d, sv in reversed(tape0):
                 g = d.bwd(sv, g)
             return decisions, scores, loss, g
+        # The base model's own levels, walked up to the last defended one (xv_plda: 1 raw, 2 CMVN; iv_plda: 1 raw, 2 delta,
+        # 3 CMVN; AudioNet: 1 only): forward with comput_feat_from_feat, the model's loss_grad from that level, back with
+        # feat_from_feat_backward (xv_plda: its cmvn_backward), the defenses of a level in reverse order in between.
         feats, saved_front = bm.frontend_forward(x)
-        tape1, tape2 = [], []
-        for d in self.flag2defense[1]:
-            feats, sv = self._fwd(d, feats)
-            tape1.append((d, sv))
-        if self.flag2defense.get(2):  # xv_plda only (AudioNet has no level 2, audionet_csine.py:127-129)
-            feats = bm.comput_feat_from_feat(feats, ori_flag=1, des_flag=2)
-            for d in self.flag2defense[2]:
-                feats, sv = self._fwd(d, feats)
-                tape2.append((d, sv))
-            decisions, scores, loss, g = bm.loss_grad(feats, y, loss_spec, flag=2, want_grad=True)
-            for d, sv in reversed(tape2):
-                g = d.bwd(sv, g)
-            g = bm.cmvn_backward(g)
-        else:
-            decisions, scores, loss, g = bm.loss_grad(feats, y, loss_spec, flag=1, want_grad=True)
-        for d, sv in reversed(tape1):
-            g = d.bwd(sv, g)
+        decisions, scores, loss, g, _ = self._loss_grad_from_level1(feats, y, loss_spec, defended[-1])
         g = bm.frontend_backward(saved_front, g)
         for d, sv in reversed(tape0):
             g = d.bwd(sv, g)
         return decisions, scores, loss, g
+
+    def _loss_grad_from_level1(self, feats, y, loss_spec, last):
+        """The feature levels of the sequential route: level-1 features -> (decisions, scores, loss, d loss / d level-1
+        features, tapes), tapes[f] = [(defense, saved), ...] of level f in forward order (tests read the cluster ids there)."""
+        bm = self.base_model
+        tapes = {}
+        for f in range(1, last + 1):
+            if f > 1:
+                feats = bm.comput_feat_from_feat(feats, ori_flag=f - 1, des_flag=f)
+            tapes[f] = []
+            for d in self.flag2defense.get(f, []):
+                feats, sv = self._fwd(d, feats)
+                tapes[f].append((d, sv))
+        decisions, scores, loss, g = bm.loss_grad(feats, y, loss_spec, flag=last, want_grad=True)
+        for f in range(last, 0, -1):
+            for d, sv in reversed(tapes[f]):
+                g = d.bwd(sv, g)
+            if f > 1:
+                g = bm.feat_from_feat_backward(g, f - 1, f)
+        return decisions, scores, loss, g, tapes
 
     def pgd_update(self, *a, **k):
         return self.base_model.pgd_update(*a, **k)

@@ -208,6 +208,42 @@ class iv_plda(PldaModel):
             parts.append(cm[:, :, :IV_CEPS])
         return torch.cat(parts, 2).contiguous()
 
+    # ---- front-end stages with their backward (used when a feature-level defense sits between them: defended_model) ----
+    def frontend_forward(self, x, dither_seed=None):
+        """wav (B,1,T) -> (raw features (B,F,24), saved) with the state the backward needs (same scale, same dither).
+        `dither_seed`: explicit generator key of this pass's dither."""
+        feats, saved = self._mfcc(x, dither_seed=dither_seed)
+        return feats[:, :, :IV_CEPS].contiguous(), saved
+
+    def frontend_backward(self, saved, d_raw):
+        """d loss / d raw features (B,F,24) -> d loss / d wav (B,1,T): the 24 columns padded into the 30 of the x-vector
+        front-end's MFCC adjoint (columns 24 .. 29 do not reach this model), with the forward's scale and dither key."""
+        if not getattr(self, "_white_box", False):
+            raise NotImplementedError(_NO_GRAD % "frontend_backward")
+        x, scale, dz = saved
+        B, T = x.shape[0], x.shape[2]
+        d_raw, _, F = self._prep(d_raw, 1)
+        d30 = torch.zeros(B, F, 30, device=self.device, dtype=torch.float32)
+        d30[:, :, :IV_CEPS] = d_raw
+        grad = torch.empty_like(x)
+        self.ctx.call("sg_xv_mfcc_backward", N._ptr(x), B, T, N._ptr(scale), C.byref(dz), N._ptr(d30), N._ptr(grad), self._stream())
+        return grad
+
+    def feat_from_feat_backward(self, dout, ori_flag, des_flag):
+        """The adjoint of ``comput_feat_from_feat(., ori_flag, des_flag)`` for one level: d CMVN -> d delta (2, 3), both
+        (B,F,72), or d delta -> d raw (B,F,24) (1, 2); sg_iv_delta_cmvn_backward."""
+        if not getattr(self, "_white_box", False):
+            raise NotImplementedError(_NO_GRAD % "feat_from_feat_backward")
+        assert (ori_flag, des_flag) in ((1, 2), (2, 3))
+        dout, B, F = self._prep(dout, des_flag)
+        if des_flag == 3:
+            din = torch.empty(B, F, IV_DIM, device=self.device, dtype=torch.float32)
+            self.ctx.call("sg_iv_delta_cmvn_backward", N._ptr(dout), 3, B, F, N._ptr(din), None, self._stream())
+        else:
+            din = torch.empty(B, F, IV_CEPS, device=self.device, dtype=torch.float32)
+            self.ctx.call("sg_iv_delta_cmvn_backward", N._ptr(dout), 2, B, F, None, N._ptr(din), self._stream())
+        return din
+
     def add_delta(self, feats):
         return self.comput_feat_from_feat(feats, 1, 2)
 

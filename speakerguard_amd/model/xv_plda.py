@@ -107,6 +107,12 @@ class xv_plda(PldaModel):
         self.ctx.call("sg_xv_cmvn_backward", N._ptr(dout), B, F, N._ptr(din), self._stream())
         return din
 
+    def feat_from_feat_backward(self, dout, ori_flag, des_flag):
+        """The adjoint of ``comput_feat_from_feat(., ori_flag, des_flag)``: what ``defended_model`` walks back through, level
+        by level, on every base model.  This model has one such step, the CMVN."""
+        assert ori_flag == 1 and des_flag == 2
+        return self.cmvn_backward(dout)
+
     def comput_feat_from_feat(self, feats, ori_flag=1, des_flag=2):
         """raw -> CMVN (sic, name as at xv_plda.py:70)."""
         assert ori_flag == 1 and des_flag == 2
