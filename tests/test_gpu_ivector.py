@@ -1,14 +1,18 @@
 """GMM / i-vector / PLDA system on the GPU (speakerguard_amd.model.iv_plda, csrc/k_ivector.hip): every stage against float64
 truth under the reference's own error, decisions, the wav flag, invariance under batching and chunking, the decision-only
 attacks, enrolment and sharding.  Shapes: the fixtures' (tests/golden/make_golden_ivector.py) -- models A = (C 16, R 24) and
-B = (C 80, R 100: tile and panel remainders), F in {2, 13, 100, 331} frames, 5 / 5 / 3 / 1 utterances."""
+B = (C 80, R 100: tile remainders), F in {2, 13, 100, 331} frames, 5 / 5 / 3 / 1 utterances; model C = (C 272, R 262), F 13 and
+100 with 3 and 2 utterances: the smallest sizes at which every 256-wide loop and grid dimension of csrc/k_ivector.hip takes a
+second, partial pass (a second loglik column block with a quarter-filled wave, a second ``cb`` pass of 16 components, 17 lin
+slices, a second stride of 6 live threads in the solve and the tail, a last Cholesky panel of 2 columns), and calls of 19 and 33
+rows of it for the second and third group of 16 utterances of the assembly kernels."""
 import numpy as np
 import pytest
 import torch
 
 import iv_restate as R
 from conftest import load_golden, log
-from test_ivector_cpu import CASES, MODELS, checksum
+from test_ivector_cpu import CASES, CASES_OF, FILES, MODEL_CASE_IDS, MODEL_CASES, MODELS, checksum
 
 pytestmark = pytest.mark.gpu
 FLOOR = 2.0 ** -20
@@ -26,12 +30,27 @@ def sys_(dev):
     from speakerguard_amd import synth
     from speakerguard_amd.model.iv_plda import iv_plda
     out = {}
-    for tag, name in (("a", "iv_ref.npz"), ("b", "iv_ref_b.npz")):
+    for tag, name in FILES.items():
         g = load_golden(name)
         w = synth.make_iv_weights(**MODELS[tag])
         assert checksum(w) == g["meta"][tag]["weights_sha256"]
         out[tag] = (w, g, R.IvRestated(w), iv_plda.from_weights(w, device=dev, dither=0.0))
     return out
+
+
+_TRUTH = {}
+
+
+def truth_chain(sys_, tag, F):
+    """float64 truth of a fixture's case, computed once per module and left unchanged (model C: seconds of numpy work)"""
+    if (tag, F) not in _TRUTH:
+        _, g, truth, _ = sys_[tag]
+        t = truth.chain(g["x_%d" % F])
+        t["extract_alone"] = np.stack([truth.extract(a, b) for a, b in zip(g["zeroth_%d" % F], g["first_%d" % F])])
+        for v in t.values():
+            v.setflags(write=False)
+        _TRUTH[tag, F] = t
+    return _TRUTH[tag, F]
 
 
 def err(a, truth):
@@ -68,14 +87,13 @@ def test_delta_and_cmvn_against_truth(sys_, dev, F, B):
     assert torch.equal(out, delta)
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F,B", CASES)
+@pytest.mark.parametrize("F,B,tag", MODEL_CASES, ids=MODEL_CASE_IDS)
 def test_stages_against_truth(sys_, dev, tag, F, B):
     """statistics, i-vector, embedding, scores: each stage fed the TRUTH's inputs of that stage where it has an entry of its
     own (statistics from the fixture's frames, the i-vector from float32-rounded true statistics), then the whole chain"""
     w, g, truth, m = sys_[tag]
     x = g["x_%d" % F]
-    t = truth.chain(x)
+    t = truth_chain(sys_, tag, F)
     xd = torch.from_numpy(x).to(dev)
     n, f = m.stats(xd)
     assert np.isfinite(n.cpu().numpy()).all()  # the x30 frame: a finite softmax
@@ -84,7 +102,7 @@ def test_stages_against_truth(sys_, dev, tag, F, B):
     np.testing.assert_allclose(n.sum(1).cpu().numpy(), F, rtol=1e-5)
     # the extractor alone: both sides from the same float32 statistics (the reference's recorded ones)
     n_ref, f_ref = g["zeroth_%d" % F], g["first_%d" % F]
-    iv_t = np.stack([truth.extract(a, b) for a, b in zip(n_ref, f_ref)])
+    iv_t = t["extract_alone"]
     iv = m.extract(torch.from_numpy(n_ref).to(dev), torch.from_numpy(f_ref).to(dev))
     judge("%s extract alone F=%d" % (tag, F), iv.cpu().numpy(), g["ivector_%d" % F], iv_t)
     # the chain from the frames
@@ -95,17 +113,17 @@ def test_stages_against_truth(sys_, dev, tag, F, B):
     assert dec.cpu().tolist() == g["decisions_%d" % F].tolist()
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("tag", ["a", "b", "c"])
 def test_all_decisions_equal_the_reference(sys_, dev, tag):
     _, g, _, m = sys_[tag]
     raws = sys_["a"][1]
-    for F, B in CASES:
+    for F, B in CASES_OF[tag]:
         for nb in sorted({1, min(3, B), B}):
             dec, _ = m.make_decision(torch.from_numpy(g["x_%d" % F][:nb]).to(dev), flag=3)
             assert dec.cpu().tolist() == g["decisions_%d" % F][:nb].tolist(), (F, nb)
             dec, sc = m.make_decision(torch.from_numpy(raws["raw_%d" % F][:nb]).to(dev), flag=1)
             assert dec.cpu().tolist() == g["raw_decisions_%d" % F][:nb].tolist(), (F, nb)
-        dec2, _ = m.make_decision(torch.from_numpy(raws["delta_%d" % F]).to(dev), flag=2)
+        dec2, _ = m.make_decision(torch.from_numpy(raws["delta_%d" % F][:B]).to(dev), flag=2)
         assert dec2.cpu().tolist() == g["raw_decisions_%d" % F].tolist()
 
 
@@ -143,6 +161,51 @@ def test_invariance_under_batching(sys_, dev):
         n, f = m.stats(x)
         n1, f1 = m.stats(x[3:4])
         assert torch.equal(n[3:4], n1) and torch.equal(f[3:4], f1)
+
+
+def group_rows(w, g, B0=16):
+    """a call of model C whose last rows are the fixture's three utterances of 13 frames, behind B0 rows of other frames"""
+    from speakerguard_amd import synth
+    return np.concatenate([synth.make_iv_frames(w, B0, 13, seed=77), g["x_13"]])
+
+
+def test_second_utterance_group_against_truth(sys_, dev):
+    """19 rows of model C, flag 3: the assembly kernels' second group of 16 utterances (blockIdx.y / z = 1, nb = 3) holds the
+    fixture's utterances -- judged against truth under the rule, and bit-equal to the 3-row call; then sg_iv_extract alone"""
+    w, g, _, m = sys_["c"]
+    t = truth_chain(sys_, "c", 13)
+    x19 = torch.from_numpy(group_rows(w, g)).to(dev)
+    assert x19.shape == (19, 13, 72)
+    full = m._forward(x19, 3, want_emb=True, want_ivector=True)
+    three = m._forward(x19[16:], 3, want_emb=True, want_ivector=True)
+    dec, scores, emb, ivec = full
+    judge("c 19 rows ivector F=13", ivec[16:].cpu().numpy(), g["ivector_13"], t["ivector"])
+    judge("c 19 rows emb F=13", emb[16:].cpu().numpy(), g["emb_13"], t["emb"])
+    judge("c 19 rows scores F=13", scores[16:].cpu().numpy(), g["scores_13"], t["scores"])
+    assert dec[16:].cpu().tolist() == g["decisions_13"].tolist()
+    for a, b in zip(full, three):
+        assert torch.equal(a[16:], b)
+    # the extractor's entry with B = 19: rows 16 .. 18 are the reference's recorded statistics
+    n16, f16 = m.stats(x19[:16])
+    n = torch.cat([n16, torch.from_numpy(g["zeroth_13"]).to(dev)]).contiguous()
+    f = torch.cat([f16, torch.from_numpy(g["first_13"]).to(dev)]).contiguous()
+    iv = m.extract(n, f)
+    assert iv.shape == (19, MODELS["c"]["R"])
+    judge("c 19 rows extract alone F=13", iv[16:].cpu().numpy(), g["ivector_13"], t["extract_alone"])
+    assert torch.equal(iv[16:], m.extract(n[16:].contiguous(), f[16:].contiguous()))
+    assert torch.equal(iv[:16], m.extract(n[:16].contiguous(), f[:16].contiguous()))
+
+
+def test_a_33_row_call_equals_its_rows(sys_, dev):
+    """model C, groups of 16, 16 and 1 utterances: the first and last row of every group equal the same row sent alone"""
+    w, g, _, m = sys_["c"]
+    x = torch.from_numpy(group_rows(w, g, 30)).to(dev)
+    assert x.shape[0] == 33
+    full = m._forward(x, 3, want_emb=True, want_ivector=True)
+    for i in (0, 15, 16, 31, 32):
+        one = m._forward(x[i:i + 1], 3, want_emb=True, want_ivector=True)
+        for a, b in zip(full, one):
+            assert torch.equal(a[i:i + 1], b), i
 
 
 def test_a_1001_row_call_equals_its_chunks(sys_, dev):

@@ -1,8 +1,11 @@
 """The i-vector gradient on the GPU (iv_plda(white_box=True), csrc/k_ivector_bwd.hip): the backward's stage entries and the
 whole chain against float64 truth (tests/iv_restate_grad.py) under the reference's own error, the saturated rows, the wav flag,
 invariance under batching and chunking, the forward outputs, and the white-box attacks.  Shapes: the fixtures'
-(tests/golden/make_golden_ivector.py, make_golden_ivector_grad.py) -- models A = (C 16, R 24) and B = (C 80, R 100: tile and
-panel remainders), F in {2, 13, 100, 331} frames, 5 / 5 / 3 / 1 utterances."""
+(tests/golden/make_golden_ivector.py, make_golden_ivector_grad.py) -- models A = (C 16, R 24) and B = (C 80, R 100: tile
+remainders), F in {2, 13, 100, 331} frames, 5 / 5 / 3 / 1 utterances; model C = (C 272, R 262), F 13 and 100 with 3 and 2
+utterances: a second 256-component span in iv_dgamma / iv_dll / iv_dx_post and a second float64 flush in iv_dx_quad, a second
+stride in iv_solve_bwd and the tail's adjoint, five d n slices (the last one partial) for iv_slice_sum, and calls of 19 and 33
+rows for the second and third group of 16 utterances of iv_rowdot."""
 import functools
 
 import numpy as np
@@ -11,7 +14,7 @@ import torch
 
 import iv_restate_grad as G
 from conftest import load_golden, log
-from test_ivector_cpu import CASES, MODELS, checksum
+from test_ivector_cpu import FILES, GRAD_FILES, MODEL_CASE_IDS, MODEL_CASES, MODELS, checksum
 
 pytestmark = pytest.mark.gpu
 FLOOR = 2.0 ** -20
@@ -28,8 +31,8 @@ class Sys:
         from speakerguard_amd import synth
         from speakerguard_amd.model.iv_plda import iv_plda
         self.tag = tag
-        self.g = load_golden("iv_ref.npz" if tag == "a" else "iv_ref_b.npz")
-        self.gf = load_golden("iv_grad_ref.npz" if tag == "a" else "iv_grad_ref_b.npz")
+        self.g = load_golden(FILES[tag])
+        self.gf = load_golden(GRAD_FILES[tag])
         self.w = synth.make_iv_weights(**MODELS[tag])
         assert checksum(self.w) == self.g["meta"][tag]["weights_sha256"] == self.gf["meta"]["weights_sha256"]
         self.truth = G.IvGrad(self.w)
@@ -40,14 +43,30 @@ class Sys:
     @functools.lru_cache(maxsize=None)
     def truth_grad(self, F, flag, loss):
         """float64 (loss, grad) of the fixture's case, computed once"""
-        x = self.g["x_%d" % F] if flag == 3 else self.raws["raw_%d" % F]
-        ls, g, _ = self.truth.loss_and_grad(x, self.gf["y_%s_f%d_%d" % (loss, flag, F)], "margin" if loss == "margin" else "ce", flag)
+        ls, g, _ = self.truth.loss_and_grad(self.x(F, flag), self.gf["y_%s_f%d_%d" % (loss, flag, F)],
+                                            "margin" if loss == "margin" else "ce", flag)
         return ls, g
+
+    def x(self, F, flag):
+        """the fixture's input of `flag`: its own frames, or the first rows of the shared raw inputs"""
+        return self.g["x_%d" % F] if flag == 3 else self.raws["raw_%d" % F][:len(self.g["x_%d" % F])]
+
+    @functools.lru_cache(maxsize=None)
+    def solve_case(self, F):
+        """the solve entry's case, computed once: float32-rounded true statistics, a random d w, the float64 and the float32
+        adjoint -> (n32, f32, dw, want, ref); want and ref: lists of (d n, d f) per utterance"""
+        t = self.truth.np.chain(self.g["x_%d" % F])
+        n32, f32 = t["zeroth"].astype(np.float32), t["first"].astype(np.float32)
+        B = n32.shape[0]
+        dw = np.random.RandomState(100 + F).randn(B, MODELS[self.tag]["R"]).astype(np.float32)
+        want = [self.adj.solve(n32[b], f32[b], dw[b]) for b in range(B)]
+        ref = [self.adj32.solve(n32[b], f32[b], dw[b]) for b in range(B)]
+        return n32, f32, dw, want, ref
 
 
 @pytest.fixture(scope="module")
 def sys_(dev):
-    return {tag: Sys(tag, dev) for tag in ("a", "b")}
+    return {tag: Sys(tag, dev) for tag in ("a", "b", "c")}
 
 
 def spec_of(loss):
@@ -75,8 +94,7 @@ def dv(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F,B", CASES)
+@pytest.mark.parametrize("F,B,tag", MODEL_CASES, ids=MODEL_CASE_IDS)
 def test_stage_entries_against_truth(sys_, dev, tag, F, B):
     """each backward stage fed float32-rounded truth inputs and a random float32 output gradient; err_ref is the float32 run of
     the hand-written numpy adjoint (the fixture holds the reference's gradient at the chain's ends only)"""
@@ -85,12 +103,9 @@ def test_stage_entries_against_truth(sys_, dev, tag, F, B):
     m, C, Rk = s.m, MODELS[tag]["C"], MODELS[tag]["R"]
     rs = np.random.RandomState(100 + F)
     x = s.g["x_%d" % F]
-    t = s.truth.np.chain(x)
-    n32, f32 = t["zeroth"].astype(np.float32), t["first"].astype(np.float32)
     # the solve and the assembly
-    dw = rs.randn(B, Rk).astype(np.float32)
-    want = [s.adj.solve(n32[b], f32[b], dw[b]) for b in range(B)]
-    ref = [s.adj32.solve(n32[b], f32[b], dw[b]) for b in range(B)]
+    n32, f32, dw, want, ref = s.solve_case(F)
+    assert np.array_equal(dw, rs.randn(B, Rk).astype(np.float32))  # (the generator moves on: the draws below stay where they were)
     dn, df = torch.empty(B, C, device=dev), torch.empty(B, C, 72, device=dev)
     n_d, f_d, dw_d = dv(n32, dev), dv(f32, dev), dv(dw, dev)  # (named: a temporary's memory is reused by the next one)
     m.ctx.call("sg_iv_extract_backward", N._ptr(n_d), N._ptr(f_d), N._ptr(dw_d), B, N._ptr(dn), N._ptr(df), m._stream())
@@ -104,7 +119,7 @@ def test_stage_entries_against_truth(sys_, dev, tag, F, B):
     x_d, dn_d, df_d = dv(x, dev), dv(dn_in, dev), dv(df_in, dev)
     m.ctx.call("sg_iv_stats_backward", N._ptr(x_d), B, F, N._ptr(dn_d), N._ptr(df_d), N._ptr(dx), m._stream())
     judge("%s stats_bwd F=%d" % (tag, F), dx.cpu().numpy(), ref, want)
-    if tag == "b":
+    if tag != "a":
         return  # the front-end is model-independent
     dcm = rs.randn(B, F, 72).astype(np.float32)
     want_d = np.stack([s.adj.cmvn(dcm[b]) for b in range(B)])
@@ -123,8 +138,7 @@ def test_stage_entries_against_truth(sys_, dev, tag, F, B):
     assert torch.equal(dr, dr3)
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F,B", CASES)
+@pytest.mark.parametrize("F,B,tag", MODEL_CASES, ids=MODEL_CASE_IDS)
 def test_chain_gradient_against_truth(sys_, dev, tag, F, B):
     """flags 3 and 1, both judged losses, err_ref the reference's recorded gradient; flag 2 against the flag-1 truth pushed
     through the delta adjoint; then the saturated rows: finite, and the loss of want_grad=False bit for bit"""
@@ -132,7 +146,7 @@ def test_chain_gradient_against_truth(sys_, dev, tag, F, B):
     m = s.m
     assert s.gf["meta"]["judged_losses"] == ["ce", "margin"]
     for flag in (3, 1):
-        x = dv(s.g["x_%d" % F] if flag == 3 else s.raws["raw_%d" % F], dev)
+        x = dv(s.x(F, flag), dev)
         for loss in ("ce", "margin"):
             key = "%s_f%d_%d" % (loss, flag, F)
             y = torch.from_numpy(s.gf["y_" + key]).to(dev)
@@ -212,10 +226,67 @@ def test_invariance_under_batching_and_chunking(sys_, dev):
         assert all(torch.equal(a[lo:hi], b) for a, b in zip(full, part)), (lo, hi)
 
 
+def group_rows(s, B0=16):
+    """tests/test_gpu_ivector.py's call of model C: B0 rows of other frames, then the fixture's three utterances of 13 frames"""
+    from speakerguard_amd import synth
+    return np.concatenate([synth.make_iv_frames(s.w, B0, 13, seed=77), s.g["x_13"]])
+
+
+def test_second_utterance_group_against_truth(sys_, dev):
+    """19 rows of model C, flag 3: iv_rowdot's (and the forward assembly's) second group of 16 utterances holds the fixture's
+    three -- both judged losses against truth under the rule and bit-equal to the 3-row call; then sg_iv_extract_backward alone"""
+    from speakerguard_amd import _native as N
+    s = sys_["c"]
+    m, C, Rk = s.m, MODELS["c"]["C"], MODELS["c"]["R"]
+    x19 = dv(group_rows(s), dev)
+    rs = np.random.RandomState(19)
+    for loss in ("ce", "margin"):
+        key = "%s_f3_13" % loss
+        y = torch.from_numpy(np.concatenate([rs.randint(0, MODELS["c"]["n_spk"], 16), s.gf["y_" + key]])).to(dev)
+        full = m.loss_grad(x19, y, spec_of(loss), flag=3, want_grad=True)
+        three = m.loss_grad(x19[16:], y[16:], spec_of(loss), flag=3, want_grad=True)
+        assert full[3].shape == x19.shape
+        judge("c 19 rows chain flag 3 %s F=13" % loss, full[3][16:].cpu().numpy(), s.gf["grad_" + key], s.truth_grad(13, 3, loss)[1])
+        assert all(torch.equal(a[16:], b) for a, b in zip(full, three)), loss
+    # the solve's adjoint with B = 19: rows 16 .. 18 are test_stage_entries_against_truth's case
+    n32, f32, dw, want, ref = s.solve_case(13)
+    n16, f16 = m.stats(x19[:16])
+    n_d = torch.cat([n16, dv(n32, dev)]).contiguous()
+    f_d = torch.cat([f16, dv(f32, dev)]).contiguous()
+    dw_d = dv(np.concatenate([rs.randn(16, Rk), dw]), dev)
+
+    def run(lo, hi):
+        nb = hi - lo
+        dn, df = torch.empty(nb, C, device=dev), torch.empty(nb, C, 72, device=dev)
+        a, b, c = n_d[lo:hi].contiguous(), f_d[lo:hi].contiguous(), dw_d[lo:hi].contiguous()
+        m.ctx.call("sg_iv_extract_backward", N._ptr(a), N._ptr(b), N._ptr(c), nb, N._ptr(dn), N._ptr(df), m._stream())
+        torch.cuda.synchronize()
+        return dn, df
+
+    dn, df = run(0, 19)
+    judge("c 19 rows extract_bwd d_zeroth F=13", dn[16:].cpu().numpy(), np.stack([r[0] for r in ref]), np.stack([r[0] for r in want]))
+    judge("c 19 rows extract_bwd d_first F=13", df[16:].cpu().numpy(), np.stack([r[1] for r in ref]), np.stack([r[1] for r in want]))
+    for lo, hi in ((16, 19), (0, 16)):
+        dn1, df1 = run(lo, hi)
+        assert torch.equal(dn[lo:hi], dn1) and torch.equal(df[lo:hi], df1), (lo, hi)
+
+
+def test_a_33_row_gradient_equals_its_rows(sys_, dev):
+    """model C, groups of 16, 16 and 1 utterances: the first and last row of every group equal the same row sent alone"""
+    s = sys_["c"]
+    x = dv(group_rows(s, 30), dev)
+    y = torch.from_numpy(np.random.RandomState(33).randint(0, MODELS["c"]["n_spk"], 33)).to(dev)
+    for loss in ("ce", "margin"):
+        full = s.m.loss_grad(x, y, spec_of(loss), flag=3, want_grad=True)
+        for i in (0, 15, 16, 31, 32):
+            one = s.m.loss_grad(x[i:i + 1], y[i:i + 1], spec_of(loss), flag=3, want_grad=True)
+            assert all(torch.equal(a[i:i + 1], b) for a, b in zip(full, one)), (loss, i)
+
+
 def test_forward_outputs_are_the_forward_pass(sys_, dev):
-    for tag in ("a", "b"):
+    for tag in ("a", "b", "c"):
         s = sys_[tag]
-        for flag, x in ((3, s.g["x_100"]), (1, s.raws["raw_100"])):
+        for flag, x in ((3, s.x(100, 3)), (1, s.x(100, 1))):
             x = dv(x, dev)
             y = torch.from_numpy(s.gf["y_ce_f%d_100" % flag]).to(dev)
             for loss in ("ce", "margin"):

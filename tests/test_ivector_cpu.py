@@ -13,8 +13,16 @@ from conftest import ROOT, load_golden
 from speakerguard_amd import _native, synth
 from speakerguard_amd.model import iv_plda as M
 
-MODELS = {"a": dict(seed=0, C=16, R=24, D=10, n_spk=4), "b": dict(seed=1, C=80, R=100, D=24, n_spk=5)}
+MODELS = {"a": dict(seed=0, C=16, R=24, D=10, n_spk=4), "b": dict(seed=1, C=80, R=100, D=24, n_spk=5),
+          "c": dict(seed=2, C=272, R=262, D=24, n_spk=5)}
 CASES = ((2, 5), (13, 5), (100, 3), (331, 1))
+# model C = 256 + 16 components, 256 + 6 i-vector entries: the smallest sizes at which every 256-wide loop of the kernels takes
+# a second, partial pass (tests/golden/make_golden_ivector.py); each model carries its own cases
+CASES_OF = {"a": CASES, "b": CASES, "c": ((13, 3), (100, 2))}
+FILES = {"a": "iv_ref.npz", "b": "iv_ref_b.npz", "c": "iv_ref_c.npz"}
+GRAD_FILES = {"a": "iv_grad_ref.npz", "b": "iv_grad_ref_b.npz", "c": "iv_grad_ref_c.npz"}
+MODEL_CASES = [(F, B, tag) for tag in "abc" for F, B in CASES_OF[tag]]
+MODEL_CASE_IDS = ["%d-%d-%s" % mc for mc in MODEL_CASES]  # (the ids of the two stacked parametrisations A and B had)
 KEYS = ("gconsts", "means_invcovars", "invcovars", "extractor", "sigma_inv", "ivector_offset", "emb_mean", "lda", "plda_mean",
         "plda_transform", "plda_psi", "enroll")
 # float32 unit roundoff times 64: sqrt(2700) ~ 52 rounding steps of the longest sum, random-walk growth, relative to the largest
@@ -32,7 +40,7 @@ def checksum(w):
 @pytest.fixture(scope="module")
 def fixtures():
     out = {}
-    for tag, name in (("a", "iv_ref.npz"), ("b", "iv_ref_b.npz")):
+    for tag, name in FILES.items():
         g = load_golden(name)
         w = synth.make_iv_weights(**MODELS[tag])
         assert checksum(w) == g["meta"][tag]["weights_sha256"], "synth.make_iv_weights moved: regenerate tests/golden/iv_ref*.npz"
@@ -53,23 +61,23 @@ def test_front_end_restated(fixtures, F, B):
     assert rel(g["cmvn_%d" % F], R.cmvn(delta)) <= REF_REL
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F,B", CASES)
+@pytest.mark.parametrize("F,B,tag", MODEL_CASES, ids=MODEL_CASE_IDS)
 def test_chain_restated(fixtures, tag, F, B):
     w, g, truth = fixtures[tag]
     t = truth.chain(g["x_%d" % F])
     for k in ("zeroth", "first", "ivector", "emb", "scores"):
         assert rel(g["%s_%d" % (k, F)], t[k]) <= REF_REL, k
     assert np.array_equal(t["decisions"], g["decisions_%d" % F])
-    raw = fixtures["a"][1]["raw_%d" % F]
+    raw = fixtures["a"][1]["raw_%d" % F][:B]  # (model C: the first rows of the shared raw inputs)
     t1 = truth.chain(R.cmvn(R.add_delta(raw)))
     assert rel(g["raw_scores_%d" % F], t1["scores"]) <= REF_REL
     assert np.array_equal(t1["decisions"], g["raw_decisions_%d" % F])
 
 
 def test_generator_recorded_its_asserts(fixtures):
-    for tag in ("a", "b"):
+    for tag in ("a", "b", "c"):
         info = fixtures[tag][1]["meta"][tag]
+        assert [tuple(c) for c in fixtures[tag][1]["meta"]["cases"]] == list(CASES_OF[tag])
         assert min(min(v) for k, v in info["cond_L"].items() if int(k) >= 100) >= 100.0
         assert all(5.0 / MODELS[tag]["C"] < v < 0.85 for v in info["top_posterior"].values())
         assert info["min_gap_over_err"] > 100.0
@@ -98,7 +106,7 @@ def test_parsers_refuse_a_short_triangle(tmp_path):
         M.parse_fgmm_file(paths["fgmm_file"])
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("tag", ["a", "b", "c"])
 def test_packing_equals_the_direct_form(fixtures, tag):
     w, g, truth = fixtures[tag]
     x = g["x_13"].reshape(-1, 72)

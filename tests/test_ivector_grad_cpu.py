@@ -15,7 +15,7 @@ import iv_restate_grad as G
 from conftest import ROOT, load_golden
 from speakerguard_amd import _native, synth
 from speakerguard_amd.model import iv_plda as M
-from test_ivector_cpu import CASES, MODELS, checksum
+from test_ivector_cpu import CASES_OF, FILES, GRAD_FILES, MODEL_CASE_IDS, MODEL_CASES, MODELS, checksum
 
 REF_BOUND = 2.0 ** -16  # the generator's condition: the reference's own error, relative to max|truth| of the utterance
 
@@ -27,7 +27,7 @@ def rel(a, b):
 @pytest.fixture(scope="module")
 def sys_():
     out = {}
-    for tag, name in (("a", "iv_ref.npz"), ("b", "iv_ref_b.npz")):
+    for tag, name in FILES.items():
         g = load_golden(name)
         w = synth.make_iv_weights(**MODELS[tag])
         assert checksum(w) == g["meta"][tag]["weights_sha256"]
@@ -35,8 +35,7 @@ def sys_():
     return out
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F,B", CASES)
+@pytest.mark.parametrize("F,B,tag", MODEL_CASES, ids=MODEL_CASE_IDS)
 def test_differentiable_forward_equals_the_restatement(sys_, tag, F, B):
     w, g, ag, _ = sys_[tag]
     x = g["x_%d" % F]
@@ -44,7 +43,7 @@ def test_differentiable_forward_equals_the_restatement(sys_, tag, F, B):
     got = ag.chain(G.t64(x))
     for k in ("zeroth", "first", "ivector", "emb", "scores"):
         assert rel(got[k].numpy(), want[k]) <= 1e-12, k
-    raw = sys_["a"][1]["raw_%d" % F]
+    raw = sys_["a"][1]["raw_%d" % F][:B]
     delta = G.add_delta_t(G.t64(raw))
     assert rel(delta.numpy(), R.add_delta(raw)) <= 1e-12
     assert rel(G.cmvn_t(delta).numpy(), R.cmvn(R.add_delta(raw))) <= 1e-12
@@ -66,8 +65,10 @@ def test_losses_equal_the_oracle():
             np.testing.assert_allclose(G.dscores_np(s.numpy(), int(l), loss), st.grad.numpy(), rtol=1e-12, atol=1e-15)
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("F", [2, 13, 100])
+ADJOINT_CASES = [(F, tag) for tag in "abc" for F in (2, 13, 100) if F in dict(CASES_OF[tag])]
+
+
+@pytest.mark.parametrize("F,tag", ADJOINT_CASES, ids=["%d-%s" % c for c in ADJOINT_CASES])
 def test_hand_adjoints_equal_autograd(sys_, tag, F):
     """steps 1-6 one by one, each fed float64 inputs and a random output gradient, then the whole chain at flags 3 and 1"""
     w, g, ag, adj = sys_[tag]
@@ -113,10 +114,10 @@ def test_hand_adjoints_equal_autograd(sys_, tag, F):
 
 
 def grad_fixture(tag):
-    return load_golden("iv_grad_ref%s.npz" % ("" if tag == "a" else "_b"))
+    return load_golden(GRAD_FILES[tag])
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("tag", ["a", "b", "c"])
 def test_reference_gradients_against_the_restatement(sys_, tag):
     """the generator's condition, checked again here: on every judged case the reference's float32 autograd stays within
     2^-16 max|truth| of the float64 restatement; the saturated rows (cross-entropy at the decided label) are recorded only"""
@@ -124,8 +125,9 @@ def test_reference_gradients_against_the_restatement(sys_, tag):
     gf = grad_fixture(tag)
     raws = sys_["a"][1]
     assert gf["meta"]["weights_sha256"] == checksum(w)
-    for F, B in CASES:
-        for flag, x in ((3, g["x_%d" % F]), (1, raws["raw_%d" % F])):
+    assert [tuple(c) for c in gf["meta"]["cases"]] == list(CASES_OF[tag])
+    for F, B in CASES_OF[tag]:
+        for flag, x in ((3, g["x_%d" % F]), (1, raws["raw_%d" % F][:B])):
             for loss in gf["meta"]["judged_losses"]:
                 y = gf["y_%s_f%d_%d" % (loss, flag, F)]
                 ls, gt, _ = ag.loss_and_grad(x, y, loss.split("_")[0], flag)
