@@ -7,7 +7,9 @@
  *
  * Conventions
  *   - plain C, no torch types; every pointer marked "dev" is a DEVICE pointer owned by the
- *     caller (e.g. tensor.data_ptr()); pointers marked "host" are host memory.
+ *     caller (e.g. tensor.data_ptr()); pointers marked "host" are host memory.  A device pointer needs only the
+ *     alignment of its element type (a row slice of a batch of odd length is fine; sg_conv1d_rows alone asks for 16
+ *     bytes), and a context may be driven from any ONE stream at a time.
  *   - the library owns only the workspace inside sg_ctx (grown on demand, freed by sg_destroy).
  *   - every call returns 0 on success, non-zero on error; sg_last_error(ctx) gives the text.
  *     Nothing throws across the ABI.
@@ -465,7 +467,8 @@ int sg_trace_end(sg_ctx* ctx, int32_t* tags_out, float* ms_out, int32_t capacity
  *   C[b*Tc + t][n] = epi( sum_{j < taps} sum_{c < Kc} A[b*Ta + t + tap_base + j*tap_step][c] * W[j*Kc + c][n] )
  *
  * rows outside [0, Ta) of an utterance contribute zero.  A: (B*Ta, Kc) floats, W: (taps*Kc, N), C: (B*Tc, N);
- * Kc % 32 == 0, N % 128 == 0.  epi: 0 none, 1 relu(acc + bias[n]), 2 acc where mask[row][n] > 0 else 0
+ * Kc % 32 == 0, N % 128 == 0, so every row is a multiple of 16 bytes: a, w, c, bias and mask must be 16-byte aligned
+ * (SG_ERR_ARG before any launch otherwise).  epi: 0 none, 1 relu(acc + bias[n]), 2 acc where mask[row][n] > 0 else 0
  * (mask shaped like C).  kernel: 0 = what the TDNN layers get (stream-K with 16-wave 256x128 quad-fed blocks when
  * the shape qualifies, one 16x16 block per wave on the 16x16x4 MFMA when there are at most 2800 such blocks, else one
  * quad-fed 64x128 block per tile), 1 = one b32-fed 64x128 block per tile, 2 = stream-K with the b32-fed 8-wave kernel,

@@ -251,7 +251,8 @@ bool sg::feco_pair_buffers(sg_ctx* ctx) {
     const size_t inst_max = (size_t)cus / 2, words = inst_max * 2 * 2 * kFecoMergeCap;  // room for the most instances that can be paired
     void *px = nullptr, *pf = nullptr;
     if (hipMalloc(&px, words * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&pf, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
-        hipMemset(pf, 0, inst_max * 2 * sizeof(unsigned)) == hipSuccess) {
+        hipMemset(pf, 0, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
+        hipDeviceSynchronize() == hipSuccess) {  // (a null-stream fill, read by launches on the caller's stream: awaited, once)
         ctx->feco_xchg = static_cast<unsigned long long*>(px);
         ctx->feco_flags = static_cast<unsigned*>(pf);
         ctx->model_allocs.push_back(px);

@@ -85,9 +85,9 @@ hipError_t launch_input_scale(const float* x, int64_t n, float* scratch, float* 
 // ---------------------------------------------------------------- PGD update (attack/FGSM.py:65,68)
 __global__ __launch_bounds__(256) void pgd_update_kernel(float* __restrict__ x, const float* __restrict__ g,
                                                          const float* __restrict__ lo, const float* __restrict__ hi,
-                                                         int64_t n, float step, int grad_sign) {
+                                                         int64_t n, float step, int grad_sign, int vec) {
     const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i4 + 3 < n) {
+    if (vec && i4 + 3 < n) {
         float4 xv = *reinterpret_cast<float4*>(x + i4);
         const float4 gv = *reinterpret_cast<const float4*>(g + i4);
         const float4 lv = *reinterpret_cast<const float4*>(lo + i4);
@@ -98,7 +98,9 @@ __global__ __launch_bounds__(256) void pgd_update_kernel(float* __restrict__ x, 
 #undef SG_UPD
         *reinterpret_cast<float4*>(x + i4) = xv;
     } else {
-        for (int64_t i = i4; i < n; ++i) {
+        // the row's tail, or (vec == 0: a base off a 16-byte boundary) this thread's four; step * +-1 is exact: same bits as above
+        const int64_t e = i4 + 4 < n ? i4 + 4 : n;
+        for (int64_t i = i4; i < e; ++i) {
             const float gv = g[i];
             const float sg = gv > 0.f ? 1.f : (gv < 0.f ? -1.f : 0.f);
             x[i] = fminf(fmaxf(x[i] + step * (float)grad_sign * sg, lo[i]), hi[i]);
@@ -109,7 +111,11 @@ __global__ __launch_bounds__(256) void pgd_update_kernel(float* __restrict__ x, 
 hipError_t launch_pgd_update(float* x, const float* g, const float* lo, const float* hi, int64_t n, float step,
                              int grad_sign, hipStream_t s) {
     const int64_t blocks = (n + 1023) / 1024;
-    hipLaunchKernelGGL(pgd_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, g, lo, hi, n, step, grad_sign);
+    // the C-ABI asks for no alignment of a caller's buffer (a row slice of a batch of odd length): 16-byte accesses only when
+    // all four bases allow them
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(lo) |
+                      reinterpret_cast<uintptr_t>(hi)) & 15) == 0;
+    hipLaunchKernelGGL(pgd_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, g, lo, hi, n, step, grad_sign, vec);
     return hipGetLastError();
 }
 

@@ -246,7 +246,7 @@ SP_DEV int sp_dft(float2* buf, int cur, const SpPlan& p, const float2* tab, int 
 // One workgroup per row.  out == nullptr: the spectrum only (sg_wav_spectrum); else the gate (sg_wav_spectrum_gate).
 template <bool LDS>
 __global__ void __launch_bounds__(kSpThreads)
-sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float2* spec, float* peak, const float* factor, float* out,
+sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float* spec, float* peak, const float* factor, float* out,
           uint8_t* keep, int32_t* kept) {
     extern __shared__ float2 sp_lds[];
     __shared__ float red_f[kSpThreads / 64];
@@ -267,7 +267,8 @@ sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float2* spec,
     const float2* post = tab + p.o_post;
     const bool gate = out != nullptr;
     const float f = gate ? factor[row] : 0.f;
-    float2* srow = spec ? spec + row * (size_t)(M + 1) : nullptr;
+    // (the caller's spectrum is a float buffer, aligned as floats: a pair goes out as two floats, not as one 8-byte word)
+    float* srow = spec ? spec + row * 2 * (size_t)(M + 1) : nullptr;
     uint8_t* krow = keep ? keep + row * (size_t)(M + 1) : nullptr;
     float pk = 0.f;
     int cnt = 0;
@@ -288,8 +289,8 @@ sp_kernel(SpPlan p, const float2* tab, const float* x, float2* ws, float2* spec,
         const float mk = sp_mag(Xk), mm = sp_mag(Xm);
         pk = fmaxf(pk, fmaxf(mk, mm));
         if (srow) {
-            srow[k] = Xk;
-            if (two) srow[m] = Xm;
+            srow[2 * k] = Xk.x, srow[2 * k + 1] = Xk.y;
+            if (two) srow[2 * m] = Xm.x, srow[2 * m + 1] = Xm.y;
         }
         if (gate) {
             const bool kk = !(mk < f), km = !(mm < f);
@@ -373,7 +374,7 @@ int sp_run(sg_ctx* ctx, const char* who, const float* x_dev, int32_t B, int32_t 
     }
     auto kernel = lds ? sp_kernel<true> : sp_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kSpThreads), dyn, s, e->plan, (const float2*)e->dev, x_dev, ctx->sp_ws.ptr,
-                       reinterpret_cast<float2*>(spec), peak, factor, out, keep, kept);
+                       spec, peak, factor, out, keep, kept);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(ctx, SG_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
     return SG_OK;

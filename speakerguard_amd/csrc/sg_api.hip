@@ -156,7 +156,10 @@ int build_tables(sg_ctx* ctx) {
     rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->cw2_scratch, 1024 * 32);
     rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_slabs, kSkSlabFloats);
     rc |= dev_alloc(ctx, ctx->model_allocs, &ctx->sk_flags, kSkFlags);
-    if (!rc && hipMemset(ctx->sk_flags, 0, kSkFlags * sizeof(unsigned)) != hipSuccess) rc = SG_ERR_HIP;
+    // the fill goes to the null stream and the stream-K launches that read the flags to the caller's, which need not be
+    // ordered behind it (a non-blocking stream): awaited here, once per context.  (From reading; no late fill was ever seen.)
+    if (!rc && (hipMemset(ctx->sk_flags, 0, kSkFlags * sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+        rc = SG_ERR_HIP;
     if (rc) return SG_ERR_HIP;
     ctx->tables_ready = true;
     return SG_OK;
@@ -1333,6 +1336,11 @@ int sg_conv1d_rows(sg_ctx* ctx, const float* a_dev, const float* w_dev, float* c
         return fail(ctx, SG_ERR_ARG, "sg_conv1d_rows: need Kc %% 32 == 0 and N %% 128 == 0 (got Kc=%d N=%d)", Kc, N);
     if (epi < 0 || epi > 2 || (epi == 1 && !bias_dev) || (epi == 2 && !mask_dev) || kernel < 0 || kernel > 10)
         return fail(ctx, SG_ERR_ARG, "sg_conv1d_rows: bad epi/kernel");
+    // every row here is a multiple of 16 bytes (Kc % 32, N % 128) and the kernels fetch rows as 16-byte words: a base off
+    // that boundary cannot come from a real caller (unlike a waveform's row slice), so it is refused, not served one by one
+    if ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(c_dev) |
+         reinterpret_cast<uintptr_t>(bias_dev) | reinterpret_cast<uintptr_t>(mask_dev)) & 15)
+        return fail(ctx, SG_ERR_ARG, "sg_conv1d_rows: a, w, c, bias and mask must be 16-byte aligned");
     if (build_tables(ctx) != SG_OK) return SG_ERR_HIP;
     hipStream_t s = (hipStream_t)stream;
     float* wq = nullptr;

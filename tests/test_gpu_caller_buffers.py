@@ -1,0 +1,910 @@
+"""The C-ABI on the buffers a caller may legally hand over (include/speakerguard_hip.h: element alignment only), and on a
+stream of the caller's choosing.
+
+A.  The sweep, SWEPT x k: every entry point that takes a caller's device buffer runs once the way every other test calls it
+    (fresh tensors; twice -- a call that does not repeat itself bit for bit fails its case, the comparison would mean
+    nothing) and once with EVERY device buffer, inputs, outputs and in-place state alike, k elements off a 16-byte boundary
+    between poisoned guards (tests/caller_buffers.py ``Relocated``; "mixed": consecutive buffers at 1, 2, 3, 0, ...).  The
+    judge asks for bit-equal outputs and intact guards.  Bit equality is the expectation: where a launcher has a 16-byte and
+    an element-wise form (launch_frames_to_wave, launch_an_frames_to_wave, launch_wav_rep_sum_update, launch_pgd_update,
+    input_range_partial_kernel, k_resample's row staging, k_pso's width dispatch) both build every output element by the same
+    chain of operations.  sg_conv1d_rows refuses a base off the boundary (its rows are multiples of 16 bytes): its case asks
+    for the refusal and for untouched outputs.
+B.  sg_input_scale, sg_pgd_update, sg_nes_queries and sg_fakebob_step against torch expressions that do not involve the
+    library, on moved buffers.
+C.  The public API on row slices of a batch of odd length (what a user does: ``big[1:3]``), against the same rows cloned.
+D.  The same public-API sequence, plus the calls that use the stream-K and the paired k-means flag words, a workspace regrow
+    and a re-enrolment, on one side stream, against the default stream in fresh models.
+
+Each case writes one line to the parity log: entry, k, stream, "bit-equal, guards intact" or what differed.
+"""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import caller_buffers as cb
+from conftest import log
+
+pytestmark = pytest.mark.gpu
+KS = (1, 2, 3, "mixed")
+
+# entry points with a caller-owned pointer that the sweep does not move, one line of reason each (the host test
+# tests/test_caller_buffers_host.py holds SWEPT + NOT_SWEPT against the prototypes of speakerguard_amd/_native.py)
+NOT_SWEPT = {
+    "sg_xv_set_enroll": "enrol call: its table is a host pointer, copied before the call returns",
+    "sg_iv_set_enroll": "enrol call: its table is a host pointer, copied before the call returns",
+    "sg_iv_load": "load call: the weight struct and everything it points to are host memory",
+    "sg_trace_end": "trace call: tags, milliseconds and count are written to host arrays",
+    "sg_stoi_debug_tables": "debug call without a context: copies the host-built tables to a host buffer",
+}
+
+T_XV = 6403  # the shortest odd length the suites use for the x-vector stack: a row slice starts 12 bytes off a boundary
+
+
+class Env:
+    """the models of the sweep, built on first use and shared (dither off: every call repeats itself)"""
+
+    @functools.cached_property
+    def dev(self):
+        assert torch.cuda.is_available()
+        return torch.device("cuda:0")
+
+    @functools.cached_property
+    def xv(self):
+        from speakerguard_amd import synth
+        from speakerguard_amd.model.xv_plda import xv_plda
+        return xv_plda.from_weights(synth.make_xv_weights(seed=0, D=200, n_spk=10), device=self.dev, dither=0.0)
+
+    @functools.cached_property
+    def an(self):
+        from speakerguard_amd import synth
+        from speakerguard_amd.model.audionet_csine import audionet_csine
+        return audionet_csine.from_weights(synth.make_audionet_state_dict(seed=0, num_class=251), device=self.dev)
+
+    @functools.cached_property
+    def iv(self):
+        from speakerguard_amd import synth
+        from speakerguard_amd.model.iv_plda import iv_plda
+        from test_ivector_cpu import MODELS
+        return iv_plda.from_weights(synth.make_iv_weights(**MODELS["a"]), device=self.dev, dither=0.0, white_box=True)
+
+    def ctx(self):
+        from speakerguard_amd.metric.metric import _context
+        return _context(self.dev)
+
+    def wave(self, B, T, seed=3):
+        from speakerguard_amd import synth
+        return torch.from_numpy(synth.make_waveforms(B, T, seed=seed)).to(self.dev)
+
+    def rand(self, *shape, seed=0, scale=1.0):
+        g = torch.Generator().manual_seed(seed + sum(shape))
+        return (torch.randn(*shape, generator=g) * scale).to(self.dev)
+
+
+ENV = Env()
+CASES = {}   # entry -> case function
+SWEPT = []
+
+
+def sweeps(*entries, refuses=False):
+    def deco(fn):
+        fn.entries, fn.refuses = entries, refuses
+        for e in entries:
+            assert e not in CASES, e
+            CASES[e] = fn
+            SWEPT.append(e)
+        return fn
+    return deco
+
+
+def ce():
+    from speakerguard_amd.attack.utils import SEC4SR_CrossEntropy
+    return SEC4SR_CrossEntropy()
+
+
+def margin():
+    from speakerguard_amd.attack.utils import SEC4SR_MarginLoss
+    return SEC4SR_MarginLoss(targeted=False, confidence=0.0, task="CSI", threshold=None, clip_max=True)
+
+
+def box(x, eps=0.002):
+    return torch.clamp(x - eps, min=-1), torch.clamp(x + eps, max=1)
+
+
+def named(prefix, values, names):
+    return {"%s.%s" % (prefix, n): v for n, v in zip(names, values)}
+
+
+LOOP_OUT = ("x_adv", "success", "decisions", "scores", "loss", "loss_trace", "decision_trace")
+
+
+# ---------------------------------------------------------------- attack state
+@sweeps("sg_pgd_update")
+def case_pgd_update(e):
+    x = e.rand(1027, seed=1, scale=0.5)
+    g = e.rand(1027, seed=2)
+    g[::7] = 0.0
+    lo, hi = box(x)
+    return {"x": e.xv.pgd_update(x, g, lo, hi, 0.0004, -1)}
+
+
+@sweeps("sg_cw2_step")
+def case_cw2_step(e):
+    B, T = 3, 1027
+    x = (torch.rand(B, 1, T, generator=torch.Generator().manual_seed(2)) * 1.9 - 0.95).to(e.dev)
+    const = torch.tensor([1e-3, 0.5, 20.0], device=e.dev)
+    mod, m, v = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
+    inp0, l0 = e.xv.cw2_step(mod, None, None, x, None, None, const, 1e-2, 0)
+    inp1, l1 = e.xv.cw2_step(mod, m, v, x, inp0, e.rand(B, 1, T, seed=5, scale=1e-3), const, 1e-2, 1)
+    return dict(inp0=inp0, l0=l0, inp1=inp1, l1=l1, modifier=mod, exp_avg=m, exp_avg_sq=v)
+
+
+@sweeps("sg_nes_queries")
+def case_nes_queries(e):
+    n, T, half = 2, 1027, 3
+    x = e.wave(n, T)
+    q_given, _ = e.xv.nes_queries(x, half, True, 0.001, 7, 0, e.rand(n, half, 1, T, seed=4))
+    q_own, z = e.xv.nes_queries(x, half, False, 0.001, 11, 4, None, want_noise=True, index_base=(1 << 32) + 5)
+    return dict(q_given=q_given, q_own=q_own, z=z)
+
+
+@sweeps("sg_nes_grad")
+def case_nes_grad(e):
+    n, T, half = 2, 1203, 3
+    out = {}
+    for tag, noise in (("given", e.rand(n, half, 1, T, seed=4)), ("own", None)):
+        grad = e.rand(n, 1, T, seed=6)
+        e.xv.nes_grad(e.rand(n, 2 * half + 1, seed=8), grad, n, T, half, True, 11, 4, noise, True, 0.001, 2)
+        out["grad_" + tag] = grad
+    return out
+
+
+@sweeps("sg_fakebob_step")
+def case_fakebob_step(e):
+    n, T = 2, 1027
+    x, grad, prev = e.wave(n, T), e.rand(n, 1, T, seed=1), e.rand(n, 1, T, seed=2)
+    grad[:, :, ::5] = 0.0
+    prev[:, :, ::5] = 0.0
+    lo, hi = box(x)
+    e.xv.fakebob_step(x, grad, prev, torch.tensor([1e-3, 2.5e-4], device=e.dev), lo, hi, 0.9, -1)
+    return dict(x=x, grad=grad)
+
+
+@sweeps("sg_wav_rep_sum_update")
+def case_rep_sum_update(e):
+    from speakerguard_amd import _native as N
+    G, n = 3, 2 * 1203
+    planes, carry = e.rand(G, n, seed=1), e.rand(n, seed=2)
+    x = e.rand(n, seed=3, scale=0.3)
+    lo, hi = box(x)
+    total, acc = torch.empty(n, device=e.dev), carry.clone()
+    s = e.xv._stream()
+    e.xv.ctx.call("sg_wav_rep_sum_update", N._ptr(planes), G, n, N._ptr(carry), N._ptr(total), None, None, None, 0.0, 1, s)
+    e.xv.ctx.call("sg_wav_rep_sum_update", N._ptr(planes), G, n, N._ptr(acc), N._ptr(acc), None, None, None, 0.0, 1, s)  # aliased
+    e.xv.ctx.call("sg_wav_rep_sum_update", N._ptr(planes), G, n, None, None, N._ptr(x), N._ptr(lo), N._ptr(hi), 0.0004, -1, s)
+    return dict(total=total, acc=acc, x=x)
+
+
+@sweeps("sg_loss_eval")
+def case_loss_eval(e):
+    from speakerguard_amd.attack.utils import loss_dscores
+    scores = e.rand(3, 10, seed=1, scale=3.0)
+    y = torch.tensor([1, -1, 9], device=e.dev)
+    out = {}
+    for tag, spec in (("ce", ce()), ("margin", margin())):
+        out.update(named(tag, loss_dscores(e.xv, scores, y, spec), ("dec", "loss", "dscores")))
+    return out
+
+
+@sweeps("sg_wav_finalize")
+def case_wav_finalize(e):
+    """pcm moves in 2-byte steps, the metrics in 8-byte steps"""
+    from speakerguard_amd.audio_io import quantize_pcm
+    from speakerguard_amd.metric.metric import batch_metrics
+    b = e.wave(3, 1203)
+    a = b + e.rand(3, 1, 1203, seed=1, scale=1e-3)
+    return dict(pcm=torch.from_numpy(quantize_pcm(a)), metrics=torch.from_numpy(batch_metrics(b, a)))
+
+
+@sweeps("sg_eer_threshold")
+def case_eer_threshold(e):
+    from speakerguard_amd.set_threshold import set_threshold
+    rs = np.random.RandomState(0)
+    return dict(out3=torch.tensor(set_threshold(rs.randn(37) + 1.0, rs.randn(101), device=e.dev), dtype=torch.float64))
+
+
+@sweeps("sg_input_scale")
+def case_input_scale(e):
+    from speakerguard_amd import _native as N
+    out = {}
+    for tag, x in (("unit", e.wave(2, 1027)), ("pcm", e.wave(2, 1027) * 20000.0)):
+        scale = torch.empty(1, device=e.dev)
+        e.xv.ctx.call("sg_input_scale", N._ptr(x), x.numel(), N._ptr(scale), e.xv._stream())
+        out[tag] = scale
+    return out
+
+
+# ---------------------------------------------------------------- x-vector
+@sweeps("sg_xv_mfcc", "sg_xv_mfcc_backward")
+def case_xv_mfcc(e):
+    x = e.wave(2, T_XV)
+    feats, saved = e.xv.frontend_forward(x)
+    out = dict(feats=feats, grad=e.xv.frontend_backward(saved, e.rand(*feats.shape, seed=1)))
+    # explicit dither noise: its pointer travels in sg_dither.noise_dev, past ``Relocated``
+    noise = cb.placed(e.rand(2, feats.shape[1], 400, seed=2))
+    noisy, saved_n = e.xv._mfcc(x, dither_noise=noise)
+    out.update(noisy=noisy, noisy_grad=e.xv.frontend_backward(saved_n, e.rand(*feats.shape, seed=1)))
+    return out
+
+
+@sweeps("sg_xv_cmvn", "sg_xv_cmvn_backward")
+def case_xv_cmvn(e):
+    f = e.rand(2, 41, 30, seed=2, scale=4.0)
+    return dict(cmvn=e.xv.cmvn(f), din=e.xv.cmvn_backward(f))
+
+
+@sweeps("sg_xv_forward", "sg_xv_debug_activation")
+def case_xv_forward(e):
+    out = {}
+    for flag, x in ((0, e.wave(2, T_XV)), (1, e.rand(2, 41, 30, seed=3, scale=4.0)), (2, e.rand(2, 41, 30, seed=4))):
+        out.update(named("flag%d" % flag, e.xv._forward(x, flag, want_emb=True, want_tdnn=True), ("dec", "scores", "emb", "tdnn")))
+    out["act3"] = e.xv.read_activation(3, 2)
+    return out
+
+
+@sweeps("sg_xv_enroll_override")
+def case_xv_enroll_override(e):
+    dec, scores = e.xv.make_decision(e.wave(2, T_XV), enroll_embs=e.rand(3, 200, seed=9))
+    return dict(dec=dec, scores=scores)
+
+
+@sweeps("sg_xv_loss_grad")
+def case_xv_loss_grad(e):
+    y = torch.tensor([1, 7], device=e.dev)
+    out = named("wav", e.xv.loss_grad(e.wave(2, T_XV), y, ce()), ("dec", "scores", "loss", "grad"))
+    out.update(named("feat", e.xv.loss_grad(e.rand(2, 41, 30, seed=3, scale=4.0), y, margin(), flag=1), ("dec", "scores", "loss", "grad")))
+    # the coefficient table of SG_LOSS_LINEAR: its pointer travels in sg_loss_spec.coef_dev, past ``Relocated``
+    from speakerguard_amd.attack.utils import ScoreVJP
+    vjp = ScoreVJP(cb.placed(e.rand(2, 10, seed=5)))
+    out.update(named("vjp", e.xv.loss_grad(e.wave(2, T_XV), y, vjp), ("dec", "scores", "loss", "grad")))
+    return out
+
+
+def xv_loop(e, method, B, T, *extra, **kw):
+    x = e.wave(B, T)
+    lo, hi = box(x)
+    y = torch.arange(B, device=e.dev) % 10
+    return dict(zip(LOOP_OUT, getattr(e.xv, method)(x, y, lo, hi, ce(), 0.0004, 2, 1, *extra, trace=True, **kw)))
+
+
+@sweeps("sg_xv_pgd_run")
+def case_xv_pgd_run(e):
+    return xv_loop(e, "pgd_run", 2, T_XV)
+
+
+@sweeps("sg_xv_pgd_run_defended")
+def case_xv_pgd_run_defended(e):
+    from speakerguard_amd.defense.frequency_domain import LPF
+    from speakerguard_amd.defense.time_domain import AS
+    return xv_loop(e, "pgd_run_defended", 2, T_XV, [AS(3), LPF()])
+
+
+@sweeps("sg_xv_pgd_run_feco")
+def case_xv_pgd_run_feco(e):
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    return xv_loop(e, "pgd_run_feco", 2, 16001, FeCoDefense(0.5))
+
+
+# ---------------------------------------------------------------- AudioNet, an even and an odd length
+AN_T = (16000, 16001)
+
+
+def an_loop(e, method, T, *extra):
+    from speakerguard_amd import synth
+    x = torch.from_numpy(synth.make_tone_waveforms(2, T)).to(e.dev)
+    lo, hi = box(x)
+    y = torch.tensor([3, 200], device=e.dev)
+    return named("T%d" % T, getattr(e.an, method)(x, y, lo, hi, ce(), 0.0004, 2, 1, *extra, trace=True), LOOP_OUT)
+
+
+@sweeps("sg_an_logmel", "sg_an_logmel_backward")
+def case_an_logmel(e):
+    out = {}
+    for T in AN_T:
+        feats, saved = e.an.frontend_forward(e.wave(2, T))
+        out["feats%d" % T], out["grad%d" % T] = feats, e.an.frontend_backward(saved, e.rand(*feats.shape, seed=1))
+    return out
+
+
+@sweeps("sg_an_forward", "sg_an_debug_activation")
+def case_an_forward(e):
+    out = {}
+    for T in AN_T:
+        out.update(named("wav%d" % T, e.an._forward(e.wave(2, T), 0, want_emb=True), ("dec", "scores", "emb")))
+    out.update(named("feat", e.an._forward(e.rand(2, 101, 32, seed=2), 1, want_emb=True), ("dec", "scores", "emb")))
+    out["act2"] = e.an.read_activation(2, 2)
+    return out
+
+
+@sweeps("sg_an_loss_grad")
+def case_an_loss_grad(e):
+    out, y = {}, torch.tensor([3, 200], device=e.dev)
+    for T in AN_T:
+        out.update(named("T%d" % T, e.an.loss_grad(e.wave(2, T), y, margin()), ("dec", "scores", "loss", "grad")))
+    return out
+
+
+@sweeps("sg_an_pgd_run")
+def case_an_pgd_run(e):
+    out = {}
+    for T in AN_T:
+        out.update(an_loop(e, "pgd_run", T))
+    return out
+
+
+@sweeps("sg_an_pgd_run_feco")
+def case_an_pgd_run_feco(e):
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    return an_loop(e, "pgd_run_feco", 16001, FeCoDefense(0.5))
+
+
+@sweeps("sg_an_pgd_run_defended")
+def case_an_pgd_run_defended(e):
+    from speakerguard_amd.defense.time_domain import MS
+    return an_loop(e, "pgd_run_defended", 16001, [MS(3)])
+
+
+# ---------------------------------------------------------------- i-vector: the smallest system of test_gpu_ivector.py
+@sweeps("sg_iv_forward", "sg_iv_enroll_override")
+def case_iv_forward(e):
+    out = named("wav", e.iv._forward(e.wave(2, T_XV), 0, want_emb=True, want_ivector=True), ("dec", "scores", "emb", "ivector"))
+    frames = e.rand(2, 13, 72, seed=1)
+    out.update(named("cmvn", e.iv._forward(frames, 3, want_emb=True, want_ivector=True), ("dec", "scores", "emb", "ivector")))
+    out.update(named("override", e.iv.make_decision(frames, flag=3, enroll_embs=e.rand(3, 10, seed=2)), ("dec", "scores")))
+    return out
+
+
+@sweeps("sg_iv_loss", "sg_iv_loss_grad")
+def case_iv_loss_grad(e):
+    y = torch.tensor([1, 3], device=e.dev)
+    out = named("wav", e.iv.loss_grad(e.wave(2, T_XV), y, ce()), ("dec", "scores", "loss", "grad"))
+    out.update(named("cmvn", e.iv.loss_grad(e.rand(2, 13, 72, seed=1), y, margin(), flag=3), ("dec", "scores", "loss", "grad")))
+    out.update(named("loss_only", e.iv.loss_grad(e.rand(2, 13, 72, seed=1), y, ce(), flag=3, want_grad=False)[:3], ("dec", "scores", "loss")))
+    return out
+
+
+@sweeps("sg_iv_delta_cmvn", "sg_iv_delta_cmvn_backward")
+def case_iv_delta_cmvn(e):
+    raw, d72 = e.rand(2, 13, 24, seed=1, scale=4.0), e.rand(2, 13, 72, seed=2)
+    # delta -> CMVN hands its input over as a bare address (three column blocks of the same rows): moved by hand
+    return dict(delta=e.iv.comput_feat_from_feat(raw, 1, 2), cmvn=e.iv.comput_feat_from_feat(raw, 1, 3),
+                cmvn_from_delta=e.iv.comput_feat_from_feat(cb.placed(e.rand(2, 13, 72, seed=3, scale=4.0)), 2, 3),
+                d_delta=e.iv.feat_from_feat_backward(d72, 2, 3), d_raw=e.iv.feat_from_feat_backward(d72, 1, 2))
+
+
+@sweeps("sg_iv_stats", "sg_iv_extract", "sg_iv_stats_backward", "sg_iv_extract_backward")
+def case_iv_stages(e):
+    from speakerguard_amd import _native as N
+    m, B, F, Cn, R = e.iv, 2, 13, 16, 24
+    frames = e.rand(B, F, 72, seed=1)
+    n, f = m.stats(frames)
+    w = m.extract(n, f)
+    dw = e.rand(B, R, seed=2)
+    dn, df = torch.empty(B, Cn, device=e.dev), torch.empty(B, Cn, 72, device=e.dev)
+    m.ctx.call("sg_iv_extract_backward", N._ptr(n), N._ptr(f), N._ptr(dw), B, N._ptr(dn), N._ptr(df), m._stream())
+    dx = torch.empty(B, F, 72, device=e.dev)
+    m.ctx.call("sg_iv_stats_backward", N._ptr(frames), B, F, N._ptr(dn), N._ptr(df), N._ptr(dx), m._stream())
+    return dict(zeroth=n, first=f, ivector=w, d_zeroth=dn, d_first=df, d_cmvn=dx)
+
+
+# ---------------------------------------------------------------- input defenses
+def defense_case(e, d, T=1203, backward=True, **kw):
+    x = e.wave(2, T)
+    out, saved = d.fwd(x, **kw)
+    res = {"out": out}
+    if backward:
+        res["gx"] = d.bwd(saved, e.rand(*out.shape, seed=1))
+    return res
+
+
+@sweeps("sg_wav_defense_forward", "sg_wav_defense_backward")
+def case_wav_defense(e):
+    from speakerguard_amd.defense.time_domain import AS, AT, MS, QT
+    out = {}
+    for name, d in (("QT", QT(128)), ("AS", AS(5)), ("MS", MS(5)), ("AT", AT(25, seed=3))):
+        out.update(named(name, defense_case(e, d, backward=name != "QT").values(), ("out", "gx")))
+    # explicit noise: its pointer travels in sg_wav_defense.noise_dev, past ``Relocated``
+    given = cb.placed(e.rand(2, 1, 1203, seed=7))
+    out.update(named("AT_given", defense_case(e, AT(25), noise=given).values(), ("out", "gx")))
+    return out
+
+
+@sweeps("sg_wav_filter_forward", "sg_wav_filter_backward")
+def case_wav_filter(e):
+    from speakerguard_amd.defense.frequency_domain import BPF, LPF
+    out = named("lpf", defense_case(e, LPF()).values(), ("out", "gx"))
+    out.update(named("bpf", defense_case(e, BPF()).values(), ("out", "gx")))
+    return out
+
+
+@sweeps("sg_wav_resample_forward", "sg_wav_resample_backward")
+def case_wav_resample(e):
+    from speakerguard_amd.defense.frequency_domain import DS
+    out = named("same", defense_case(e, DS(0.5)).values(), ("out", "gx"))
+    out.update(named("own_length", defense_case(e, DS(0.5, same_size=False)).values(), ("out", "gx")))
+    return out
+
+
+@sweeps("sg_wav_spectrum", "sg_wav_spectrum_gate")
+def case_wav_spectrum(e):
+    """the spectrum is a float buffer of (re, im) pairs: at k = 1 and 3 every pair straddles an 8-byte boundary"""
+    from speakerguard_amd.attack.Kenan import wav_spectrum, wav_spectrum_gate
+    out = {}
+    for T in (480, 662):  # a smooth length and one that takes Bluestein's route
+        x = e.wave(2, T)
+        spec, peak = wav_spectrum(x)
+        gated, keep, kept = wav_spectrum_gate(x, 0.3 * peak, want_keep=True)
+        out.update(named("T%d" % T, (torch.view_as_real(spec), peak, gated, keep, kept), ("spec", "peak", "out", "keep", "kept")))
+    return out
+
+
+@sweeps("sg_ssa_decompose", "sg_ssa_reconstruct")
+def case_ssa(e):
+    from speakerguard_amd.attack.KenanSSA import ssa_decompose, ssa_reconstruct
+    st = ssa_decompose(e.wave(2, 100), want_cov=True)
+    out, out64 = ssa_reconstruct(st, [2, 4], want64=True)
+    return dict(xq=st["xq"], eval=st["eval"], evec=st["evec"], sweeps=st["sweeps"], cov=st["cov"], out=out, out64=out64)
+
+
+@sweeps("sg_wav_stoi")
+def case_wav_stoi(e):
+    from speakerguard_amd.metric.metric import _stoi_rows
+    from speakerguard_amd import _native as N
+    b = e.wave(2, 6758).squeeze(1).contiguous()
+    a = (b + e.rand(2, 6758, seed=1, scale=0.02)).contiguous()
+    d, frames = _stoi_rows(e.ctx(), b, a, 16000, N.current_stream_ptr(e.dev))
+    return dict(stoi=torch.from_numpy(d), frames=torch.from_numpy(frames))
+
+
+@sweeps("sg_pso_init", "sg_pso_select", "sg_pso_move")
+def case_pso(e):
+    """the smallest shape of test_gpu_siren.py whose T allows the 16-byte kernels, under both settings of SG_PSO_VEC: moved off
+    the boundary, both must fall to the element-wise kernels, with the same bits"""
+    from test_gpu_siren import INDEX_BASE, KEY, STATE, problem, to_device
+    n, P, T = 2, 5, 800
+    rows = [0, 1]
+    out = {}
+    old = os.environ.get("SG_PSO_VEC")
+    try:
+        for width in ("rule", "4"):
+            if width == "rule":
+                os.environ.pop("SG_PSO_VEC", None)
+            else:
+                os.environ["SG_PSO_VEC"] = width
+            x, lower, upper, cpu = problem(n, P, T, rows)
+            st = to_device(cpu)
+            xd, ld, ud = x.to(e.dev), lower.to(e.dev), upper.to(e.dev)
+            rs = np.random.RandomState(1)
+            q0 = e.xv.pso_init(st, xd, ld, ud, rows, 0, None, KEY, INDEX_BASE)  # own generator
+            report = e.xv.pso_select(st, e.rand(len(rows), P, seed=3), rows)
+            r12 = [torch.from_numpy(rs.uniform(1e-5, 1.0, (len(rows), P, 1, T)).astype(np.float32)).to(e.dev) for _ in range(2)]
+            q1 = e.xv.pso_move(st, xd, ld, ud, rows, [0, P - 1], [1, 1], 1, 0.74, 1.4961, 1.4961, KEY + 1, INDEX_BASE, *r12)
+            pos = torch.from_numpy(rs.uniform(-0.01, 0.01, (len(rows), P - 1, 1, T)).astype(np.float32)).to(e.dev)
+            vel = torch.from_numpy(rs.uniform(-0.02, 0.02, (len(rows), P, 1, T)).astype(np.float32)).to(e.dev)
+            q2 = e.xv.pso_init(st, xd, ld, ud, rows, 1, [P - 1, 2], KEY + 2, INDEX_BASE, pos, vel)  # given draws
+            q3 = e.xv.pso_move(st, xd, ld, ud, rows, [-1, 1], [1, 0], 1, 0.58, 1.4961, 1.4961, KEY + 3, INDEX_BASE)
+            res = dict(q0=q0, q1=q1, q2=q2, q3=q3, improved=st.improved, **{s: getattr(st, s) for s in STATE})
+            res.update({"report%d" % i: torch.from_numpy(np.asarray(r)) for i, r in enumerate(report)})
+            out.update({"%s.%s" % (width, k): v for k, v in res.items()})
+    finally:
+        if old is None:
+            os.environ.pop("SG_PSO_VEC", None)
+        else:
+            os.environ["SG_PSO_VEC"] = old
+    return out
+
+
+# ---------------------------------------------------------------- FeCo: F 37, D 30 (and D 72 for the wide kernel)
+def feco_buffers(e, rows, F, D, k):
+    return (torch.empty(rows, F, device=e.dev, dtype=torch.int32), torch.empty(rows, k, D, device=e.dev),
+            torch.empty(rows, k, device=e.dev, dtype=torch.int32))
+
+
+@sweeps("sg_feco_kmeans", "sg_feco_kmeans_seeded")
+def case_feco_kmeans(e):
+    from speakerguard_amd import _native as N
+    B, F, D, k = 2, 37, 30, 18
+    feat = e.rand(B, F, D, seed=1)
+    even, seeded = torch.empty(B, F, device=e.dev, dtype=torch.int32), torch.empty(B, F, device=e.dev, dtype=torch.int32)
+    s = N.current_stream_ptr(e.dev)
+    e.ctx().call("sg_feco_kmeans", N._ptr(feat), B, F, D, k, 10, N._ptr(even), s)
+    e.ctx().call("sg_feco_kmeans_seeded", N._ptr(feat), B, F, D, k, 10, C.c_uint64(77), 3, N._ptr(seeded), s)
+    return dict(even=even, seeded=seeded)
+
+
+@sweeps("sg_feco_kmeans_compress", "sg_feco_compress", "sg_feco_compress_backward")
+def case_feco_defense(e):
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    feat = e.rand(2, 37, 30, seed=1)
+    out = {}
+    for init in ("even", "random"):
+        d = FeCoDefense(0.5, init=init, seed=5)
+        comp, saved = d.fwd(feat)
+        again, _ = d.fwd(feat, ids=saved[0])
+        out.update(named(init, (comp, saved[0], saved[1], again, d.bwd(saved, e.rand(*comp.shape, seed=2))),
+                         ("out", "ids", "counts", "from_ids", "dfeat")))
+    return out
+
+
+@sweeps("sg_feco_kmeans_compress_rows", "sg_feco_compress_backward_reps")
+def case_feco_reps(e):
+    from speakerguard_amd import _native as N
+    B, F, D, k, reps = 2, 37, 30, 18, 2
+    s = N.current_stream_ptr(e.dev)
+    feat = e.rand(reps * B, F, D, seed=1)
+    ids, out, counts = feco_buffers(e, reps * B, F, D, k)
+    e.ctx().call("sg_feco_kmeans_compress_rows", N._ptr(feat), B, F, D, k, 10, 1, C.c_uint64(77), 3, reps, N._ptr(ids), N._ptr(out),
+                 N._ptr(counts), s)
+    ids2, out2, counts2 = feco_buffers(e, reps * B, F, D, k)
+    first = feat[:B].contiguous()
+    e.ctx().call("sg_feco_kmeans_compress", N._ptr(first), B, F, D, k, 10, 1, C.c_uint64(77), 3, reps, N._ptr(ids2), N._ptr(out2),
+                 N._ptr(counts2), s)
+    dfeat, dout = torch.empty(B, F, D, device=e.dev), e.rand(reps * B, k, D, seed=2)
+    e.ctx().call("sg_feco_compress_backward_reps", N._ptr(dout), N._ptr(ids2), N._ptr(counts2), B, F, D, k, 1, reps, N._ptr(dfeat), s)
+    return dict(ids=ids, out=out, counts=counts, ids2=ids2, out2=out2, counts2=counts2, dfeat=dfeat)
+
+
+@sweeps("sg_feco_kmeans_compress_metric")
+def case_feco_cos(e):
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    comp, saved = FeCoDefense(0.5, other_param="cos").fwd(e.rand(2, 37, 30, seed=1))
+    return dict(out=comp, ids=saved[0], counts=saved[1])
+
+
+@sweeps("sg_feco_kmeans_compress_wide")
+def case_feco_wide(e):
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    comp, saved = FeCoDefense(0.5, init="random", seed=2).fwd(e.rand(2, 37, 72, seed=1))
+    return dict(out=comp, ids=saved[0], counts=saved[1])
+
+
+@sweeps("sg_feco_warped")
+def case_feco_warped(e):
+    from speakerguard_amd.defense.feature_level import WarpedFeCoDefense
+    d = WarpedFeCoDefense(0.5, other_param="random", seed=4)
+    walk = torch.cumsum(e.rand(2, 37, 30, seed=1), 1).contiguous()
+    comp, saved = d.fwd(walk)
+    return dict(out=comp, init_ids=saved[0], init_counts=saved[1], boundaries=d.last_boundaries, sweeps=d.last_sweeps)
+
+
+# ---------------------------------------------------------------- the one entry that refuses a moved buffer
+CONV_FILL = -7.0
+
+
+@sweeps("sg_conv1d_rows", refuses=True)
+def case_conv1d_rows(e):
+    """every row is a multiple of 16 bytes by the entry's own rules (Kc % 32, N % 128): a base off the boundary is refused
+    with SG_ERR_ARG before any launch, and the outputs stay as they were"""
+    from speakerguard_amd import _native as N
+    B, Ta, Tc, Kc, n, taps = 3, 50, 46, 64, 128, 5
+    a, w = e.rand(B * Ta, Kc, seed=1), e.rand(taps * Kc, n, seed=2, scale=0.05)
+    bias = e.rand(n, seed=3)
+    out = torch.full((B * Tc, n), CONV_FILL, device=e.dev)
+    refused = 0
+    try:
+        e.ctx().call("sg_conv1d_rows", N._ptr(a), N._ptr(w), N._ptr(out), N._ptr(bias), None, B, Ta, Tc, Kc, n, taps, 1, 0, 1, 0,
+                     N.current_stream_ptr(e.dev))
+    except N.NativeError as err:
+        assert "code 1" in str(err) and "16-byte aligned" in str(err), err
+        refused = 1
+    return dict(out=out, refused=torch.tensor([refused]))
+
+
+# ================================================================ the sweep
+def to_host(out):
+    torch.cuda.synchronize()
+    return {k: (None if v is None else v.detach().cpu().clone()) for k, v in out.items()}
+
+
+_EXPECTED, _VERDICTS = {}, {}
+
+
+def expected_of(fn):
+    """the plain call, fresh tensors, twice: (outputs, None) or (None, why the two runs differ)"""
+    if fn not in _EXPECTED:
+        first, second = to_host(fn(ENV)), to_host(fn(ENV))
+        ok, why = cb.same(first, second, [])
+        _EXPECTED[fn] = (first, None) if ok else (None, "two plain runs differ: " + why)
+    return _EXPECTED[fn]
+
+
+def verdict_of(fn, k):
+    if (fn, k) not in _VERDICTS:
+        exp, broken = expected_of(fn)
+        if broken:
+            _VERDICTS[fn, k] = (False, broken, {})
+        else:
+            with cb.Relocated(k) as r:
+                got = to_host(fn(ENV))
+            if fn.refuses:
+                ok, why = cb.same({"out": torch.full_like(exp["out"], CONV_FILL)}, {"out": got["out"]}, r.windows)
+                if int(exp["refused"]) or not int(got["refused"]):
+                    ok, why = False, "refused: plain call %d, moved call %d" % (int(exp["refused"]), int(got["refused"]))
+                elif ok:
+                    why = "refused with SG_ERR_ARG, outputs untouched, guards intact"
+            else:
+                ok, why = cb.same(exp, got, r.windows)
+            _VERDICTS[fn, k] = (ok, why, dict(r.entries))
+    return _VERDICTS[fn, k]
+
+
+@pytest.mark.parametrize("k", KS, ids=lambda k: "k%s" % k)
+@pytest.mark.parametrize("entry", SWEPT)
+def test_entry_on_moved_buffers(entry, k):
+    fn = CASES[entry]
+    ok, why, entries = verdict_of(fn, k)
+    log("caller_buffers %-34s k %-5s stream default  %s" % (entry, k, why))
+    assert ok, (entry, k, why)
+    assert entries.get(entry, 0) > 0, "%s: the case never handed it a moved buffer (%s)" % (entry, sorted(entries))
+
+
+def test_xv_pgd_run_at_the_batch_that_takes_the_16_byte_overlap_add():
+    """launch_frames_to_wave takes its 16-byte form only from B T >= 16 x 48000 with T % 4 == 0: the smallest batch whose
+    element-wise fallback is reached by the base alone"""
+    plain = to_host(xv_loop(ENV, "pgd_run", 16, 48000))
+    ok, why = cb.same(plain, to_host(xv_loop(ENV, "pgd_run", 16, 48000)), [])
+    assert ok, "two plain runs differ: " + why
+    with cb.Relocated(1) as r:
+        got = to_host(xv_loop(ENV, "pgd_run", 16, 48000))
+    ok, why = cb.same(plain, got, r.windows)
+    log("caller_buffers %-34s k %-5s stream default  %s" % ("sg_xv_pgd_run 16x48000", 1, why))
+    assert ok, why
+    ENV.xv.check_health()
+
+
+# ================================================================ B. references that do not involve the library
+def scale_positions(n):
+    """index 0, n - 1, and one sample each inside the four-deep unrolled range, the single-vector range and the scalar tail of
+    input_range_partial_kernel (256 blocks x 1024 threads; the unrolled loop starts at 3 x 256 x 1024 float4)"""
+    stride, n4 = 256 * 1024, n // 4
+    pos = {0, n - 1}
+    unrolled = max(0, n4 - 3 * stride)           # float4 indices i < unrolled, and i + stride, i + 2 stride, i + 3 stride
+    if unrolled:
+        pos.add(4 * (2 * stride + unrolled // 2) + 1)
+    if n4 > unrolled:
+        pos.add(4 * (unrolled + (min(n4, stride) - unrolled) // 2) + 2)
+    if n % 4:
+        pos.add(4 * n4)
+    return sorted(pos)
+
+
+@pytest.mark.parametrize("n", [3, 1027, 3_200_003])
+def test_input_scale_against_the_reference_rule(n):
+    """3 200 003 is the smallest round size above 3 x 256 x 1024 x 4 floats, where the unrolled loop starts; the rule is the
+    reference's, as torch evaluates it on the CPU"""
+    from speakerguard_amd import _native as N
+    # (float4 2 x 262144 + 6784 is fetched by the unrolled loop, float4 137856 by the single-vector loop, 3 200 000 by the tail)
+    assert scale_positions(3_200_003) == [0, 551_426, 2_124_289, 3_200_000, 3_200_002]
+    assert scale_positions(1027) == [0, 514, 1024, 1026] and scale_positions(3) == [0, 2]
+    base = (torch.rand(n, generator=torch.Generator().manual_seed(n)) - 0.5)
+    assert float(base.abs().max()) <= 0.5
+    ctx, s = ENV.xv.ctx, ENV.xv._stream()
+    for k in (0, 1, 2, 3):
+        w = cb.window(base.to(ENV.dev), k)
+        scale = cb.window(torch.zeros(1, device=ENV.dev), k)
+        worst = "bit-equal, guards intact"
+        for pos in [None] + scale_positions(n):
+            for v in (1.2, -1.2):
+                x = base.clone()
+                if pos is not None:
+                    x[pos] = v
+                    w[pos] = v
+                want = 32768.0 if bool(0.9 * x.max() <= 1) and bool(0.9 * x.min() >= -1) else 1.0
+                assert want == (32768.0 if pos is None else 1.0)
+                ctx.call("sg_input_scale", N._ptr(w), n, N._ptr(scale), s)
+                got = float(scale.item())
+                if pos is not None:
+                    w[pos] = base[pos]
+                if got != want:
+                    worst = "n %d k %d deciding sample %r at %r: scale %r, expected %r" % (n, k, v, pos, got, want)
+        if not (cb.intact(w) and cb.intact(scale)):
+            worst = "a guard was damaged"
+        log("caller_buffers %-34s k %-5s stream default  %s" % ("sg_input_scale n=%d vs torch" % n, k, worst))
+        assert worst == "bit-equal, guards intact", worst
+
+
+@pytest.mark.parametrize("n", [1, 3, 5, 1023, 1025])
+def test_pgd_update_against_torch(n):
+    g = torch.Generator().manual_seed(n)
+    x = (torch.rand(n, generator=g) * 2 - 1).to(ENV.dev)
+    grad = torch.randn(n, generator=g).to(ENV.dev)
+    grad[::7] = 0.0
+    lower, upper = box(x)
+    for gsn in (1, -1):
+        want = torch.min(torch.max(x + 0.0004 * torch.sign(grad) * gsn, lower), upper)
+        for k in (0, 1, 2, 3, "mixed"):
+            with cb.Relocated(k) as r:
+                got = ENV.xv.pgd_update(x.clone(), grad, lower, upper, 0.0004, gsn)
+            ok, why = cb.same({"x": want}, {"x": got}, r.windows)
+            log("caller_buffers %-34s k %-5s stream default  %s" % ("sg_pgd_update n=%d sign %+d vs torch" % (n, gsn), k, why))
+            assert ok, (n, gsn, k, why)
+
+
+def test_nes_queries_and_fakebob_step_against_torch():
+    n, T, half, sigma = 2, 1027, 3, 0.001
+    g = torch.Generator().manual_seed(3)
+    x = (torch.rand(n, 1, T, generator=g) * 1.8 - 0.9).to(ENV.dev)
+    noise = torch.randn(n, half, 1, T, generator=g).to(ENV.dev)
+    prev, grad = torch.randn(n, 1, T, generator=g).to(ENV.dev), torch.randn(n, 1, T, generator=g).to(ENV.dev)
+    grad[:, :, ::5] = 0.0
+    prev[:, :, ::5] = 0.0
+    lr = torch.tensor([1e-3, 2.5e-4], device=ENV.dev)
+    lower, upper = box(x)
+    full = torch.cat((torch.zeros_like(x).unsqueeze(1), noise, -noise), 1)
+    want_q = (full * sigma + x.unsqueeze(1)).view(-1, 1, T)
+    mg = 0.9 * prev + (1.0 - 0.9) * grad
+    want_x = torch.min(torch.max(x + (-1) * lr.view(-1, 1, 1) * torch.sign(mg), lower), upper)
+    for k in (0, 1, 2, 3, "mixed"):
+        with cb.Relocated(k) as r:
+            q, _ = ENV.xv.nes_queries(x, half, True, sigma, 7, 0, noise)
+            xx, gg = x.clone(), grad.clone()
+            ENV.xv.fakebob_step(xx, gg, prev, lr, lower, upper, 0.9, -1)
+        ok, why = cb.same(dict(q=want_q, x=want_x, grad=mg), dict(q=q, x=xx, grad=gg), r.windows)
+        log("caller_buffers %-34s k %-5s stream default  %s" % ("sg_nes_queries / sg_fakebob_step vs torch", k, why))
+        assert ok, (k, why)
+
+
+# ================================================================ C / D. the public API: row slices, and a side stream
+def fresh_models(dev):
+    from speakerguard_amd import synth
+    from speakerguard_amd.model.audionet_csine import audionet_csine
+    from speakerguard_amd.model.iv_plda import iv_plda
+    from speakerguard_amd.model.xv_plda import xv_plda
+    from test_ivector_cpu import MODELS
+    return dict(xv=xv_plda.from_weights(synth.make_xv_weights(seed=0, D=200, n_spk=10), device=dev, dither=0.0),
+                an=audionet_csine.from_weights(synth.make_audionet_state_dict(seed=0, num_class=251), device=dev),
+                iv=iv_plda.from_weights(synth.make_iv_weights(**MODELS["a"]), device=dev, dither=0.0, white_box=True))
+
+
+def public_api(dev, rows, stream_cases):
+    """the sequence of groups C and D in fresh models.  `rows(big, B)`: how the B utterances are cut out of a batch of B + 2
+    (a slice, or its clone); -> (results, [(big, its copy before, the slice's rows)], the streams the calls named).
+    Everything is created on the current stream -- the process-wide context that the defenses, the metrics and Kenan's gate
+    share (``metric._context``) too: it is set aside for the length of the sequence, so that its first-use setup (tables,
+    pairing buffers, table caches) happens here like the models'.  Every stream argument handed to ``Context.call`` must be
+    the current stream."""
+    from speakerguard_amd import _native as N
+    from speakerguard_amd.metric import metric
+    shared_before = metric._ctx.pop(dev.index, None)
+    streams, plain_call = set(), N.Context.call
+
+    def call(ctx, name, *args):
+        if args and isinstance(args[-1], C.c_void_p):  # (every entry called here that ends in a pointer ends in its stream)
+            streams.add(args[-1].value or 0)
+        return plain_call(ctx, name, *args)
+
+    N.Context.call = call
+    try:
+        return _public_api(dev, rows, stream_cases, metric) + (streams,)
+    finally:
+        N.Context.call = plain_call
+        metric._ctx.pop(dev.index, None)
+        if shared_before is not None:
+            metric._ctx[dev.index] = shared_before
+
+
+def _public_api(dev, rows, stream_cases, metric):
+    from speakerguard_amd import _native as N
+    from speakerguard_amd import synth
+    from speakerguard_amd.attack.Kenan import Kenan
+    from speakerguard_amd.attack.PGD import PGD
+    from speakerguard_amd.attack.SirenAttack import SirenAttack
+    from speakerguard_amd.defense.feature_level import FeCoDefense
+    from speakerguard_amd.defense.frequency_domain import LPF
+    from speakerguard_amd.defense.time_domain import AS
+    from speakerguard_amd.model.defended_model import defended_model
+    m = fresh_models(dev)
+    out, bigs = {}, []
+
+    def cut(B, T=T_XV, seed=3, tones=False):
+        host = synth.make_tone_waveforms(B + 2, T) if tones else synth.make_waveforms(B + 2, T, seed=seed)
+        big = torch.from_numpy(host).to(dev)
+        bigs.append((big, big.clone(), B))
+        return rows(big, B)
+
+    y2 = torch.tensor([1, 3], device=dev)
+    for name in ("xv", "an", "iv"):
+        x = cut(2, tones=name == "an")
+        out.update(named(name + ".decision", m[name].make_decision(x), ("dec", "scores")))
+        out.update(named(name + ".loss_grad", m[name].loss_grad(x, y2, ce()), ("dec", "scores", "loss", "grad")))
+    defended = defended_model(m["xv"], [(0, AS(3)), (0, LPF())])
+    x = cut(2)
+    out.update(named("defended.decision", defended.make_decision(x), ("dec", "scores")))
+    out.update(named("defended.loss_grad", defended.loss_grad(x, y2, ce())[:4], ("dec", "scores", "loss", "grad")))
+    # the step loop over 5 utterances in batches of 2: batches 2 and 3 start off the boundary whatever the first row does
+    x5 = cut(5, seed=5)
+    y5 = m["xv"].make_decision(x5)[0]
+    pgd = PGD(m["xv"], task="CSI", epsilon=0.002, step_size=0.0004, max_iter=2, batch_size=2, verbose=0)
+    pgd._device_route = lambda n_audios: None
+    adv, succ = pgd.attack(x5, y5)
+    out["pgd.adv"], out["pgd.success"] = adv, torch.tensor(succ)
+    # (the spectrum gate takes even lengths; 6406 samples put row 1 eight bytes off a boundary)
+    adv, succ = Kenan(m["xv"], max_iter=2, batch_size=2, verbose=0).attack(cut(3, T=6406, seed=6), y5[:3])
+    out["kenan.adv"], out["kenan.success"] = adv, torch.tensor(succ)
+    siren = SirenAttack(m["xv"], task="CSI", n_particles=3, max_epoch=1, max_iter=2, batch_size=2, verbose=0, seed=1)
+    adv, succ = siren.attack(cut(3, seed=7), y5[:3])
+    out["siren.adv"], out["siren.success"] = adv, torch.tensor(succ)
+    if stream_cases:
+        # the stream-K launches and their flag words; the paired k-means and its flag words (300 x 150: two CUs per instance)
+        x8 = torch.from_numpy(synth.make_waveforms(8, 48000, seed=8)).to(dev)
+        out.update(named("xv.streamk", m["xv"].loss_grad(x8, torch.arange(8, device=dev), ce()), ("dec", "scores", "loss", "grad")))
+        feco = defended_model(m["an"], [(1, FeCoDefense(0.5))])
+        xa = torch.from_numpy(synth.make_tone_waveforms(2, 48000)).to(dev)
+        out.update(named("an.feco", feco.loss_grad(xa, y2, ce())[:4], ("dec", "scores", "loss", "grad")))
+        # ... and the same pairing through the model's OWN context (the device loop): its buffers and their flag fill are
+        # created by this call
+        lo, hi = box(xa)
+        out.update(named("an.feco_loop", m["an"].pgd_run_feco(xa, y2, lo, hi, ce(), 0.0004, 2, 1, FeCoDefense(0.5), trace=True), LOOP_OUT))
+        # one workspace regrow (a second call at a larger B), one re-enrolment between two calls
+        x12 = torch.from_numpy(synth.make_waveforms(12, 48000, seed=9)).to(dev)
+        out.update(named("xv.regrow", m["xv"].make_decision(x12), ("dec", "scores")))
+        out.update(named("iv.before", m["iv"].make_decision(x12[:3, :, :T_XV].contiguous()), ("dec", "scores")))
+        rs = np.random.RandomState(4)
+        m["xv"].set_enroll(rs.randn(6, 200).astype(np.float32))
+        m["iv"].set_enroll(rs.randn(5, 10).astype(np.float32))
+        out.update(named("xv.reenrolled", m["xv"].make_decision(x12[:3]), ("dec", "scores")))
+        out.update(named("iv.reenrolled", m["iv"].make_decision(x12[:3, :, :T_XV].contiguous()), ("dec", "scores")))
+    torch.cuda.current_stream(dev).synchronize()
+    for model in m.values():
+        model.check_health()  # sg_health: clean
+    metric._context(dev).call("sg_health")  # ... and in the shared context, where the defenses and the gate ran
+    now = torch.cuda.current_stream(dev).cuda_stream
+    assert N.current_stream_ptr(dev).value == (now or None)
+    return {k: (None if v is None else v.detach().cpu().clone()) for k, v in out.items()}, bigs
+
+
+_PUBLIC = {}
+
+
+def public_reference(stream_cases):
+    """the cloned rows on the default stream: what both the sliced run and the side-stream run must equal; computed once"""
+    if stream_cases not in _PUBLIC:
+        torch.cuda.synchronize()
+        res, _, streams = public_api(ENV.dev, lambda big, B: big[1:1 + B].clone(), stream_cases)
+        assert streams == {torch.cuda.default_stream(ENV.dev).cuda_stream}, streams
+        _PUBLIC[stream_cases] = res
+    return _PUBLIC[stream_cases]
+
+
+def test_public_api_on_row_slices_of_an_odd_length_batch():
+    want = public_reference(False)
+    got, bigs, _ = public_api(ENV.dev, lambda big, B: big[1:1 + B], False)
+    assert any(big[1:1 + B].data_ptr() % 16 for big, _, B in bigs)
+    ok, why = cb.same(want, got, [])
+    log("caller_buffers %-34s k %-5s stream default  %s" % ("public API on big[1:1+B]", "slice", why if not ok else "bit-equal, batch unchanged"))
+    assert ok, why
+    for big, before, B in bigs:
+        assert cb.first_difference(before, big) is None, "an entry wrote to the caller's batch"
+
+
+def test_public_api_on_a_side_stream():
+    """one side stream, nothing concurrent: models, inputs and results are created inside the block, so the first-use setup
+    (build_tables and its flag fill, the paired k-means buffers of the AudioNet model's context and of the shared context,
+    workspace growth, the table caches) happens there; every call must name that stream"""
+    from speakerguard_amd import _native as N
+    want = public_reference(True)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert side.cuda_stream != 0 and N.current_stream_ptr(ENV.dev).value == side.cuda_stream
+        got, _, streams = public_api(ENV.dev, lambda big, B: big[1:1 + B].clone(), True)
+        side.synchronize()
+    assert streams == {side.cuda_stream}, "a call named another stream than the caller's: %s" % sorted(streams)
+    torch.cuda.synchronize()
+    ok, why = cb.same(want, got, [])
+    log("caller_buffers %-34s k %-5s stream side     %s" % ("public API + stream-K, paired k-means, regrow, re-enrol", "-", why if not ok else "bit-equal, sg_health clean"))
+    assert ok, why
