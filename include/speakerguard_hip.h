@@ -209,6 +209,26 @@ int sg_xv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
                     int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* grad_dev,
                     void* stream);
 
+/* Backward workspace of the LAST sg_xv_loss_grad call that asked for a gradient (debug / parity): copies one buffer to
+ * out_dev, laid out as that pass wrote it (its B and F, not the workspace's capacity), at most capacity_floats floats.
+ *   which                    buffer                                                 dims[0..3]
+ *   SG_GRAD_DEMB             d loss / d fc1 output                                  1, B, 1, 512
+ *   SG_GRAD_DACT1 + l - 1    d loss / d pre-activation of tdnn l = 1..5             1, B, F_l, C_l (C_5 padded to 1536)
+ *   SG_GRAD_DSTATS           the 8 split-K slabs of fc1's data gradient             8, B, 1, 3072
+ *   SG_GRAD_DFEATS           the 10 split-K slabs of tdnn1's data gradient          10, B, F, 32
+ *   SG_GRAD_DFEATS_RAW       d loss / d raw MFCC (a flag-0 pass only)               1, B, F, 30
+ * dims (4 host int32, may be NULL) is filled whether or not out_dev is NULL.  Read only: launches nothing but the copy.
+ * SG_ERR_STATE unless the context's last x-vector pass was such a call: a forward-only call, a device loop, a layer
+ * timing or a rebuilt workspace since leave these buffers stale.  SG_ERR_ARG for an unknown `which`, capacity <= 0 with
+ * out_dev, SG_GRAD_DFEATS_RAW after a feature-level pass. */
+#define SG_GRAD_DEMB 0
+#define SG_GRAD_DACT1 1
+#define SG_GRAD_DSTATS 6
+#define SG_GRAD_DFEATS 7
+#define SG_GRAD_DFEATS_RAW 8
+int sg_xv_debug_gradient(sg_ctx* ctx, int32_t which, float* out_dev, int64_t capacity_floats, int32_t* dims,
+                         void* stream);
+
 /* attack/FGSM.py:65,68: x += step*sign(grad)*grad_sign; x = min(max(x, lower), upper). In place. */
 int sg_pgd_update(sg_ctx* ctx, float* x_dev, const float* grad_dev, const float* lower_dev,
                   const float* upper_dev, int64_t n, float step_size, int32_t grad_sign, void* stream);

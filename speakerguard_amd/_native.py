@@ -36,7 +36,10 @@ EXPORTS = (
     "sg_iv_forward", "sg_iv_loss",
     "sg_iv_loss_grad", "sg_iv_extract_backward", "sg_iv_stats_backward", "sg_iv_delta_cmvn_backward",
     "sg_feco_kmeans_compress_wide",
+    "sg_xv_debug_gradient",
 )
+# `which` of sg_xv_debug_gradient (SG_GRAD_* of the header); "dact1" .. "dact5" = SG_GRAD_DACT1 + l - 1
+SG_GRAD = dict({"demb": 0, "dstats": 6, "dfeats": 7, "dfeats_raw": 8}, **{"dact%d" % l: l for l in range(1, 6)})
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
 STAGE_NAMES = {10: "mfcc_fwd", 11: "cmvn_fwd", 12: "pool_fwd", 13: "fc1_fwd", 14: "tail", 15: "fc1_bwd", 16: "pool_bwd",
@@ -187,6 +190,7 @@ def load():
         "sg_xv_debug_activation": (C.c_int, [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), vp]),
         "sg_xv_loss_grad": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither),
                                       vp, vp, vp, vp, vp]),
+        "sg_xv_debug_gradient": (C.c_int, [vp, i32, vp, i64, C.POINTER(i32), vp]),
         "sg_pgd_update": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, i32, vp]),
         "sg_loss_eval": (C.c_int, [vp, vp, vp, i32, i32, f32, C.POINTER(LossSpec), vp, vp, vp, vp]),
         "sg_xv_pgd_run": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),

@@ -351,6 +351,7 @@ int run_tdnn_backward(sg_ctx* ctx, const PassDims& d, hipStream_t s) {
 
 int check_dims(sg_ctx* ctx, int B, int TF, int flag, PassDims* d) {
     if (!ctx) return SG_ERR_ARG;
+    ctx->ws.grad_B = 0;  // a pass starts: the backward buffers of the last gradient call are no longer its own
     if (!ctx->xv.loaded) return fail(ctx, SG_ERR_STATE, "no x-vector model loaded (call sg_xv_load)");
     if (int h = sg_health(ctx)) return h;
     SG_HIP(hipSetDevice(ctx->device));
@@ -1165,6 +1166,40 @@ int sg_xv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
     if (grad_dev) {
         rc = run_backward_to_input(ctx, x_dev, d, flag, dither, grad_dev, nullptr, nullptr, nullptr, 0.f, 0, s);
         if (rc) return rc;
+        w.grad_B = d.B; w.grad_F = d.F; w.grad_flag = flag;  // what sg_xv_debug_gradient may read back
+    }
+    return SG_OK;
+}
+
+int sg_xv_debug_gradient(sg_ctx* ctx, int32_t which, float* out_dev, int64_t capacity_floats, int32_t* dims, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    const Workspace& w = ctx->ws;
+    if (!w.scale || w.grad_B < 1)
+        return fail(ctx, SG_ERR_STATE, "sg_xv_debug_gradient: the last x-vector pass on this context was not an sg_xv_loss_grad call with a gradient");
+    const int B = w.grad_B, F = w.grad_F;
+    int Fl[kLayers];
+    layer_frames(F, Fl);
+    const float* src = nullptr;
+    int slabs = 1, rows = 1, cols = 0;
+    if (which == SG_GRAD_DEMB) { src = w.demb; cols = kEmb; }
+    else if (which >= SG_GRAD_DACT1 && which < SG_GRAD_DACT1 + kLayers) {
+        const int l = which - SG_GRAD_DACT1;
+        src = w.dact[l]; rows = Fl[l]; cols = kCoutPad[l];
+    }
+    else if (which == SG_GRAD_DSTATS) { src = w.dstats_part; slabs = kFc1BwdSplitK; cols = kStats; }
+    else if (which == SG_GRAD_DFEATS) { src = w.dfeats; slabs = kL1BwdSplitK; rows = F; cols = kFeatPad; }
+    else if (which == SG_GRAD_DFEATS_RAW) {
+        if (w.grad_flag != SG_FLAG_WAV) return fail(ctx, SG_ERR_ARG, "sg_xv_debug_gradient: only a waveform pass writes d loss / d raw MFCC");
+        src = w.dfeats_raw; rows = F; cols = kCep;
+    }
+    else return fail(ctx, SG_ERR_ARG, "sg_xv_debug_gradient: unknown buffer %d", which);
+    if (dims) { dims[0] = slabs; dims[1] = B; dims[2] = rows; dims[3] = cols; }
+    if (out_dev) {
+        if (capacity_floats <= 0) return fail(ctx, SG_ERR_ARG, "capacity must be positive");
+        // the pass fits its workspace (B <= w.B, F <= w.F), and the slabs lie at the pass's stride: one contiguous run
+        const size_t n = std::min<size_t>((size_t)capacity_floats, (size_t)slabs * B * rows * cols);
+        SG_HIP(hipSetDevice(ctx->device));
+        SG_HIP(hipMemcpyAsync(out_dev, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return SG_OK;
 }
@@ -1370,6 +1405,7 @@ int sg_xv_time_layer(sg_ctx* ctx, int32_t layer, int32_t B, int32_t T, int32_t i
     if (!w.scale || B > w.B || F > w.F)
         return fail(ctx, SG_ERR_STATE, "run a forward pass with this (B, T) first so the activations are resident");
     hipStream_t s = (hipStream_t)stream;
+    w.grad_B = 0;  // the launches below overwrite an activation or a gradient of the last pass
     layer_frames(F, w.Fl);
     ConvGemmArgs a = fwd_layer_args(ctx, l, B, F);
     int tile = 0, epi = EPI_BIAS_RELU, splits = 1;

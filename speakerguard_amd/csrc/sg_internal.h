@@ -272,6 +272,9 @@ struct XvModel {
 struct Workspace {
     int B = 0, T = 0, F = 0;          // capacity the buffers were sized for
     int Fl[kLayers] = {};              // TDNN output frames per layer
+    // B, F and flag of the sg_xv_loss_grad backward whose buffers are still in place (sg_xv_debug_gradient); grad_B == 0:
+    // none -- cleared by every later pass (check_dims), by a layer timing and with the workspace itself
+    int grad_B = 0, grad_F = 0, grad_flag = -1;
     float* scale = nullptr;            // [1]
     float* feats_raw = nullptr;        // [B][F][30]
     float* feats = nullptr;            // [B][F][32] CMVN output, zero padded

@@ -128,6 +128,20 @@ class xv_plda(PldaModel):
         """ReLU output of TDNN layer 1..5 from the last pass, (B, F_l, C_l) channel-last (parity tests)."""
         return self.activation_shape(layer)
 
+    def read_gradient(self, what):
+        """A buffer of the last ``loss_grad`` call's backward (sg_xv_debug_gradient; parity tests), laid out as that pass
+        wrote it: 'demb' (B, 512), 'dact1' .. 'dact5' (B, F_l, C_l), 'dstats' (8, B, 3072) and 'dfeats' (10, B, F, 32) -- the
+        split-K slabs -- and, after a waveform pass, 'dfeats_raw' (B, F, 30).  Refused (NativeError) unless that call was the
+        last pass of this model."""
+        dims = (C.c_int32 * 4)()
+        self.ctx.call("sg_xv_debug_gradient", N.SG_GRAD[what], None, 0, dims, self._stream())
+        slabs, B, rows, cols = (int(v) for v in dims)
+        out = torch.empty(slabs, B, rows, cols, device=self.device, dtype=torch.float32)
+        self.ctx.call("sg_xv_debug_gradient", N.SG_GRAD[what], N._ptr(out), out.numel(), None, self._stream())
+        if what in ("demb", "dstats"):
+            out = out.view(slabs, B, cols)
+        return out[0] if slabs == 1 else out
+
     # ------------------------------------------------------------------ engine protocol used by attack.*
     def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):
         """make_decision + per-example loss + d loss / d x in one native call (replaces EOT.py:32-35).

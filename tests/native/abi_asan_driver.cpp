@@ -426,6 +426,10 @@ int main(int argc, char** argv) {
     EXPECT(sg_xv_set_enroll(ctx, xv.enroll.data(), S, -INFINITY) == SG_OK);
     EXPECT(sg_xv_enroll_override(ctx, enr2.data(), 2) == SG_OK && sg_xv_enroll_override(ctx, nullptr, 0) == SG_OK);
 
+    {
+        int32_t dm[4] = {-1, -1, -1, -1};
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, nullptr, 0, dm, nullptr) == SG_ERR_STATE && dm[0] == -1);  // no pass yet
+    }
     // shape validation of the pass entry points
     EXPECT(sg_xv_forward(ctx, x.data(), 0, T, 0, &nod, dec.data(), scores.data(), nullptr, nullptr, nullptr) != SG_OK);
     EXPECT(sg_xv_forward(ctx, x.data(), B, 100, 0, &nod, dec.data(), scores.data(), nullptr, nullptr, nullptr) != SG_OK);
@@ -444,6 +448,32 @@ int main(int argc, char** argv) {
     EXPECT(sg_xv_forward(ctx, feats.data(), B, F, 1, nullptr, dec.data(), scores.data(), nullptr, nullptr, nullptr) == SG_OK);
     EXPECT(sg_xv_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, &nod, dec.data(), scores.data(), loss.data(), grad.data(), nullptr) == SG_OK);
     EXPECT(sg_xv_loss_grad(ctx, feats.data(), y.data(), B, F, 2, &ce, nullptr, dec.data(), scores.data(), loss.data(), gfeat.data(), nullptr) == SG_OK);
+    {
+        // the backward workspace of that call, at the pass's own B and F (the workspace was sized by the waveform passes above)
+        int32_t dm[4] = {};
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DFEATS, nullptr, 0, dm, nullptr) == SG_OK && dm[0] == 10 && dm[1] == B && dm[2] == F && dm[3] == 32);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DSTATS, nullptr, 0, dm, nullptr) == SG_OK && dm[0] == 8 && dm[1] == B && dm[2] == 1 && dm[3] == 3072);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DACT1 + 4, nullptr, 0, dm, nullptr) == SG_OK && dm[0] == 1 && dm[2] == F - 30 && dm[3] == 1536);
+        // a capacity past what the pass wrote is clamped: exact-size destinations, so the sanitizer sees any overrun
+        std::vector<float> slabs((size_t)10 * B * F * 32), d5((size_t)B * (F - 30) * 1536), de((size_t)B * 512), few(7);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DFEATS, slabs.data(), (int64_t)1 << 40, nullptr, nullptr) == SG_OK);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DACT1 + 4, d5.data(), (int64_t)d5.size() + 1, nullptr, nullptr) == SG_OK);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, de.data(), (int64_t)1 << 40, dm, nullptr) == SG_OK && dm[3] == 512);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DSTATS, few.data(), (int64_t)few.size(), nullptr, nullptr) == SG_OK);  // a short one
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, de.data(), 0, nullptr, nullptr) == SG_ERR_ARG);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, de.data(), -5, nullptr, nullptr) == SG_ERR_ARG);
+        EXPECT(sg_xv_debug_gradient(ctx, 9, nullptr, 0, dm, nullptr) == SG_ERR_ARG && sg_xv_debug_gradient(ctx, -1, nullptr, 0, dm, nullptr) == SG_ERR_ARG);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DFEATS_RAW, nullptr, 0, dm, nullptr) == SG_ERR_ARG);  // a feature-level pass wrote none
+        EXPECT(sg_xv_debug_gradient(nullptr, SG_GRAD_DEMB, nullptr, 0, dm, nullptr) != SG_OK);
+        // a forward-only pass since: act[] is the new pass's, dact[] the old one's -- refused, both forms of forward-only
+        EXPECT(sg_xv_forward(ctx, feats.data(), B, F, 1, nullptr, dec.data(), scores.data(), nullptr, nullptr, nullptr) == SG_OK);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, de.data(), (int64_t)de.size(), dm, nullptr) == SG_ERR_STATE);
+        EXPECT(sg_xv_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, &nod, dec.data(), scores.data(), loss.data(), grad.data(), nullptr) == SG_OK);
+        std::vector<float> raw((size_t)B * F * 30);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DFEATS_RAW, raw.data(), (int64_t)raw.size() + 9, dm, nullptr) == SG_OK && dm[2] == F && dm[3] == 30);
+        EXPECT(sg_xv_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, &nod, dec.data(), scores.data(), loss.data(), nullptr, nullptr) == SG_OK);
+        EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, de.data(), (int64_t)de.size(), dm, nullptr) == SG_ERR_STATE);
+    }
     EXPECT(sg_xv_loss_grad(ctx, x.data(), nullptr, B, T, 0, &ce, &nod, dec.data(), scores.data(), loss.data(), grad.data(), nullptr) != SG_OK);
     // round 6: the same pass on the float64 transforms (the launch selection of both instantiations runs under the sanitizer)
     EXPECT(sg_xv_configure(ctx, 64) == SG_OK);
@@ -480,6 +510,7 @@ int main(int argc, char** argv) {
     int32_t tags[16];
     float ms[16];
     EXPECT(sg_trace_end(ctx, tags, ms, 16, &n_rec) == SG_OK && n_rec == 16);  // more launches than records: capped, no overrun
+    EXPECT(sg_xv_debug_gradient(ctx, SG_GRAD_DEMB, nullptr, 0, nullptr, nullptr) == SG_ERR_STATE);  // a device loop is no single pass
     EXPECT(sg_trace_begin(ctx, 4096) == SG_OK);
     setenv("SG_EOT_MAX_ROWS", "6", 1);  // two groups of two repeats: the per-step records collect rows over the groups
     EXPECT(sg_xv_pgd_run(ctx, x.data(), y.data(), lower.data(), upper.data(), B, T, &pp, succ.data(), dec.data(), scores.data(), loss.data(),

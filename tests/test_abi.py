@@ -104,6 +104,16 @@ def test_struct_layouts_match_header(tmp_path):
     assert ctypes.sizeof(_native.LossSpec) == 32 and ctypes.sizeof(_native.Dither) == 48
 
 
+def test_gradient_buffer_ids_match_the_header():
+    """``_native.SG_GRAD`` (the names ``xv_plda.read_gradient`` takes) against the SG_GRAD_* of sg_xv_debug_gradient"""
+    ids = {k: int(v) for k, v in re.findall(r"#define\s+SG_GRAD_(\w+)\s+(\d+)", header_text())}
+    assert ids == {"DEMB": 0, "DACT1": 1, "DSTATS": 6, "DFEATS": 7, "DFEATS_RAW": 8}
+    want = {"demb": ids["DEMB"], "dstats": ids["DSTATS"], "dfeats": ids["DFEATS"], "dfeats_raw": ids["DFEATS_RAW"]}
+    want.update({"dact%d" % l: ids["DACT1"] + l - 1 for l in range(1, 6)})
+    assert _native.SG_GRAD == want
+    assert "sg_xv_debug_gradient" in _native.EXPORTS and declared("sg_xv_debug_gradient")[1][-2:] == ["int32_t*", "void*"]
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     monkeypatch.setattr(_native, "_lib", None)
     monkeypatch.setattr(_native, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -21,9 +21,10 @@ The grid is chosen from the launcher's branch points at 256 CUs (launch_conv_gem
 layers, and 16 x 16 (B = 1), plain tiles (2), kind 7 (4), kind 6 (8) and kind 5 (>= 16) on N = 1536; plus ragged and long
 utterances.  Every output element of every case is compared.
 
-NOT pinned bitwise by this module, judged end to end only (tests/test_gpu_truth.py): tdnn1's data gradient (split-K per
-tap into slabs the CMVN backward sums) and fc1 backward (split-K into slabs the pooling backward sums).  Pinning them needs
-a readback of the backward workspace, which the C-ABI does not offer.
+The backward half in situ -- tdnn1's data gradient (split-K per tap into slabs the CMVN backward sums), fc1 backward
+(split-K into slabs the pooling backward sums), the data gradients as the step launches them, pooling's backward, the CMVN
+adjoint and the tail's gradient -- is pinned stage by stage in tests/test_gpu_backward_stages.py, on a readback of the
+backward workspace (sg_xv_debug_gradient).
 """
 import numpy as np
 import pytest
