@@ -41,7 +41,7 @@ ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefi
 ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 DRIVERS    := abi_asan_driver defended_asan_driver an_defended_asan_driver xv_feco_asan_driver feco_cos_asan_driver \
               ds_asan_driver spectrum_asan_driver ssa_asan_driver stoi_asan_driver pso_asan_driver iv_asan_driver iv_grad_asan_driver \
-              feco_wide_asan_driver
+              feco_wide_asan_driver ragged_asan_driver
 ASAN_EXES  := $(addprefix $(ASAN_DIR)/,$(DRIVERS))
 
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(HDRS)
@@ -61,12 +61,13 @@ $(ASAN_DIR)/fatbin_syms.o: $(ASAN_OBJS)
 $(ASAN_EXES): %: %.o $(ASAN_OBJS) $(ASAN_DIR)/hip_host_double.o $(ASAN_DIR)/fatbin_syms.o
 	/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o $@ $^
 
-# (the xv-feco driver prints its launch sequence on stdout: tests/test_xv_feco_launch_sequence.py reads it, this run drops it)
+# (the xv-feco and the ragged driver print their launch sequences on stdout: tests/test_xv_feco_launch_sequence.py and
+# tests/test_ragged_launch_sequence.py read them, this run drops them)
 ASAN_RUN   := ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1
 asan: $(ASAN_EXES)
 	@set -e; for d in $(ASAN_EXES); do \
 	    echo $$d; \
-	    case $$d in *xv_feco*) $(ASAN_RUN) $$d > /dev/null;; *) $(ASAN_RUN) $$d;; esac; \
+	    case $$d in *xv_feco*|*ragged*) $(ASAN_RUN) $$d > /dev/null;; *) $(ASAN_RUN) $$d;; esac; \
 	done
 
 clean:

@@ -337,6 +337,36 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
                   uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
                   float* loss_trace_dev, int64_t* decision_trace_dev, void* stream);
 
+/* ---- batches of unequal lengths (waveform level, flag 0) ----------------------------------------
+ * x (B,T_max) is a padded batch: utterance b is x[b, :lengths[b]], the rest of the row is padding whose content does not
+ * matter.  Row b of every output is, bit for bit, what the uniform entry point gives for utterance b alone at its own
+ * length: reflection at lengths[b], CMVN and statistics pooling over the utterance's own frames (each on the branch that
+ * length takes alone), dither keyed by utterance, frame and sample.  grad (B,T_max) is 0 in the padding and the loop never
+ * moves a padding sample.  Buffers keep the row strides of T_max; a pass costs what a uniform batch of T_max costs in the
+ * TDNN and less in the front-end.  The range decision (x32768 or not) is taken once per batch, padding included, as the
+ * uniform entry points take it.
+ * lengths come twice: lengths_dev (B) int32 is what the kernels read, lengths_host (B) int32 the caller's host copy of the same
+ * numbers, which is validated before any launch or allocation -- so no entry point waits for the device.  SG_ERR_ARG when
+ * either is NULL, a length exceeds T_max, is shorter than one 25 ms window (400) or has too few frames for the TDNN context
+ * (what the uniform entry point refuses), when no length equals T_max, or with an explicit dither tensor (noise_dev).  A
+ * device copy that differs from the host copy cannot make a kernel leave its row (counts are clamped to [400, T_max]), but
+ * the results are then undefined.
+ * sg_xv_debug_activation / sg_xv_debug_gradient after such a pass report the padded dims (F of T_max); rows beyond an
+ * utterance's own frames hold zeros in every gradient buffer and unspecified values in the activations.
+ * sg_xv_pgd_run_ragged: sg_xv_pgd_run with lengths of the B utterances; the EOT repeats of a pass share them. */
+int sg_xv_forward_ragged(sg_ctx* ctx, const float* x_dev, const int32_t* lengths_dev, const int32_t* lengths_host,
+                         int32_t B, int32_t T_max, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev,
+                         float* emb_dev, float* tdnn_emb_dev, void* stream);
+int sg_xv_loss_grad_ragged(sg_ctx* ctx, const float* x_dev, const int32_t* lengths_dev, const int32_t* lengths_host,
+                           const int64_t* y_dev, int32_t B, int32_t T_max, const sg_loss_spec* loss,
+                           const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* loss_dev,
+                           float* grad_dev, void* stream);
+int sg_xv_pgd_run_ragged(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev,
+                         const float* upper_dev, const int32_t* lengths_dev, const int32_t* lengths_host, int32_t B,
+                         int32_t T_max, const sg_pgd_params* params, uint8_t* success_dev, int64_t* decisions_dev,
+                         float* scores_dev, float* loss_dev, float* loss_trace_dev, int64_t* decision_trace_dev,
+                         void* stream);
+
 /* ---- AudioNet CSI-NE model (model/audionet_csine.py) ----------------------------------------
  * log-mel(32) front-end (model/_audionet/Preprocessor.py:85-112) -> 5x5 pre-filter -> seven
  * Conv1d/BatchNorm/ReLU(/MaxPool) blocks -> max over time -> Linear(32, num_class).  Input levels:

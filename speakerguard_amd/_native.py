@@ -37,6 +37,7 @@ EXPORTS = (
     "sg_iv_loss_grad", "sg_iv_extract_backward", "sg_iv_stats_backward", "sg_iv_delta_cmvn_backward",
     "sg_feco_kmeans_compress_wide",
     "sg_xv_debug_gradient",
+    "sg_xv_forward_ragged", "sg_xv_loss_grad_ragged", "sg_xv_pgd_run_ragged",
 )
 # `which` of sg_xv_debug_gradient (SG_GRAD_* of the header); "dact1" .. "dact5" = SG_GRAD_DACT1 + l - 1
 SG_GRAD = dict({"demb": 0, "dstats": 6, "dfeats": 7, "dfeats_raw": 8}, **{"dact%d" % l: l for l in range(1, 6)})
@@ -191,6 +192,10 @@ def load():
         "sg_xv_loss_grad": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither),
                                       vp, vp, vp, vp, vp]),
         "sg_xv_debug_gradient": (C.c_int, [vp, i32, vp, i64, C.POINTER(i32), vp]),
+        "sg_xv_forward_ragged": (C.c_int, [vp, vp, vp, vp, i32, i32, C.POINTER(Dither), vp, vp, vp, vp, vp]),
+        "sg_xv_loss_grad_ragged": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(LossSpec), C.POINTER(Dither),
+                                             vp, vp, vp, vp, vp]),
+        "sg_xv_pgd_run_ragged": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),
         "sg_pgd_update": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, i32, vp]),
         "sg_loss_eval": (C.c_int, [vp, vp, vp, i32, i32, f32, C.POINTER(LossSpec), vp, vp, vp, vp]),
         "sg_xv_pgd_run": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),

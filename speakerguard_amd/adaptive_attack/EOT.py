@@ -17,7 +17,9 @@ class EOT:
         self.EOT_num_batches = self.EOT_size // self.EOT_batch_size
         self.use_grad = use_grad
 
-    def forward(self, x_batch, y_batch, EOT_num_batches=None, EOT_batch_size=None, use_grad=None):
+    def forward(self, x_batch, y_batch, EOT_num_batches=None, EOT_batch_size=None, use_grad=None, lengths=None):
+        """`lengths` (n,) int32: x_batch is a padded batch of unequal lengths; repeated with the rows and handed to the model's
+        ``loss_grad`` as the keyword ``lengths`` (a call without lengths is made exactly as before)."""
         EOT_num_batches = EOT_num_batches if EOT_num_batches else self.EOT_num_batches
         EOT_batch_size = EOT_batch_size if EOT_batch_size else self.EOT_batch_size
         use_grad = use_grad if use_grad else self.use_grad  # (sic) same truthiness rule as EOT.py:19
@@ -29,12 +31,13 @@ class EOT:
         base = getattr(self.model, 'base_model', self.model)
         keyed = hasattr(base, 'row_keys')  # the engine keys its noise by (utterance, repeat), not by the row of the call
         y_rep = self._labels(y_batch, EOT_batch_size)
+        ragged = {} if lengths is None else {'lengths': self._lengths(lengths, EOT_batch_size)}
         for EOT_index in range(EOT_num_batches):
             x_rep = x_batch.repeat(EOT_batch_size, 1, 1)
             if keyed:
                 base._rep_rows = n_audios if EOT_batch_size > 1 else 0
             try:
-                dec, sc, ls, g = self.model.loss_grad(x_rep, y_rep, self.loss, want_grad=bool(use_grad))
+                dec, sc, ls, g = self.model.loss_grad(x_rep, y_rep, self.loss, want_grad=bool(use_grad), **ragged)
             finally:
                 if keyed:
                     base._rep_rows = 0
@@ -61,6 +64,14 @@ class EOT:
         c = self._y_rep
         if c is None or c[0] is not y_batch or c[1] != y_batch._version or c[2] != reps:
             c = self._y_rep = (y_batch, y_batch._version, reps, y_batch.repeat(reps))
+        return c[3]
+
+    _len_rep = None  # (lengths, their version, repeats, the repeated tensor): the model uploads a lengths tensor once, too
+
+    def _lengths(self, lengths, reps):
+        c = self._len_rep
+        if c is None or c[0] is not lengths or c[1] != lengths._version or c[2] != reps:
+            c = self._len_rep = (lengths, lengths._version, reps, lengths.repeat(reps))
         return c[3]
 
     __call__ = forward

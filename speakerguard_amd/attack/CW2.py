@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .FGSM import FGSM
-from .utils import SEC4SR_MarginLoss
+from .utils import SEC4SR_MarginLoss, refuse_lengths
 
 
 class CW2(FGSM):
@@ -118,5 +118,6 @@ class CW2(FGSM):
         """The examples of a chunk share the early-stop test (their mean loss) and nothing else."""
         return 'mean' if self.stop_early else None
 
-    def attack(self, x, y):
+    def attack(self, x, y, lengths=None):
+        refuse_lengths(self, lengths)
         return super().attack(x, y)

@@ -20,7 +20,7 @@ import torch
 from ..adaptive_attack.EOT import EOT
 from ..adaptive_attack.NES import NES
 from .Attack import Attack
-from .utils import resolve_loss
+from .utils import resolve_loss, refuse_lengths
 
 
 class FAKEBOB(Attack):
@@ -135,7 +135,8 @@ class FAKEBOB(Attack):
         success = [bl < 0 for bl in best_loss]
         return best_adver_x, success
 
-    def attack(self, x, y):
+    def attack(self, x, y, lengths=None):
+        refuse_lengths(self, lengths)
         if self.task in ['SV', 'OSI'] and self.threshold is None:
             raise NotImplementedError('You are running black box attack for {} task, '
                                       'but the threshold not specified. Consider calling estimate threshold'.format(self.task))

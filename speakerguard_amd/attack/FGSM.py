@@ -129,6 +129,7 @@ class FGSM(Attack):
         return route if isinstance(route, _Route) else _Route(*route)
 
     def _attack_batch_fused(self, x_batch, y_batch, lower, upper, batch_id, name, extra, **kwargs):
+        # (kwargs: the route's own keywords and, for a padded batch of unequal lengths, ``lengths`` -- never passed when None)
         base = getattr(self.model, 'base_model', self.model)
         x_adv, success, dec, scores, loss, ltr, dtr = getattr(base, name)(
             x_batch, y_batch, lower, upper, self.loss, self.step_size, self.max_iter, self.grad_sign, *extra,
@@ -141,10 +142,14 @@ class FGSM(Attack):
         return x_adv, [bool(v) for v in success.tolist()]  # (one device round trip, no conversion launch)
 
     # ---- step-by-step loop (FGSM.py:38-70) ---------------------------------------------------
-    def attack_batch(self, x_batch, y_batch, lower, upper, batch_id):
+    def attack_batch(self, x_batch, y_batch, lower, upper, batch_id, lengths=None):
+        """`lengths` (n,) int32: the chunk is a padded batch of unequal lengths, its longest utterance filling the row; bounds
+        and start point are already 0 in the padding (``_mask_padding``).  It goes to ``pgd_run`` / ``loss_grad`` as the
+        keyword ``lengths`` -- a call without lengths is made exactly as before."""
+        ragged = {} if lengths is None else {'lengths': lengths}
         route = self._device_route(x_batch.shape[0])
         if route is not None:
-            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, *route, **getattr(route, 'kwargs', {}))
+            return self._attack_batch_fused(x_batch, y_batch, lower, upper, batch_id, *route, **getattr(route, 'kwargs', {}), **ragged)
         x_batch = x_batch.clone()
         lower = lower.expand_as(x_batch).contiguous()
         upper = upper.expand_as(x_batch).contiguous()
@@ -154,7 +159,7 @@ class FGSM(Attack):
             EOT_num_batches = int(self.EOT_size // self.EOT_batch_size) if it < self.max_iter else 1
             real_EOT_batch_size = self.EOT_batch_size if it < self.max_iter else 1
             use_grad = it < self.max_iter
-            scores, loss, grad, decisions = self.EOT_wrapper(x_batch, y_batch, EOT_num_batches, real_EOT_batch_size, use_grad)
+            scores, loss, grad, decisions = self.EOT_wrapper(x_batch, y_batch, EOT_num_batches, real_EOT_batch_size, use_grad, **ragged)
             loss = loss / EOT_num_batches
             predict = resolve_prediction(decisions)
             target = y_batch.detach().cpu().numpy()
@@ -180,8 +185,10 @@ class FGSM(Attack):
         if hasattr(base, 'begin_batch'):
             base.begin_batch(self.index_offset + start, 0 if tag is None else int(tag) + 1)
 
-    def _run_batches(self, x, y, lower, upper, tag=None):
+    def _run_batches(self, x, y, lower, upper, tag=None, lengths=None):
         base = getattr(self.model, 'base_model', self.model)
+        if lengths is not None:  # (no stream-K retry around a padded batch: kept to the one path the tests pin)
+            return self._run_batches_once(x, y, lower, upper, tag, lengths)
         try:
             return self._run_batches_once(x, y, lower, upper, tag)
         except Exception as e:  # the engine's NativeError (kept generic: the CPU test double has no such class)
@@ -196,7 +203,9 @@ class FGSM(Attack):
             base.set_streamk(False)
             return self._run_batches_once(x, y, lower, upper, tag)
 
-    def _run_batches_once(self, x, y, lower, upper, tag=None):
+    def _run_batches_once(self, x, y, lower, upper, tag=None, lengths=None):
+        """`lengths`: sliced with the batch.  A chunk is cut to ITS longest utterance (the engine wants the longest to fill the
+        row, and shorter rows cost less) and its result is zero-padded back to the width of x."""
         n_audios = x.shape[0]
         batch_size = min(self.batch_size, n_audios)
         n_batches = int(np.ceil(n_audios / float(batch_size)))
@@ -205,7 +214,12 @@ class FGSM(Attack):
             sl = slice(batch_id * batch_size, (batch_id + 1) * batch_size)
             bid = batch_id if tag is None else '{}-{}'.format(tag, batch_id)
             self._begin_batch(sl.start, tag)
-            a, s = self.attack_batch(x[sl], y[sl], lower[sl], upper[sl], bid)
+            if lengths is not None:
+                T = int(lengths[sl].max())
+                a, s = self.attack_batch(x[sl, :, :T], y[sl], lower[sl, :, :T], upper[sl, :, :T], bid, lengths=lengths[sl])
+                a = torch.nn.functional.pad(a, (0, x.shape[2] - T))
+            else:
+                a, s = self.attack_batch(x[sl], y[sl], lower[sl], upper[sl], bid)
             adver.append(a)
             success += s
         # the success flags are on the host, so every launch of these batches has finished: a kernel that flagged
@@ -223,9 +237,43 @@ class FGSM(Attack):
         assert n_channels == 1, 'Only Support Mono Audio'
         assert y.shape[0] == n_audios, 'The number of x and y should be equal'
 
-    def attack(self, x, y):
+    # ---- padded batches of unequal lengths ---------------------------------------------------
+    def _check_lengths(self, x, lengths):
+        """What ``attack(x, y, lengths=)`` refuses before anything runs: a model that cannot take lengths -- by name, so that
+        nobody attacks padding unawares -- and lengths that do not describe x.  -> lengths as a host int32 tensor."""
+        m = self.model
+        if getattr(m, 'defense', None) is not None:
+            raise ValueError("%s with a defense in place does not take lengths=: the defenses handle batches of one length only"
+                             % type(m).__name__)
+        base = getattr(m, 'base_model', m)
+        if not getattr(base, 'takes_lengths', False):
+            raise ValueError("%s does not take lengths=: it handles batches of one length only" % type(base).__name__)
+        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],):
+            raise ValueError("lengths must be an int32 tensor of shape (%d,), one sample count per row of x" % x.shape[0])
+        lengths = lengths.detach().cpu()
+        if int(lengths.min()) < 1 or int(lengths.max()) > x.shape[2]:
+            raise ValueError("lengths must lie in 1 .. %d, the width of x" % x.shape[2])
+        return lengths
+
+    @staticmethod
+    def _mask_padding(lengths, *tensors):
+        """every (B, 1, T) tensor with zeros behind its rows' own samples: start point, bounds, random-init noise"""
+        T = tensors[0].shape[2]
+        keep = (torch.arange(T).unsqueeze(0) < lengths.to(torch.int64).unsqueeze(1)).unsqueeze(1).to(tensors[0].device)
+        out = tuple(torch.where(keep, t, torch.zeros((), dtype=t.dtype, device=t.device)) for t in tensors)
+        return out if len(out) > 1 else out[0]
+
+    def attack(self, x, y, lengths=None):
+        """`lengths` (B,) int32: x is a padded batch of utterances of unequal lengths (``audio_io.pad_batch``).  Every utterance
+        is attacked as it would be alone at its own length; the returned audio is 0 in the padding whatever x held there."""
+        if lengths is not None:
+            lengths = self._check_lengths(x, lengths)
+            x = self._mask_padding(lengths, x)
         self._check_inputs(x, y)
         self._begin_attack()
         lower = torch.tensor(-1, device=x.device, dtype=x.dtype).expand_as(x)
         upper = torch.tensor(1, device=x.device, dtype=x.dtype).expand_as(x)
+        if lengths is not None:
+            lower, upper = self._mask_padding(lengths, lower, upper)
+            return self._run_batches(x, y, lower, upper, lengths=lengths)
         return self._run_batches(x, y, lower, upper)

@@ -14,6 +14,7 @@ Faithfulness notes:
   * ``atk_name='ssa'`` is a class of its own, ``speakerguard_amd.attack.KenanSSA.KenanSSA`` (int16 audio, a native
     decomposition per utterance, a native reconstruction per query); asked for here it is a NotImplementedError that says so.
 """
+from .utils import refuse_lengths
 import numpy as np
 import torch
 
@@ -129,7 +130,8 @@ class Kenan(object):
         self._records.append((last, factors, decisions))
         return adv, success
 
-    def attack(self, x, y, fs=16_000):
+    def attack(self, x, y, fs=16_000, lengths=None):
+        refuse_lengths(self, lengths)
         n_audios, n_channels, _ = x.size()
         assert n_channels == 1, 'Only Support Mono Audio'
         assert y.shape[0] == n_audios, 'The number of x and y should be equal'

@@ -18,6 +18,7 @@ Faithfulness notes:
     A ``batch_coupled`` model gets chunks of one.  The chunk is capped so that the native workspace (about 3 W^2 float64 per
     utterance) stays below ``workspace_limit`` bytes.
 """
+from .utils import refuse_lengths
 import ctypes as C
 
 import numpy as np
@@ -170,7 +171,8 @@ class KenanSSA(object):
         size = 1 if bool(getattr(self.model, "batch_coupled", False)) else self.batch_size
         return max(1, min(size, n_audios, fit))
 
-    def attack(self, x, y, fs=16_000):
+    def attack(self, x, y, fs=16_000, lengths=None):
+        refuse_lengths(self, lengths)
         n_audios, n_channels, T = x.size()
         assert n_channels == 1, 'Only Support Mono Audio'
         assert y.shape[0] == n_audios, 'The number of x and y should be equal'

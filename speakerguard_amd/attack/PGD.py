@@ -22,11 +22,19 @@ class PGD(FGSM):
         self.batch_size = batch_size
         self._init_common(EOT_size, EOT_batch_size, verbose)
 
-    def attack(self, x, y):
+    def attack(self, x, y, lengths=None):
+        """`lengths`: as in ``FGSM.attack`` -- bounds, start point and the restarts' noise are 0 in the padding."""
+        ragged = {}
+        if lengths is not None:
+            lengths = self._check_lengths(x, lengths)
+            x = self._mask_padding(lengths, x)
+            ragged = {'lengths': lengths}
         self._check_inputs(x, y)
         self._begin_attack()
         upper = torch.clamp(x + self.epsilon, max=1)   # PGD.py:48-49
         lower = torch.clamp(x - self.epsilon, min=-1)
+        if lengths is not None:
+            lower, upper = self._mask_padding(lengths, lower, upper)
         x_ori = x.clone() if self.num_random_init > 0 else x  # only the restarts overwrite x (PGD.py:58-61)
         best_success_rate = -1
         best_success = None
@@ -35,7 +43,9 @@ class PGD(FGSM):
             if self.num_random_init > 0:  # host RNG, same call as PGD.py:60
                 x = x_ori + torch.tensor(np.random.uniform(-self.epsilon, self.epsilon, tuple(x_ori.shape)),
                                          device=x.device, dtype=x.dtype)
-            adver_x, success = self._run_batches(x, y, lower, upper, tag=init)
+                if lengths is not None:
+                    x = self._mask_padding(lengths, x)
+            adver_x, success = self._run_batches(x, y, lower, upper, tag=init, **ragged)
             if sum(success) / len(success) > best_success_rate:   # whole-batch criterion, PGD.py:74-77
                 best_success_rate = sum(success) / len(success)
                 best_success = success

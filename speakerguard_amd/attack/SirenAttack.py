@@ -26,7 +26,7 @@ import torch
 from ..adaptive_attack.EOT import EOT
 from ..model._engine_ops import mix64
 from .Attack import Attack
-from .utils import resolve_loss, resolve_prediction
+from .utils import resolve_loss, resolve_prediction, refuse_lengths
 
 MAX_CHUNK, MAX_PARTICLES = 256, 1024  # kPsoMaxRows / kPsoMaxParticles of csrc/k_pso.hip
 SEED_TAG = 0x5349524E  # 'SIRN': the key domain of the swarm's draws (EngineOps.noise_seed)
@@ -232,7 +232,8 @@ class SirenAttack(Attack):
             self.loss_record.append(losses)
         return st.gbest_loc.view(n_audios, n_channels, N) + x_batch, success
 
-    def attack(self, x, y):
+    def attack(self, x, y, lengths=None):
+        refuse_lengths(self, lengths)
         if self.task in ['SV', 'OSI'] and self.threshold is None:
             raise NotImplementedError('You are running black box attack for {} task, '
                                       'but the threshold not specified. Consider Estimating the threshold by FAKEBOB!'.format(self.task))

@@ -182,3 +182,11 @@ def resolve_loss(loss_name='Entropy', targeted=False, confidence=0., task='CSI',
 def resolve_prediction(decisions):
     """Majority vote over the EOT decisions of each example, first-seen wins ties (:118-125)."""
     return np.array([Counter(d).most_common(1)[0][0] for d in decisions])
+
+
+def refuse_lengths(attack, lengths):
+    """``attack(x, y, lengths=...)`` on an attack that handles batches of one length only: refused by name (padded batches
+    of unequal lengths are FGSM / PGD / CWinf on the x-vector model), never run on the padding."""
+    if lengths is not None:
+        raise ValueError("%s does not take lengths=: it attacks batches of one length only (crop, or attack the utterances one "
+                         "at a time)" % type(attack).__name__)

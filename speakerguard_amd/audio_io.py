@@ -13,6 +13,27 @@ from . import _native as N
 from .metric.metric import _context
 
 
+def pad_batch(waves):
+    """Utterances of unequal lengths as one batch: a list of (1, T_b) or (T_b,) tensors -> (x, lengths), x (B, 1, T_max)
+    zero-padded on the right (dtype and device of the first utterance) and lengths (B,) int32 sample counts on the host.
+    The pair is what ``xv_plda.make_decision / score / forward / loss_grad / pgd_run`` and ``FGSM / PGD / CWinf.attack`` take
+    as ``(x, lengths=lengths)``: row b is then treated as utterance b alone at its own length."""
+    waves = list(waves)
+    if not waves:
+        raise ValueError("pad_batch needs at least one utterance")
+    flat = []
+    for i, w in enumerate(waves):
+        if not torch.is_tensor(w) or w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != 1) or w.shape[-1] < 1:
+            raise ValueError("utterance %d: expected a (1, T) or (T,) tensor, got %s" % (
+                i, tuple(w.shape) if torch.is_tensor(w) else type(w).__name__))
+        flat.append(w.reshape(-1))
+    lengths = torch.tensor([w.shape[0] for w in flat], dtype=torch.int32)
+    x = torch.zeros(len(flat), 1, int(lengths.max()), dtype=flat[0].dtype, device=flat[0].device)
+    for b, w in enumerate(flat):
+        x[b, 0, :w.shape[0]] = w.to(x.device, x.dtype)
+    return x, lengths
+
+
 def quantize_pcm(advers):
     """(N,1,T) or (N,T) float tensor -> (N,T) int16 CPU numpy array, reference save_audio rounding."""
     a = advers.detach().to(torch.float32)

@@ -116,6 +116,26 @@ __device__ __forceinline__ void load_frame(const float* __restrict__ x, int T, i
     }
 }
 
+// The same for a batch of unequal lengths (RowLens, sg_internal.h): row stride T, the right edge reflected at the row's own
+// sample count.  A frame beyond the row's own (padding: its result is never used) reads the row's last frame, so every index
+// stays inside the utterance.  gf is wave-uniform: the count is one scalar load.
+__device__ __forceinline__ void load_frame_ragged(const float* __restrict__ x, int T, int F, const int32_t* __restrict__ lens, int nlen,
+                                                  int gf, int total, int lane, float (&raw)[7], int rep_utts) {
+    const int g = gf < total ? gf : total - 1;
+    const int row = g / F;
+    const int b = rep_utts > 0 ? row % rep_utts : row;
+    const int Tb = row_samples(lens, nlen, row, T), Fb = num_frames(Tb);
+    const int f = min(g - row * F, Fb - 1);
+    const int base = f * kShift - (kWin / 2 - kShift / 2);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const int n = lane + 64 * i;
+        const int p = base + (n < kWin ? n : kWin - 1);
+        const int idx = p < 0 ? -p - 1 : (p >= Tb ? 2 * Tb - 1 - p : p);
+        raw[i] = x[(size_t)b * T + idx];
+    }
+}
+
 // An offset the compiler cannot see through (always 0): table reads addressed with it are re-issued per frame instead of
 // being hoisted out of the frame loop into 30-60 registers per lane.
 __device__ __forceinline__ int opaque_zero() {
@@ -266,6 +286,43 @@ __global__ __launch_bounds__(MfccCfg<R>::kWaves * 64, MfccCfg<R>::kMinBlocks) vo
     }
 }
 
+// The forward for a batch of unequal lengths: T, F are the row strides (the longest utterance's), row r has lens[r % nlen]
+// samples.  Its own frames are computed as mfcc_fwd_kernel computes them for an utterance of that length alone; the rows behind
+// them are written as zeros (the workspace is reused: nothing stale may stand there), and cost no transform.
+template <typename R, int DZ>
+__global__ __launch_bounds__(MfccCfg<R>::kWaves * 64, MfccCfg<R>::kMinBlocks) void mfcc_fwd_ragged_kernel(MfccTables t, const float* __restrict__ x, int B, int T, int F,
+                                                                          const int32_t* __restrict__ lens, int nlen,
+                                                                          const float* __restrict__ scale_p, sg_dither dz,
+                                                                          float* __restrict__ feats) {
+    constexpr int kWaves = MfccCfg<R>::kWaves;
+    __shared__ FrameLdsT<R> lds[kWaves];
+    __shared__ TabLdsT<R> tb;
+    stage_tables<R>(t, tb);
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: the counts load as scalars)
+    const float scale = scale_p ? *scale_p : 1.f;
+    FrameLdsT<R>& L = lds[wid];
+    const int total = B * F, stride = gridDim.x * kWaves;
+    float raw[7], nxt[7];
+    load_frame_ragged(x, T, F, lens, nlen, blockIdx.x * kWaves + wid, total, lane, nxt, t.rep_utts);
+    for (int gf = blockIdx.x * kWaves + wid; gf < total; gf += stride) {
+        const int b = gf / F, f = gf - b * F;
+        const int tz = opaque_zero();
+#pragma unroll
+        for (int i = 0; i < 7; ++i) raw[i] = nxt[i];
+        load_frame_ragged(x, T, F, lens, nlen, gf + stride, total, lane, nxt, t.rep_utts);
+        if (f >= num_frames(row_samples(lens, nlen, b, T))) {
+            if (lane < kCep) feats[((size_t)b * F + f) * kCep + lane] = 0.f;
+            continue;
+        }
+        FrameState st;
+        float cep;
+        cx<R> Xk[4];
+        frame_forward<R, 0, DZ>(t, tb, tz, L, raw, F, b, f, scale, dz, lane, st, cep, Xk);
+        if (lane < kCep) feats[((size_t)b * F + f) * kCep + lane] = cep;
+        wave_sync();
+    }
+}
+
 // dfeats: (B,F,ld) gradient wrt the 30 cepstra; dframes: (B,F,400) gradient wrt the strided frames,
 // already multiplied by `scale` (the int16 rescale of check_input_range, model/utils.py:14).
 // CACHED: the forward kernel of the same pass left spectrum + mel energies in t.spec_cache / t.mel_cache (the attack
@@ -303,73 +360,48 @@ __global__ __launch_bounds__(MfccCfg<R>::kWaves * 64, CACHED ? MfccCfg<R>::kMinB
 #pragma unroll
         for (int i = 0; i < 7; ++i) raw[i] = nxt[i];
         load_frame(x, T, F, gf + stride, total, lane, nxt, t.rep_utts);
-        FrameState st;
-        float cep;
-        cx<R> Xk[4];
-        frame_forward<R, CACHED ? 1 : 0, DZ>(t, tb, tz, L, raw, F, b, f, scale, dz, lane, st, cep, Xk);
-        // ---- cepstra -> log-mel
-        float dc = 0.f;
-        if (lane < kCep) dc = dfeats[((size_t)b * F + f) * ld + lane];
-        const float denergy = __shfl(dc, 0, 64);
-        if (lane < 32) L.tmp[lane] = (lane == 0 || lane >= kCep) ? 0.f : dc * tb.lifter[lane];
+#define SG_MFCC_BODY 1  // (the frame of the adjoint)
+#include "k_mfcc_bodies.h"
         wave_sync();
-        if (lane < 32) {
-            float dm = 0.f;
-            if (lane < kMel) {
-                float dl = 0.f;
+    }
+}
+
+// The adjoint for a batch of unequal lengths (see mfcc_fwd_ragged_kernel): a row's own frames as mfcc_bwd_kernel treats them,
+// nothing for the rows behind them -- the overlap-add of such a batch reads no frame beyond a row's own.
+template <typename R, bool CACHED, int DZ>
+__global__ __launch_bounds__(MfccCfg<R>::kWaves * 64, CACHED ? MfccCfg<R>::kMinBlocks : 1) void mfcc_bwd_ragged_kernel(MfccTables t, const float* __restrict__ x, int B, int T, int F,
+                                                                          const int32_t* __restrict__ lens, int nlen,
+                                                                          const float* __restrict__ scale_p, sg_dither dz,
+                                                                          const float* __restrict__ dfeats, int ld,
+                                                                          float* __restrict__ dframes) {
+    constexpr int kWaves = MfccCfg<R>::kWaves;
+    __shared__ FrameLdsT<R> lds[kWaves];
+    __shared__ TabLdsT<R> tb;
+    stage_tables<R>(t, tb);
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float scale = scale_p ? *scale_p : 1.f;
+    FrameLdsT<R>& L = lds[wid];
+    const int kb = (lane >> 3) + 8 * (lane & 7);
+    int bin_m0[4];
+    float bin_w0[4], bin_w1[4];
 #pragma unroll
-                for (int c = 0; c < kCep; ++c) dl = __builtin_fmaf(L.tmp[c], tb.dct_t[tz + c * 32 + lane], dl);
-                const float mel = L.mel[lane];
-                dm = mel > kEps ? dl / mel : 0.f;
-            }
-            L.lmel[lane] = dm;  // d loss / d mel energy (entries 30,31 = 0)
-        }
-        wave_sync();
-        // ---- mel -> power -> spectrum gradient G[k] = 2 X[k] dP[k] at this lane's bins, in transform order -- the layout the
-        //      TRANSPOSED inverse network takes (d >= 4: bins 256..511, zero); it returns samples lane + 64 j in registers.
-        cx<R> v[8];
+    for (int d = 0; d < 4; ++d) {
+        bin_m0[d] = t.bin_m0[kb + 64 * d];
+        bin_w0[d] = t.bin_w0[kb + 64 * d];
+        bin_w1[d] = t.bin_w1[kb + 64 * d];
+    }
+    const int total = B * F, stride = gridDim.x * kWaves;
+    float raw[7], nxt[7];
+    load_frame_ragged(x, T, F, lens, nlen, blockIdx.x * kWaves + wid, total, lane, nxt, t.rep_utts);
+    for (int gf = blockIdx.x * kWaves + wid; gf < total; gf += stride) {
+        const int b = gf / F, f = gf - b * F;
+        const int tz = opaque_zero();
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            v[d] = cmk<R>((R)0, (R)0);
-            const int m0 = bin_m0[d];
-            if (m0 >= 0) {
-                const R dp = (R)(2.f * __builtin_fmaf(L.lmel[m0], bin_w0[d], L.lmel[m0 + 1] * bin_w1[d]));
-                v[d] = cmk<R>(Xk[d].x * dp, Xk[d].y * dp);
-            }
-        }
-#pragma unroll
-        for (int d = 4; d < 8; ++d) v[d] = cmk<R>((R)0, (R)0);
-        fft512T_transposed<R>(L.spec, tb.tw1c() + tz, tb.tw2c() + tz, lane, (R)1, v);
-        // ---- window, pre-emphasis (sample n + 1 is the right neighbour lane's, lane 63: lane 0's next register), energy,
-        //      DC removal
-        float sw[8];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) sw[i] = (float)v[i].x * tb.window[tz + lane + 64 * i];
-        sw[7] = 0.f;
-        float ds[7];
-        float sum = 0.f;
-        const float einv = st.energy > kEps ? 2.f * denergy / st.energy : 0.f;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const int n = lane + 64 * i;
-            const float edge = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sw[i + 1]), 0));
-            const float next = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, sw[i]),
-                                                                                      0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-            float g = 0.f;
-            if (n < kWin) {
-                g = sw[i] - 0.97f * next;  // (sample 400 does not exist: its sw is 0)
-                if (n == 0) g -= 0.97f * sw[0];
-                g = __builtin_fmaf(einv, st.s[i], g);
-            }
-            ds[i] = g;
-            sum += g;
-        }
-        const float mean = wave_sum_rows(sum) / (float)kWin;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const int n = lane + 64 * i;
-            if (n < kWin) dframes[((size_t)b * F + f) * kWin + n] = (ds[i] - mean) * scale;
-        }
+        for (int i = 0; i < 7; ++i) raw[i] = nxt[i];
+        load_frame_ragged(x, T, F, lens, nlen, gf + stride, total, lane, nxt, t.rep_utts);
+        if (f >= num_frames(row_samples(lens, nlen, b, T))) continue;
+#define SG_MFCC_BODY 1
+#include "k_mfcc_bodies.h"
         wave_sync();
     }
 }
@@ -383,151 +415,115 @@ __global__ __launch_bounds__(256) void frames_to_wave_kernel(const float* __rest
                                                              const float* acc_in, float* grad_out, float* __restrict__ x_io,
                                                              const float* __restrict__ lower,
                                                              const float* __restrict__ upper, float step, int grad_sign) {
-    // acc_in (may alias grad_out): gradient accumulated over the earlier EOT repeats of this step (EOT.py:41-47)
-    // V = 4: a thread owns four consecutive samples n0 .. n0 + 3 (n0 a multiple of 4; host: T % 4 == 0).  Away from the
-    // reflected edges the four share their frames (frame shift and window are multiples of 4), so every gather is one aligned
-    // 16-byte load and the per-sample sums keep their order; a thread whose samples touch an edge takes them one by one.
-    const int n0 = (blockIdx.x * 256 + threadIdx.x) * V;
-    const int b = blockIdx.y;
-    if (n0 >= T) return;
-    constexpr int kPad = kWin / 2 - kShift / 2;
-    const int last_q = (F - 1) * kShift - kPad + kWin - 1;  // the largest original position a frame covers
-    const size_t o = (size_t)b * T + n0;
-    float total[V];
-    const bool interior = V == 4 && n0 >= kPad && 2 * T - 1 - (n0 + 3) > last_q && n0 + 3 < T;
-    // dframes (R, B, F, 400): R batched EOT repeats of the B utterances; their gradients are summed in repeat order,
-    // exactly as R sequential passes handing the sum on through acc_in did (EOT.py:41-47)
-    if (interior) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const int q = n0 + kPad;
-        int fhi = q / kShift;
-        const int flo = q > kWin - 1 ? (q - (kWin - 1) + kShift - 1) / kShift : 0;
-        if (fhi > F - 1) fhi = F - 1;
-        f4 tot = {0.f, 0.f, 0.f, 0.f};
-        for (int r = 0; r < R; ++r) {
-            const float* df = dframes + ((size_t)r * B + b) * F * kWin;
-            f4 g = {0.f, 0.f, 0.f, 0.f};
-            for (int f = flo; f <= fhi; ++f) g += *reinterpret_cast<const f4*>(df + (size_t)f * kWin + (q - f * kShift));
-            if (r == 0) tot = acc_in ? *reinterpret_cast<const f4*>(acc_in + o) + g : g;
-            else tot = tot + g;
-        }
-        total[0] = tot.x;
-        if (V == 4) { total[1] = tot.y; total[2] = tot.z; total[3] = tot.w; }
-    } else {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int n = n0 + v;
-            total[v] = 0.f;
-            if (n >= T) continue;
-            const int pr = 2 * T - 1 - n;
-            for (int r = 0; r < R; ++r) {
-                const float* df = dframes + ((size_t)r * B + b) * F * kWin;
-                float g = 0.f;
-                auto add_pos = [&](int p) {
-                    const int q = p + kPad;  // position in the padded signal, >= 0
-                    int fhi = q / kShift;
-                    int flo = q > kWin - 1 ? (q - (kWin - 1) + kShift - 1) / kShift : 0;
-                    if (fhi > F - 1) fhi = F - 1;
-                    for (int f = flo; f <= fhi; ++f) g += df[(size_t)f * kWin + (q - f * kShift)];
-                };
-                add_pos(n);
-                if (n < kPad) add_pos(-n - 1);
-                if (pr <= last_q) add_pos(pr);
-                if (r == 0) total[v] = acc_in ? acc_in[o + v] + g : g;
-                else total[v] = total[v] + g;
-            }
-        }
-    }
-    if (V == 4 && n0 + 3 < T) {  // (T % 4 == 0: always, for V = 4) the update as 16-byte accesses
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        if (grad_out) *reinterpret_cast<f4*>(grad_out + o) = f4{total[0], total[V > 1 ? 1 : 0], total[V > 2 ? 2 : 0], total[V > 3 ? 3 : 0]};
-        if (x_io) {
-            const f4 xv = *reinterpret_cast<const f4*>(x_io + o), lo = *reinterpret_cast<const f4*>(lower + o),
-                     hi = *reinterpret_cast<const f4*>(upper + o);
-            f4 res;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const float g = total[v < V ? v : 0];
-                const float sg = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
-                res[v] = fminf(fmaxf(xv[v] + step * sg * (float)grad_sign, lo[v]), hi[v]);
-            }
-            *reinterpret_cast<f4*>(x_io + o) = res;
-        }
-        return;
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        if (n0 + v >= T) break;
-        const float g = total[v];
-        if (grad_out) grad_out[o + v] = g;
-        if (x_io) {
-            const float sg = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
-            float val = x_io[o + v] + step * sg * (float)grad_sign;
-            val = fminf(fmaxf(val, lower[o + v]), upper[o + v]);
-            x_io[o + v] = val;
-        }
-    }
+#define SG_MFCC_BODY 2  // (the samples of a thread; a uniform batch: rows as long as the utterances)
+#define SG_OLA_TLD T
+#define SG_OLA_FLD F
+#include "k_mfcc_bodies.h"
+#undef SG_OLA_TLD
+#undef SG_OLA_FLD
 }
 
+// A batch of unequal lengths: utterance b has lens[b] samples in rows of Tld (dframes: of Fld frames).  Its own samples are gathered,
+// and stepped, as frames_to_wave_kernel does it for an utterance of that length alone -- every bound from the row's own counts, so a
+// V = 4 thread whose quad straddles the row's end takes its samples one by one; the samples behind get the gradient 0 and no step.
+template <int V>
+__global__ __launch_bounds__(256) void frames_to_wave_ragged_kernel(const float* __restrict__ dframes, int B, int Tld, int Fld,
+                                                                    const int32_t* __restrict__ lens, int R, const float* acc_in,
+                                                                    float* grad_out, float* __restrict__ x_io,
+                                                                    const float* __restrict__ lower,
+                                                                    const float* __restrict__ upper, float step, int grad_sign) {
+    // (the gradient behind the row's own samples first; the shared text below returns early for a thread that owns none)
+    const int T = row_samples(lens, B, blockIdx.y, Tld), F = num_frames(T);
+    if (grad_out) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int n = (blockIdx.x * 256 + threadIdx.x) * V + v;
+            if (n >= T && n < Tld) grad_out[(size_t)blockIdx.y * Tld + n] = 0.f;
+        }
+    }
+#define SG_MFCC_BODY 2
+#define SG_OLA_TLD Tld
+#define SG_OLA_FLD Fld
+#include "k_mfcc_bodies.h"
+#undef SG_OLA_TLD
+#undef SG_OLA_FLD
+}
+
+// rl.dev: a batch of unequal lengths takes the *_ragged kernels, same grids (an explicit noise tensor: refused by the entry points)
 template <typename R>
 static void mfcc_fwd_launch(const MfccTables& t, const float* x, int B, int T, int F, const float* scale, const sg_dither& d,
-                            float* feats, hipStream_t s) {
+                            float* feats, const RowLens& rl, hipStream_t s) {
     constexpr int kWaves = MfccCfg<R>::kWaves;
     const int want = (B * F + kWaves - 1) / kWaves;
     dim3 grid(want < kMfccMaxBlocks ? want : kMfccMaxBlocks);
-    if (d.noise_dev) hipLaunchKernelGGL((mfcc_fwd_kernel<R, 2>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, scale, d, feats);
+    if (rl.dev) {
+        if (d.dither != 0.f) hipLaunchKernelGGL((mfcc_fwd_ragged_kernel<R, 1>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, rl.dev, rl.n, scale, d, feats);
+        else hipLaunchKernelGGL((mfcc_fwd_ragged_kernel<R, 0>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, rl.dev, rl.n, scale, d, feats);
+    }
+    else if (d.noise_dev) hipLaunchKernelGGL((mfcc_fwd_kernel<R, 2>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, scale, d, feats);
     else if (d.dither != 0.f) hipLaunchKernelGGL((mfcc_fwd_kernel<R, 1>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, scale, d, feats);
     else hipLaunchKernelGGL((mfcc_fwd_kernel<R, 0>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, scale, d, feats);
 }
 
 template <typename R>
 static void mfcc_bwd_launch(const MfccTables& t, const float* x, int B, int T, int F, const float* scale, const sg_dither& d,
-                            const float* dfeats, float* dframes, hipStream_t s) {
+                            const float* dfeats, float* dframes, const RowLens& rl, hipStream_t s) {
     constexpr int kWaves = MfccCfg<R>::kWaves;
     const int want = (B * F + kWaves - 1) / kWaves;
     dim3 grid(want < kMfccMaxBlocks ? want : kMfccMaxBlocks);
 #define SG_MFCC_BWD(CACHED, DZ) \
     hipLaunchKernelGGL((mfcc_bwd_kernel<R, CACHED, DZ>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, scale, d, dfeats, kCep, dframes)
+#define SG_MFCC_BWD_RAGGED(CACHED, DZ) \
+    hipLaunchKernelGGL((mfcc_bwd_ragged_kernel<R, CACHED, DZ>), grid, dim3(kWaves * 64), 0, s, t, x, B, T, F, rl.dev, rl.n, scale, d, dfeats, kCep, dframes)
     const int dzk = d.noise_dev ? 2 : (d.dither != 0.f ? 1 : 0);
-    if (t.spec_cache) {
+    if (rl.dev) {
+        if (t.spec_cache) { if (dzk == 1) SG_MFCC_BWD_RAGGED(true, 1); else SG_MFCC_BWD_RAGGED(true, 0); }
+        else { if (dzk == 1) SG_MFCC_BWD_RAGGED(false, 1); else SG_MFCC_BWD_RAGGED(false, 0); }
+    } else if (t.spec_cache) {
         if (dzk == 2) SG_MFCC_BWD(true, 2); else if (dzk == 1) SG_MFCC_BWD(true, 1); else SG_MFCC_BWD(true, 0);
     } else {
         if (dzk == 2) SG_MFCC_BWD(false, 2); else if (dzk == 1) SG_MFCC_BWD(false, 1); else SG_MFCC_BWD(false, 0);
     }
 #undef SG_MFCC_BWD
+#undef SG_MFCC_BWD_RAGGED
 }
 
 hipError_t launch_mfcc_fwd(const MfccTables& t, const float* x, int B, int T, int F, const float* scale,
-                           const sg_dither* dz, float* feats, hipStream_t s) {
+                           const sg_dither* dz, float* feats, hipStream_t s, const RowLens& rl) {
     sg_dither d = dz ? *dz : sg_dither{0.f, 0, 0, nullptr};
-    if (t.fft64) mfcc_fwd_launch<double>(t, x, B, T, F, scale, d, feats, s);
-    else mfcc_fwd_launch<float>(t, x, B, T, F, scale, d, feats, s);
+    if (t.fft64) mfcc_fwd_launch<double>(t, x, B, T, F, scale, d, feats, rl, s);
+    else mfcc_fwd_launch<float>(t, x, B, T, F, scale, d, feats, rl, s);
     return hipGetLastError();
 }
 
 hipError_t launch_mfcc_bwd(const MfccTables& t, const float* x, int B, int T, int F, const float* scale,
-                           const sg_dither* dz, const float* dfeats, float* dframes, hipStream_t s) {
+                           const sg_dither* dz, const float* dfeats, float* dframes, hipStream_t s, const RowLens& rl) {
     sg_dither d = dz ? *dz : sg_dither{0.f, 0, 0, nullptr};
-    if (t.fft64) mfcc_bwd_launch<double>(t, x, B, T, F, scale, d, dfeats, dframes, s);
-    else mfcc_bwd_launch<float>(t, x, B, T, F, scale, d, dfeats, dframes, s);
+    if (t.fft64) mfcc_bwd_launch<double>(t, x, B, T, F, scale, d, dfeats, dframes, rl, s);
+    else mfcc_bwd_launch<float>(t, x, B, T, F, scale, d, dfeats, dframes, rl, s);
     return hipGetLastError();
 }
 
 hipError_t launch_frames_to_wave(const float* dframes, int B, int T, int F, int R, const float* acc_in, float* grad_out,
                                  float* x_io, const float* lower, const float* upper, float step, int grad_sign,
-                                 hipStream_t s) {
+                                 hipStream_t s, const RowLens& rl) {
     // four samples per thread once the launch is bandwidth-bound (19.4 -> ~12 us at 64 utterances); small batches are
     // latency-bound and keep one sample per thread (5.1 us at 8 utterances against 6.5)
     // (T % 4 and 16-byte aligned bases: every row of the caller-owned buffers is read / written as 16-byte vectors)
     const uintptr_t bases = reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x_io) |
                             reinterpret_cast<uintptr_t>(lower) | reinterpret_cast<uintptr_t>(upper) |
                             reinterpret_cast<uintptr_t>(acc_in) | reinterpret_cast<uintptr_t>(dframes);
-    if (T % 4 == 0 && bases % 16 == 0 && (long)B * T >= 16L * 48000) {
-        dim3 grid((T / 4 + 255) / 256, B);
+    const bool quads = T % 4 == 0 && bases % 16 == 0 && (long)B * T >= 16L * 48000;
+    dim3 grid(((quads ? T / 4 : T) + 255) / 256, B);
+    if (rl.dev) {  // unequal lengths (rl.n == B utterances): the same choice, made on the padded batch
+        if (quads) hipLaunchKernelGGL(frames_to_wave_ragged_kernel<4>, grid, dim3(256), 0, s, dframes, B, T, F, rl.dev, R, acc_in, grad_out, x_io,
+                                      lower, upper, step, grad_sign);
+        else hipLaunchKernelGGL(frames_to_wave_ragged_kernel<1>, grid, dim3(256), 0, s, dframes, B, T, F, rl.dev, R, acc_in, grad_out, x_io, lower,
+                                upper, step, grad_sign);
+    } else if (quads) {
         hipLaunchKernelGGL(frames_to_wave_kernel<4>, grid, dim3(256), 0, s, dframes, B, T, F, R, acc_in, grad_out, x_io, lower, upper,
                            step, grad_sign);
     } else {
-        dim3 grid((T + 255) / 256, B);
         hipLaunchKernelGGL(frames_to_wave_kernel<1>, grid, dim3(256), 0, s, dframes, B, T, F, R, acc_in, grad_out, x_io, lower, upper,
                            step, grad_sign);
     }

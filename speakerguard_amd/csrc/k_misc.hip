@@ -183,59 +183,21 @@ __global__ __launch_bounds__(kCmvnThreads) void cmvn_fwd_kernel(const float* __r
     const int b = blockIdx.x;
     const float* x = in + (size_t)b * F * ld_in;
     float* y = out + (size_t)b * F * ld_out;
-    __shared__ double total[kCep];
-    __shared__ double part[kCmvnParts][32];
-    if (F <= kCmnWindow) {
-        // every window is the whole utterance: one column sum per cepstrum, 32 row-strided partial sums per column
-        // combined in a fixed order.  Thread (column d, row class r) keeps its <= 10 values (rows r, r + 32, ...) in
-        // registers -- loaded in one batch of independent, clamped loads -- and writes the same elements back: one global
-        // round trip and two barriers, where the first version read the utterance twice (9.1 -> see profiles/).
-        constexpr int kRows = (kCmnWindow + kCmvnParts - 1) / kCmvnParts;
-        const int d = threadIdx.x & 31, r = threadIdx.x >> 5;
-        float v[kRows];
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) {
-            const int t = min(r + j * kCmvnParts, F - 1);
-            v[j] = d < kCep ? x[(size_t)t * ld_in + d] : 0.f;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < kRows; ++j)
-            if (r + j * kCmvnParts < F) acc += (double)v[j];
-        part[r][d] = acc;
-        __syncthreads();
-        if (threadIdx.x < kCep) {
-            double a2 = 0.0;
-            for (int rr = 0; rr < kCmvnParts; ++rr) a2 += part[rr][threadIdx.x];
-            total[threadIdx.x] = a2;
-        }
-        __syncthreads();
-        const float mean = d < kCep ? (float)(total[d] / (double)F) : 0.f;
-        if (d < ld_out) {
-#pragma unroll
-            for (int j = 0; j < kRows; ++j) {
-                const int t = r + j * kCmvnParts;
-                if (t < F) y[(size_t)t * ld_out + d] = d < kCep ? v[j] - mean : 0.f;
-            }
-        }
-        for (int i = threadIdx.x; i < F * (ld_out - 32); i += kCmvnThreads) {  // (row stride above 32: the rest of the zero padding)
-            const int t = i / (ld_out - 32), dd = 32 + i - t * (ld_out - 32);
-            y[(size_t)t * ld_out + dd] = 0.f;
-        }
-    } else {
-        for (int i = threadIdx.x; i < F * ld_out; i += kCmvnThreads) {
-            const int t = i / ld_out, d = i - t * ld_out;
-            float v = 0.f;
-            if (d < kCep) {
-                int s, e;
-                cmvn_window(t, F, s, e);
-                double acc = 0.0;
-                for (int u = s; u < e; ++u) acc += (double)x[(size_t)u * ld_in + d];
-                v = x[(size_t)t * ld_in + d] - (float)(acc / (double)(e - s));
-            }
-            y[i] = v;
-        }
-    }
+#define SG_MISC_BODY 1
+#include "k_misc_bodies.h"
+}
+
+// A batch of unequal lengths (RowLens, sg_internal.h): rows Fld frames apart, row b normalised over its own F frames -- window,
+// mean and the branch on kCmnWindow as for that utterance alone; the rows behind them are written as zeros, all ld_out columns.
+__global__ __launch_bounds__(kCmvnThreads) void cmvn_fwd_ragged_kernel(const float* __restrict__ in, int ld_in, float* __restrict__ out,
+                                                              int ld_out, int Fld, const int32_t* __restrict__ lens, int nlen, int T) {
+    const int b = blockIdx.x;
+    const int F = num_frames(row_samples(lens, nlen, b, T));
+    const float* x = in + (size_t)b * Fld * ld_in;
+    float* y = out + (size_t)b * Fld * ld_out;
+#define SG_MISC_BODY 1
+#include "k_misc_bodies.h"
+    for (int i = F * ld_out + threadIdx.x; i < Fld * ld_out; i += kCmvnThreads) y[i] = 0.f;
 }
 
 // d_in[u] = d_out[u] - sum_{t : u in window(t)} d_out[t] / |window(t)|
@@ -249,77 +211,39 @@ __global__ __launch_bounds__(kCmvnThreads) void cmvn_bwd_kernel(const float* __r
     const int b = blockIdx.x;
     const float* g = dout + (size_t)b * F * ld_dout;
     float* y = din + (size_t)b * F * ld_din;
-    const int nsplit = NS > 0 ? NS : nsplit_rt;
-    auto gsum = [&](int t, int d) __attribute__((always_inline)) {
-        const float* src = g + (size_t)t * ld_dout + d;
-        if (NS > 0) {
-            float part[NS > 0 ? NS : 1];
-#pragma unroll
-            for (int z = 0; z < NS; ++z) part[z] = src[(size_t)z * slab_stride];
-            float v = 0.f;
-#pragma unroll
-            for (int z = 0; z < NS; ++z) v += part[z];
-            return v;
-        }
-        float v = 0.f;
-#pragma unroll 5
-        for (int z = 0; z < nsplit; ++z) v += src[(size_t)z * slab_stride];
-        return v;
-    };
-    __shared__ double total[kCep];
-    __shared__ double part[kCmvnParts][32];
-    if (F <= kCmnWindow) {
-        // thread (column d, row class r): the slab sums of its <= 10 rows stay in registers (kRows x nsplit independent
-        // loads, slabs added in order), the column means come from the same row-strided partial sums as before
-        constexpr int kRows = (kCmnWindow + kCmvnParts - 1) / kCmvnParts;
-        const int d = threadIdx.x & 31, r = threadIdx.x >> 5;
-        float v[kRows];
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) {
-            const int t = min(r + j * kCmvnParts, F - 1);
-            v[j] = d < kCep ? gsum(t, d) : 0.f;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < kRows; ++j)
-            if (r + j * kCmvnParts < F) acc += (double)v[j];
-        part[r][d] = acc;
-        __syncthreads();
-        if (threadIdx.x < kCep) {
-            double a2 = 0.0;
-            for (int rr = 0; rr < kCmvnParts; ++rr) a2 += part[rr][threadIdx.x];
-            total[threadIdx.x] = a2 / (double)F;
-        }
-        __syncthreads();
-        if (d < kCep) {
-            const float mean = (float)total[d];
-#pragma unroll
-            for (int j = 0; j < kRows; ++j) {
-                const int t = r + j * kCmvnParts;
-                if (t < F) y[(size_t)t * ld_din + d] = v[j] - mean;
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < F * kCep; i += kCmvnThreads) {
-            const int u = i / kCep, d = i - u * kCep;
-            double acc = 0.0;
-            for (int t = 0; t < F; ++t) {
-                int s, e;
-                cmvn_window(t, F, s, e);
-                if (u >= s && u < e) acc += (double)gsum(t, d) / (double)(e - s);
-            }
-            y[(size_t)u * ld_din + d] = gsum(u, d) - (float)acc;
-        }
-    }
+#define SG_MISC_BODY 2
+#include "k_misc_bodies.h"
 }
 
-hipError_t launch_cmvn_fwd(const float* in, int ld_in, float* out, int ld_out, int B, int F, hipStream_t s) {
-    hipLaunchKernelGGL(cmvn_fwd_kernel, dim3(B), dim3(kCmvnThreads), 0, s, in, ld_in, out, ld_out, F);
+// ... of a batch of unequal lengths (cmvn_fwd_ragged_kernel): row b over its own F frames, +0 behind them
+template <int NS>
+__global__ __launch_bounds__(kCmvnThreads) void cmvn_bwd_ragged_kernel(const float* __restrict__ dout, int ld_dout, int nsplit_rt,
+                                                              long long slab_stride, float* __restrict__ din, int ld_din, int Fld,
+                                                              const int32_t* __restrict__ lens, int nlen, int T) {
+    const int b = blockIdx.x;
+    const int F = num_frames(row_samples(lens, nlen, b, T));
+    const float* g = dout + (size_t)b * Fld * ld_dout;
+    float* y = din + (size_t)b * Fld * ld_din;
+#define SG_MISC_BODY 2
+#include "k_misc_bodies.h"
+    for (int i = F * ld_din + threadIdx.x; i < Fld * ld_din; i += kCmvnThreads) y[i] = 0.f;
+}
+
+// rl.dev: a batch of unequal lengths, T its row stride in samples (F = num_frames(T))
+hipError_t launch_cmvn_fwd(const float* in, int ld_in, float* out, int ld_out, int B, int F, hipStream_t s, const RowLens& rl, int T) {
+    if (rl.dev) hipLaunchKernelGGL(cmvn_fwd_ragged_kernel, dim3(B), dim3(kCmvnThreads), 0, s, in, ld_in, out, ld_out, F, rl.dev, rl.n, T);
+    else hipLaunchKernelGGL(cmvn_fwd_kernel, dim3(B), dim3(kCmvnThreads), 0, s, in, ld_in, out, ld_out, F);
     return hipGetLastError();
 }
 hipError_t launch_cmvn_bwd(const float* dout, int ld_dout, int nsplit, long long slab_stride, float* din, int ld_din,
-                           int B, int F, hipStream_t s) {
-    if (nsplit == kL1BwdSplitK)
+                           int B, int F, hipStream_t s, const RowLens& rl, int T) {
+    if (rl.dev && nsplit == kL1BwdSplitK)
+        hipLaunchKernelGGL(cmvn_bwd_ragged_kernel<kL1BwdSplitK>, dim3(B), dim3(kCmvnThreads), 0, s, dout, ld_dout, nsplit, slab_stride, din,
+                           ld_din, F, rl.dev, rl.n, T);
+    else if (rl.dev)
+        hipLaunchKernelGGL(cmvn_bwd_ragged_kernel<0>, dim3(B), dim3(kCmvnThreads), 0, s, dout, ld_dout, nsplit, slab_stride, din, ld_din, F,
+                           rl.dev, rl.n, T);
+    else if (nsplit == kL1BwdSplitK)
         hipLaunchKernelGGL(cmvn_bwd_kernel<kL1BwdSplitK>, dim3(B), dim3(kCmvnThreads), 0, s, dout, ld_dout, nsplit, slab_stride, din, ld_din, F);
     else
         hipLaunchKernelGGL(cmvn_bwd_kernel<0>, dim3(B), dim3(kCmvnThreads), 0, s, dout, ld_dout, nsplit, slab_stride, din, ld_din, F);
@@ -334,47 +258,21 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
     const int c = blockIdx.x * 64 + lane;
     const int b = blockIdx.y;
     const float* a = act + (size_t)b * Tc * kPoolC + c;
-    __shared__ float red[4][64];
-    // two-pass variance (like torch.std); the <= 96 frames a wave owns stay in registers between the
-    // passes so the activation tensor is read once (longer utterances re-read from L2)
-    constexpr int kKeep = 96;
-    float keep[kKeep];
-    const bool fits = Tc <= 4 * kKeep;
-    float s = 0.f;
-    if (fits) {
-#pragma unroll
-        for (int i = 0; i < kKeep; ++i) {
-            const int t = wid + 4 * i;
-            keep[i] = t < Tc ? a[(size_t)t * kPoolC] : 0.f;
-            s += keep[i];
-        }
-    } else {
-        for (int t = wid; t < Tc; t += 4) s += a[(size_t)t * kPoolC];
-    }
-    red[wid][lane] = s;
-    __syncthreads();
-    const float mean = (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (float)Tc;
-    __syncthreads();
-    float q = 0.f;
-    if (fits) {
-#pragma unroll
-        for (int i = 0; i < kKeep; ++i) {
-            const float d = keep[i] - mean;
-            q += (wid + 4 * i < Tc) ? d * d : 0.f;
-        }
-    } else {
-        for (int t = wid; t < Tc; t += 4) {
-            const float d = a[(size_t)t * kPoolC] - mean;
-            q += d * d;
-        }
-    }
-    red[wid][lane] = q;
-    __syncthreads();
-    if (wid == 0) {
-        const float var = (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (float)(Tc - 1);
-        stats[(size_t)b * kStats + c] = mean;
-        stats[(size_t)b * kStats + kPoolC + c] = sqrtf(var);
-    }
+#define SG_MISC_BODY 3
+#include "k_misc_bodies.h"
+}
+
+// A batch of unequal lengths (RowLens, sg_internal.h): rows Tld frames apart, row b pooled over its own Tc frames, kTdnnContext
+// fewer than its MFCC has -- the sums in the order, and on the branch, of that utterance alone.
+__global__ __launch_bounds__(256) void pool_fwd_ragged_kernel(const float* __restrict__ act, int Tld, float* __restrict__ stats,
+                                                              const int32_t* __restrict__ lens, int nlen, int T) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int Tc = min(num_frames(row_samples(lens, nlen, b, T)) - kTdnnContext, Tld);
+    const float* a = act + (size_t)b * Tld * kPoolC + c;
+#define SG_MISC_BODY 3
+#include "k_misc_bodies.h"
 }
 
 // d act[t][c] = relu'(act) * ( dmean[c]/T + dstd[c] * (act - mean) / ((T-1) * std) ), std == 0 -> no std term
@@ -387,29 +285,8 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const int b = blockIdx.y;
-    float dmean = 0.f, dstd = 0.f;
-    if (NS > 0) {
-        float pm[NS > 0 ? NS : 1], ps[NS > 0 ? NS : 1];
-#pragma unroll
-        for (int z = 0; z < NS; ++z) {
-            pm[z] = dpart[((size_t)z * B + b) * kStats + c];
-            ps[z] = dpart[((size_t)z * B + b) * kStats + kPoolC + c];
-        }
-#pragma unroll
-        for (int z = 0; z < NS; ++z) {
-            dmean += pm[z];
-            dstd += ps[z];
-        }
-    } else {
-        for (int z = 0; z < nsplit; ++z) {
-            dmean += dpart[((size_t)z * B + b) * kStats + c];
-            dstd += dpart[((size_t)z * B + b) * kStats + kPoolC + c];
-        }
-    }
-    const float mean = stats[(size_t)b * kStats + c];
-    const float sd = stats[(size_t)b * kStats + kPoolC + c];
-    const float beta = sd > 0.f ? dstd / ((float)(Tc - 1) * sd) : 0.f;
-    const float alpha = dmean / (float)Tc;
+#define SG_MISC_BODY 4
+#include "k_misc_bodies.h"
     const float* a = act + (size_t)b * Tc * kPoolC + c;
     float* d = dact + (size_t)b * Tc * kPoolC + c;
     // elementwise from here on: the frames are dealt over the blocks of grid.z (small batches: 24 x 8 blocks of a 68-step
@@ -422,14 +299,44 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     }
 }
 
-hipError_t launch_pool_fwd(const float* act5, int B, int Tc, float* stats, hipStream_t s) {
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(kPoolC / 64, B), dim3(256), 0, s, act5, Tc, stats);
+// ... of a batch of unequal lengths (pool_fwd_ragged_kernel): the coefficients from the row's own frame count Tc, +0 into the
+// rows behind its own frames -- the zeros the data gradients carry down the stack
+template <int NS>
+__global__ __launch_bounds__(256) void pool_bwd_ragged_kernel(const float* __restrict__ act, const float* __restrict__ stats,
+                                                              const float* __restrict__ dpart, int nsplit, int B, int Tld,
+                                                              float* __restrict__ dact, const int32_t* __restrict__ lens, int nlen, int T) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int Tc = min(num_frames(row_samples(lens, nlen, b, T)) - kTdnnContext, Tld);
+#define SG_MISC_BODY 4
+#include "k_misc_bodies.h"
+    const float* a = act + (size_t)b * Tld * kPoolC + c;
+    float* d = dact + (size_t)b * Tld * kPoolC + c;
+    const int per = (Tld + (int)gridDim.z - 1) / (int)gridDim.z;
+    const int t0 = (int)blockIdx.z * per, t1 = min(Tld, t0 + per);
+    for (int t = t0 + wid; t < t1; t += 4) {
+        const float v = t < Tc ? a[(size_t)t * kPoolC] : 0.f;
+        d[(size_t)t * kPoolC] = v > 0.f ? alpha + beta * (v - mean) : 0.f;
+    }
+}
+
+// rl.dev: a batch of unequal lengths, T its row stride in samples (Tc = num_frames(T) - kTdnnContext)
+hipError_t launch_pool_fwd(const float* act5, int B, int Tc, float* stats, hipStream_t s, const RowLens& rl, int T) {
+    if (rl.dev) hipLaunchKernelGGL(pool_fwd_ragged_kernel, dim3(kPoolC / 64, B), dim3(256), 0, s, act5, Tc, stats, rl.dev, rl.n, T);
+    else hipLaunchKernelGGL(pool_fwd_kernel, dim3(kPoolC / 64, B), dim3(256), 0, s, act5, Tc, stats);
     return hipGetLastError();
 }
 hipError_t launch_pool_bwd(const float* act5, const float* stats, const float* dstats_part, int nsplit, int B, int Tc,
-                           float* dact5, hipStream_t s) {
+                           float* dact5, hipStream_t s, const RowLens& rl, int T) {
     const int z = B >= 64 ? 1 : (1536 + (kPoolC / 64) * B - 1) / ((kPoolC / 64) * B);  // >= ~1500 blocks in all
-    if (nsplit == kFc1BwdSplitK)
+    if (rl.dev && nsplit == kFc1BwdSplitK)
+        hipLaunchKernelGGL(pool_bwd_ragged_kernel<kFc1BwdSplitK>, dim3(kPoolC / 64, B, z), dim3(256), 0, s, act5, stats, dstats_part, nsplit,
+                           B, Tc, dact5, rl.dev, rl.n, T);
+    else if (rl.dev)
+        hipLaunchKernelGGL(pool_bwd_ragged_kernel<0>, dim3(kPoolC / 64, B, z), dim3(256), 0, s, act5, stats, dstats_part, nsplit, B, Tc, dact5,
+                           rl.dev, rl.n, T);
+    else if (nsplit == kFc1BwdSplitK)
         hipLaunchKernelGGL(pool_bwd_kernel<kFc1BwdSplitK>, dim3(kPoolC / 64, B, z), dim3(256), 0, s, act5, stats, dstats_part, nsplit, B,
                            Tc, dact5);
     else

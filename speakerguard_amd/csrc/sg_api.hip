@@ -228,6 +228,7 @@ struct PassDims {
     bool keep_scale = false;  // reuse ws.scale from the previous pass (fused loop: x stays in [-1, 1])
     int Bu = 0;               // > 0: the rows are B / Bu EOT repeats of Bu utterances (row = repeat * Bu + utterance); the
                               // waveform has Bu rows and d loss / d x sums the repeats (sg_xv_pgd_run)
+    RowLens lens;             // a batch of unequal lengths (sg_xv_*_ragged): T, F are the longest utterance's, the row strides
 };
 
 // waveform / features -> padded CMVN features in ws.feats
@@ -241,7 +242,7 @@ int run_mfcc_forward(sg_ctx* ctx, const float* x, const PassDims& d, const sg_di
     tab.spec_cache = want_grad ? w.spec_cache : nullptr;  // the backward of this pass starts from the stored spectrum
     tab.mel_cache = want_grad ? w.mel_cache : nullptr;
     tab.rep_utts = d.Bu;
-    SG_STAGE(SG_STAGE_MFCC_FWD, launch_mfcc_fwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.feats_raw, s));
+    SG_STAGE(SG_STAGE_MFCC_FWD, launch_mfcc_fwd(tab, x, d.B, d.T, d.F, w.scale, dz, w.feats_raw, s, d.lens));
     return SG_OK;
 }
 
@@ -249,7 +250,7 @@ int run_frontend(sg_ctx* ctx, const float* x, const PassDims& d, int flag, const
     Workspace& w = ctx->ws;
     if (flag == SG_FLAG_WAV) {
         if (int rc = run_mfcc_forward(ctx, x, d, dz, want_grad, s)) return rc;
-        SG_STAGE(SG_STAGE_CMVN_FWD, launch_cmvn_fwd(w.feats_raw, kCep, w.feats, kFeatPad, d.B, d.F, s));
+        SG_STAGE(SG_STAGE_CMVN_FWD, launch_cmvn_fwd(w.feats_raw, kCep, w.feats, kFeatPad, d.B, d.F, s, d.lens, d.T));
     } else if (flag == SG_FLAG_RAW) {
         SG_HIP(launch_cmvn_fwd(x, kCep, w.feats, kFeatPad, d.B, d.F, s));
     } else {
@@ -290,7 +291,7 @@ int run_tdnn_forward(sg_ctx* ctx, const PassDims& d, hipStream_t s) {
         ConvGemmArgs a = fwd_layer_args(ctx, l, d.B, d.F);
         SG_STAGE(l + 1, launch_conv_gemm(a, 0, EPI_BIAS_RELU, 1, s));
     }
-    SG_STAGE(SG_STAGE_POOL_FWD, launch_pool_fwd(w.act[4], d.B, w.Fl[4], w.stats, s));
+    SG_STAGE(SG_STAGE_POOL_FWD, launch_pool_fwd(w.act[4], d.B, w.Fl[4], w.stats, s, d.lens, d.T));
     // fc1 as a split-K contraction: (B x 3072) x (3072 x 512) -> kFc1SplitK partial slabs
     ConvGemmArgs a{};
     a.A = w.stats; a.W = ctx->xv.fc1_w; a.C = w.fc1_part; a.bias = nullptr; a.mask = nullptr;
@@ -314,7 +315,7 @@ int run_tdnn_backward(sg_ctx* ctx, const PassDims& d, hipStream_t s) {
         a.split_stride = (long long)d.B * kStats;
         SG_STAGE(SG_STAGE_FC1_BWD, launch_conv_gemm(a, 2, EPI_NONE, kFc1BwdSplitK, s));
     }
-    SG_STAGE(SG_STAGE_POOL_BWD, launch_pool_bwd(w.act[4], w.stats, w.dstats_part, kFc1BwdSplitK, d.B, w.Fl[4], w.dact[4], s));
+    SG_STAGE(SG_STAGE_POOL_BWD, launch_pool_bwd(w.act[4], w.stats, w.dstats_part, kFc1BwdSplitK, d.B, w.Fl[4], w.dact[4], s, d.lens, d.T));
     for (int l = kLayers - 1; l >= 0; --l) {
         ConvGemmArgs a{};
         a.A = w.dact[l];
@@ -405,7 +406,7 @@ int run_mfcc_adjoint(sg_ctx* ctx, const float* x, const PassDims& d, const sg_di
     }
     tab.rep_utts = d.Bu;
     return mfcc_adjoint(ctx, tab, x, d.B, d.T, d.F, w.scale, dz, w.dfeats_raw, w.dframes, d.Bu > 0 ? d.B / d.Bu : 1, grad_acc_in,
-                        grad_out, x_update, lower, upper, step, grad_sign, true, s);
+                        grad_out, x_update, lower, upper, step, grad_sign, true, s, d.lens);
 }
 
 // after the tail produced ws.demb: chain back to the caller's input level
@@ -423,7 +424,7 @@ int run_backward_to_input(sg_ctx* ctx, const float* x, const PassDims& d, int fl
                                d.F, s));
     } else {
         SG_STAGE(SG_STAGE_CMVN_BWD, launch_cmvn_bwd(w.dfeats, kFeatPad, kL1BwdSplitK, (long long)d.B * d.F * kFeatPad,
-                                                    w.dfeats_raw, kCep, d.B, d.F, s));
+                                                    w.dfeats_raw, kCep, d.B, d.F, s, d.lens, d.T));
         return run_mfcc_adjoint(ctx, x, d, dz, grad_out, x_update, lower, upper, step, grad_sign, s, grad_acc_in);
     }
     return SG_OK;
@@ -484,7 +485,32 @@ struct XvLoopCall {  // the caller's buffers, as the entry point received them
     int B, T;
     const sg_pgd_params* p;
     LoopOut out;
+    RowLens lens;  // sg_xv_pgd_run_ragged: the B utterances' sample counts (T: the longest)
 };
+
+// What the *_ragged entry points refuse about their lengths, from the caller's HOST copy and before any launch or allocation:
+// every utterance must be one the uniform entry point takes alone, fit its row, and the longest must fill it (T_max is the row
+// stride and sizes the workspace: padding beyond every utterance would only cost).  The kernels read the device copy.
+int check_lengths(sg_ctx* ctx, const char* who, const int32_t* lengths_dev, const int32_t* lengths_host, int B, int T_max,
+                  const sg_dither* dz, RowLens* out) {
+    if (!lengths_dev || !lengths_host) return fail(ctx, SG_ERR_ARG, "%s: lengths_dev and lengths_host are required", who);
+    if (B < 1) return fail(ctx, SG_ERR_ARG, "B must be >= 1");
+    if (dz && dz->noise_dev) return fail(ctx, SG_ERR_ARG, "%s: an explicit dither tensor is not supported with lengths", who);
+    bool full = false;
+    for (int b = 0; b < B; ++b) {
+        const int t = lengths_host[b];
+        int Fl[kLayers];
+        if (t > T_max) return fail(ctx, SG_ERR_ARG, "%s: lengths[%d] = %d exceeds T_max = %d", who, b, t, T_max);
+        if (t < kWin) return fail(ctx, SG_ERR_ARG, "%s: lengths[%d] = %d is shorter than one 25 ms window", who, b, t);
+        if (!layer_frames(num_frames(t), Fl))
+            return fail(ctx, SG_ERR_ARG, "%s: lengths[%d] = %d gives %d frames, too few for the TDNN context", who, b, t, num_frames(t));
+        full |= t == T_max;
+    }
+    if (!full) return fail(ctx, SG_ERR_ARG, "%s: no utterance has T_max = %d samples (T_max must be the longest length)", who, T_max);
+    out->dev = lengths_dev;
+    out->n = B;
+    return SG_OK;
+}
 
 // ---- FeCo inside the loop (sg_xv_pgd_run_feco)
 struct XvFecoPass {  // one pass of the loop as FeCo sees it
@@ -583,6 +609,7 @@ int xv_pgd_loop(sg_ctx* ctx, const XvLoopCall& c, const sg_wav_stage* chain, int
         return fail(ctx, SG_ERR_ARG, "sg_xv_pgd_run_defended: %d rows per pass, the stage kernels take at most 65535: split the batch", rows_max);
     PassDims d;
     if ((rc = check_dims(ctx, B * G, T, SG_FLAG_WAV, &d))) return rc;  // workspace for the largest pass
+    d.lens = c.lens;
     if (defended && (rc = ensure_def_workspace(ctx, rows_max, T, n_stages, ci.n_saved, per_row, s))) return rc;
     Workspace& w = ctx->ws;
     if (feco) {  // rows of the largest pass, in front of FeCo and behind it
@@ -691,12 +718,12 @@ namespace sg {
 
 int mfcc_adjoint(sg_ctx* ctx, const MfccTables& tab, const float* x, int B, int T, int F, const float* scale, const sg_dither* dz,
                  const float* dfeats, float* dframes, int reps, const float* acc_in, float* grad_out, float* x_io, const float* lower,
-                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s) {
+                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s, const RowLens& rl) {
     if (staged) trace_mark(ctx, SG_STAGE_MFCC_BWD, s, 0);
-    SG_HIP(launch_mfcc_bwd(tab, x, B, T, F, scale, dz, dfeats, dframes, s));
+    SG_HIP(launch_mfcc_bwd(tab, x, B, T, F, scale, dz, dfeats, dframes, s, rl));
     if (staged) trace_mark(ctx, SG_STAGE_MFCC_BWD, s, 1);
     if (staged) trace_mark(ctx, SG_STAGE_OVERLAP_ADD, s, 0);
-    SG_HIP(launch_frames_to_wave(dframes, B / reps, T, F, reps, acc_in, grad_out, x_io, lower, upper, step, grad_sign, s));
+    SG_HIP(launch_frames_to_wave(dframes, B / reps, T, F, reps, acc_in, grad_out, x_io, lower, upper, step, grad_sign, s, rl));
     if (staged) trace_mark(ctx, SG_STAGE_OVERLAP_ADD, s, 1);
     return SG_OK;
 }
@@ -1109,11 +1136,13 @@ int sg_xv_cmvn_backward(sg_ctx* ctx, const float* dout_dev, int32_t B, int32_t F
     return SG_OK;
 }
 
-int sg_xv_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, int32_t flag, const sg_dither* dither,
-                  int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* tdnn_emb_dev, void* stream) {
+// sg_xv_forward and sg_xv_forward_ragged (lens: the checked lengths, flag 0) after their own argument checks
+static int xv_forward(sg_ctx* ctx, const float* x_dev, const RowLens& lens, int32_t B, int32_t T_or_F, int32_t flag, const sg_dither* dither,
+                      int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* tdnn_emb_dev, void* stream) {
     PassDims d;
     int rc = check_dims(ctx, B, T_or_F, flag, &d);
     if (rc) return rc;
+    d.lens = lens;
     if (!x_dev) return fail(ctx, SG_ERR_ARG, "x is NULL");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = run_frontend(ctx, x_dev, d, flag, dither, false, s))) return rc;
@@ -1124,6 +1153,20 @@ int sg_xv_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, in
     t.tdnn_emb = tdnn_emb_dev; t.emb = emb_dev; t.scores = scores_dev; t.decisions = decisions_dev;
     SG_STAGE(SG_STAGE_TAIL, launch_tail(t, s));
     return SG_OK;
+}
+
+int sg_xv_forward(sg_ctx* ctx, const float* x_dev, int32_t B, int32_t T_or_F, int32_t flag, const sg_dither* dither,
+                  int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* tdnn_emb_dev, void* stream) {
+    return xv_forward(ctx, x_dev, RowLens(), B, T_or_F, flag, dither, decisions_dev, scores_dev, emb_dev, tdnn_emb_dev, stream);
+}
+
+int sg_xv_forward_ragged(sg_ctx* ctx, const float* x_dev, const int32_t* lengths_dev, const int32_t* lengths_host, int32_t B, int32_t T_max,
+                         const sg_dither* dither, int64_t* decisions_dev, float* scores_dev, float* emb_dev, float* tdnn_emb_dev,
+                         void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    RowLens lens;
+    if (int rc = check_lengths(ctx, "sg_xv_forward_ragged", lengths_dev, lengths_host, B, T_max, dither, &lens)) return rc;
+    return xv_forward(ctx, x_dev, lens, B, T_max, SG_FLAG_WAV, dither, decisions_dev, scores_dev, emb_dev, tdnn_emb_dev, stream);
 }
 
 int sg_xv_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t capacity_floats, int32_t* rows_per_utt,
@@ -1146,12 +1189,14 @@ int sg_xv_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t c
     return SG_OK;
 }
 
-int sg_xv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
-                    const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev,
-                    float* loss_dev, float* grad_dev, void* stream) {
+// sg_xv_loss_grad and sg_xv_loss_grad_ragged, as xv_forward
+static int xv_loss_grad(sg_ctx* ctx, const float* x_dev, const RowLens& lens, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
+                        const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev,
+                        float* loss_dev, float* grad_dev, void* stream) {
     PassDims d;
     int rc = check_dims(ctx, B, T_or_F, flag, &d);
     if (rc) return rc;
+    d.lens = lens;
     if (!x_dev || !y_dev || !loss) return fail(ctx, SG_ERR_ARG, "x, y and loss are required");
     if (loss->loss == SG_LOSS_LINEAR && !loss->coef_dev) return fail(ctx, SG_ERR_ARG, "SG_LOSS_LINEAR needs coef_dev");
     hipStream_t s = (hipStream_t)stream;
@@ -1169,6 +1214,21 @@ int sg_xv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
         w.grad_B = d.B; w.grad_F = d.F; w.grad_flag = flag;  // what sg_xv_debug_gradient may read back
     }
     return SG_OK;
+}
+
+int sg_xv_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F, int32_t flag,
+                    const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev, float* scores_dev,
+                    float* loss_dev, float* grad_dev, void* stream) {
+    return xv_loss_grad(ctx, x_dev, RowLens(), y_dev, B, T_or_F, flag, loss, dither, decisions_dev, scores_dev, loss_dev, grad_dev, stream);
+}
+
+int sg_xv_loss_grad_ragged(sg_ctx* ctx, const float* x_dev, const int32_t* lengths_dev, const int32_t* lengths_host, const int64_t* y_dev,
+                           int32_t B, int32_t T_max, const sg_loss_spec* loss, const sg_dither* dither, int64_t* decisions_dev,
+                           float* scores_dev, float* loss_dev, float* grad_dev, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    RowLens lens;
+    if (int rc = check_lengths(ctx, "sg_xv_loss_grad_ragged", lengths_dev, lengths_host, B, T_max, dither, &lens)) return rc;
+    return xv_loss_grad(ctx, x_dev, lens, y_dev, B, T_max, SG_FLAG_WAV, loss, dither, decisions_dev, scores_dev, loss_dev, grad_dev, stream);
 }
 
 int sg_xv_debug_gradient(sg_ctx* ctx, int32_t which, float* out_dev, int64_t capacity_floats, int32_t* dims, void* stream) {
@@ -1271,6 +1331,20 @@ int sg_xv_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const flo
     if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
     const XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T, p,
                        {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
+    return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, nullptr, 0, (hipStream_t)stream);
+}
+
+int sg_xv_pgd_run_ragged(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,
+                         const int32_t* lengths_dev, const int32_t* lengths_host, int32_t B, int32_t T_max, const sg_pgd_params* p,
+                         uint8_t* success_dev, int64_t* decisions_dev, float* scores_dev, float* loss_dev, float* loss_trace_dev,
+                         int64_t* decision_trace_dev, void* stream) {
+    int rc, eot_size;
+    if (!ctx) return SG_ERR_ARG;
+    if ((rc = loop_check_args(ctx, !x_adv_dev || !y_dev || !lower_dev || !upper_dev || !p, xv_loop_shape(B, T_max), p))) return rc;
+    if ((rc = loop_eot_size(ctx, p, &eot_size))) return rc;
+    XvLoopCall c{x_adv_dev, y_dev, lower_dev, upper_dev, B, T_max, p,
+                 {success_dev, decisions_dev, scores_dev, loss_dev, loss_trace_dev, decision_trace_dev}};
+    if ((rc = check_lengths(ctx, "sg_xv_pgd_run_ragged", lengths_dev, lengths_host, B, T_max, &p->dither, &c.lens))) return rc;
     return xv_pgd_loop(ctx, c, nullptr, 0, DefChainInfo{false, true, 0}, eot_size, nullptr, 0, (hipStream_t)stream);
 }
 

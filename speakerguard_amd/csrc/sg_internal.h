@@ -42,7 +42,22 @@ constexpr int kL1BwdSplitK = 10;       // tdnn1 data gradient: two K-slabs per t
                                        // slab per tap 95 blocks for 256 CUs, 19 -> 11 us at 8 utterances, 29 -> 24 at 32, same at 64).  A
                                        // constant of the arithmetic: the slabs are summed in order, whatever the batch
 
-inline int num_frames(int T) { return (T + kShift / 2) / kShift; }
+constexpr int num_frames(int T) { return (T + kShift / 2) / kShift; }
+constexpr int kTdnnContext = 30;  // frames tdnn1 .. tdnn3 take off an utterance: (5 - 1) 1 + (5 - 1) 2 + (7 - 1) 3 (tdnn4 / tdnn5: none)
+
+// A batch of unequal lengths (sg_xv_*_ragged): the device array of per-utterance sample counts.  Every buffer keeps the row
+// stride of the longest utterance (T, F, F5 of the call); row r of a pass is utterance r % n, so EOT repeats wrap.  dev == null:
+// a uniform batch, the kernels of old.
+struct RowLens {
+    const int32_t* dev = nullptr;  // (n) int32
+    int n = 0;
+};
+// samples of row `row`, held inside what the buffers and the front-end can take whatever the array says (the entry points
+// validate a host copy before the first launch; a kernel still never derives an address from an unchecked count)
+__device__ __forceinline__ int row_samples(const int32_t* lens, int n, int row, int T) {
+    const int t = lens[row % n];
+    return t > T ? T : (t < kWin ? kWin : t);
+}
 
 // a device buffer that is grown on demand (dev_grow): the pointer and the elements it has room for; reads as the pointer
 template <typename T>
@@ -842,21 +857,23 @@ hipError_t launch_pack_k4(const float* w, int K, int N, float* wq, hipStream_t s
 
 // mode 0: xv_plda ('origin': [-1,1] -> x32768), mode 1: AudioNet ('scale': int16 range -> /32768)
 hipError_t launch_input_scale(const float* x, int64_t n, float* scratch512, float* scale, int mode, hipStream_t s);
+// rl (here and below): the per-utterance sample counts of a batch of unequal lengths -- T, F (and Tc) are then the row strides,
+// the longest utterance's -- or none: a uniform batch
 hipError_t launch_mfcc_fwd(const MfccTables& t, const float* x, int B, int T, int F, const float* scale,
-                           const sg_dither* dz, float* feats, hipStream_t s);
+                           const sg_dither* dz, float* feats, hipStream_t s, const RowLens& rl = RowLens());
 hipError_t launch_mfcc_bwd(const MfccTables& t, const float* x, int B, int T, int F, const float* scale,
-                           const sg_dither* dz, const float* dfeats, float* dframes, hipStream_t s);
+                           const sg_dither* dz, const float* dfeats, float* dframes, hipStream_t s, const RowLens& rl = RowLens());
 // overlap-add of dframes into d loss / d x (+ acc_in, the sum over earlier EOT repeats; may alias grad_out);
 // optional fused PGD update of x (in place)
 // dframes (R, B, F, 400): R batched EOT repeats, summed in repeat order
 hipError_t launch_frames_to_wave(const float* dframes, int B, int T, int F, int R, const float* acc_in, float* grad_out,
                                  float* x_io, const float* lower, const float* upper, float step, int grad_sign,
-                                 hipStream_t s);
+                                 hipStream_t s, const RowLens& rl = RowLens());
 // The two launches above as the one MFCC adjoint (sg_api.hip): dfeats (B, F, 30) -> dframes (the caller's buffer) -> d loss / d x,
 // the B rows being `reps` repeats of B / reps utterances.  `staged`: the launches carry their SG_STAGE tags (the x-vector pass)
 int mfcc_adjoint(sg_ctx* ctx, const MfccTables& tab, const float* x, int B, int T, int F, const float* scale, const sg_dither* dz,
                  const float* dfeats, float* dframes, int reps, const float* acc_in, float* grad_out, float* x_io, const float* lower,
-                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s);
+                 const float* upper, float step, int grad_sign, bool staged, hipStream_t s, const RowLens& rl = RowLens());
 hipError_t launch_pgd_update(float* x, const float* g, const float* lo, const float* hi, int64_t n,
                              float step, int grad_sign, hipStream_t s);
 // planes (G, n): the cotangents of G EOT repeats; total = ((carry +) p0 + p1) + ... in float32, in that order.  sum_out != null:
@@ -899,12 +916,13 @@ int def_chain_backward(sg_ctx* ctx, const sg_wav_stage* chain, int n_stages, con
 hipError_t launch_copy_cols(const float* in, int ld_in, float* out, int ld_out, int64_t rows, int ncol, hipStream_t s);
 hipError_t launch_sum_cols(const float* in, int ld_in, int nsplit, long long slab_stride, float* out, int ld_out,
                            int64_t rows, int ncol, hipStream_t s);
-hipError_t launch_cmvn_fwd(const float* in, int ld_in, float* out, int ld_out, int B, int F, hipStream_t s);
+hipError_t launch_cmvn_fwd(const float* in, int ld_in, float* out, int ld_out, int B, int F, hipStream_t s,
+                           const RowLens& rl = RowLens(), int T = 0);
 hipError_t launch_cmvn_bwd(const float* dout, int ld_dout, int nsplit, long long slab_stride, float* din, int ld_din,
-                           int B, int F, hipStream_t s);
-hipError_t launch_pool_fwd(const float* act5, int B, int Tc, float* stats, hipStream_t s);
+                           int B, int F, hipStream_t s, const RowLens& rl = RowLens(), int T = 0);
+hipError_t launch_pool_fwd(const float* act5, int B, int Tc, float* stats, hipStream_t s, const RowLens& rl = RowLens(), int T = 0);
 hipError_t launch_pool_bwd(const float* act5, const float* stats, const float* dstats_part, int nsplit,
-                           int B, int Tc, float* dact5, hipStream_t s);
+                           int B, int Tc, float* dact5, hipStream_t s, const RowLens& rl = RowLens(), int T = 0);
 
 hipError_t launch_cw2_step(float* modifier, float* exp_avg, float* exp_avg_sq, const float* x, const float* input_cur,
                            const float* grad1, const float* const_c, int B, int T, float lr, int step_t,

@@ -132,6 +132,46 @@ class EngineOps:
         assert x.dim() == 3 and x.shape[2] == self._feat_width, "feature input must be (B, F, %d)" % self._feat_width
         return x, x.shape[0], x.shape[1]
 
+    # ---- batches of unequal lengths (sg_xv_*_ragged): x (B, 1, T_max) padded, lengths (B,) int32 samples per utterance
+    takes_lengths = False  # a model whose engine entries take lengths says True (xv_plda)
+    _lengths_ok = None     # (tensor, its version, T_max, device copy, host copy) of the last lengths accepted
+    min_length = 400       # one 25 ms window
+    min_frames = 32        # the TDNN context (30 frames) and two frames for the pooled standard deviation
+
+    def refuse_lengths(self, lengths):
+        """A model (or a route through it) that cannot take ``lengths=`` must say so, never attack the padding."""
+        if lengths is not None:
+            raise ValueError("%s does not take lengths=: it handles batches of one length only (crop, or attack the utterances "
+                             "one at a time)" % type(self).__name__)
+
+    def _lengths_args(self, lengths, B, T, flag=0):
+        """The checks of the *_ragged entry points, made here on the host from the tensor given (ValueError, before anything is
+        drawn or launched) -> (device int32 tensor, host int32 array): what the kernels read and what the C entry validates
+        again.  The pair is remembered per tensor (identity and in-place version), so a step loop pays one upload."""
+        if not self.takes_lengths:
+            self.refuse_lengths(lengths)
+        if flag != 0:
+            raise ValueError("lengths= goes with waveform input (flag 0) only")
+        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError("lengths must be an int32 tensor of shape (%d,), one sample count per row of x" % B)
+        ok = self._lengths_ok
+        if ok is not None and ok[0] is lengths and ok[1] == lengths._version and ok[2] == T:
+            return ok[3], ok[4]
+        host = np.ascontiguousarray(lengths.detach().cpu().numpy(), dtype=np.int32)
+        frames = N.load().sg_xv_num_frames
+        for b, t in enumerate(host.tolist()):
+            if t > T:
+                raise ValueError("lengths[%d] = %d exceeds the padded length %d" % (b, t, T))
+            if t < self.min_length:
+                raise ValueError("lengths[%d] = %d is shorter than one 25 ms window (%d samples)" % (b, t, self.min_length))
+            if frames(t) < self.min_frames:
+                raise ValueError("lengths[%d] = %d gives %d frames, too few for the TDNN context (%d)" % (b, t, frames(t), self.min_frames))
+        if int(host.max()) != T:
+            raise ValueError("no utterance has the padded length %d: pad to the longest utterance (audio_io.pad_batch)" % T)
+        dev = torch.from_numpy(host).to(self.device)
+        self._lengths_ok = (lengths, lengths._version, T, dev, host)
+        return dev, host
+
     def activation_shape(self, layer):
         """(rows, channels) per utterance of layer `layer`'s activation in the last pass"""
         rows, ch = C.c_int32(), C.c_int32()
@@ -215,14 +255,17 @@ class EngineOps:
         return stages, keep
 
     def _pgd_loop(self, entry, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size, eot_batch_size, trace,
-                  chain=None, feco=None, feco_slot=False, feco_level=None):
+                  chain=None, feco=None, feco_slot=False, feco_level=None, lengths=None):
         """One device-resident PGD loop call: C entry `entry` over the common arguments, then the stage array and its length
         if a `chain` is given, then the FeCo block if `feco` is given (`feco_slot`: the entry takes that pointer anyway,
         NULL without a defense) and behind it the feature level FeCo sits at if `feco_level` is given (sg_xv_pgd_run_feco),
         then the outputs and the stream.  Keys are drawn in this order: the front-end's dither (``_pgd_dither``), the chain's
-        randomised stages in chain order, FeCo's (``_feco_params``)."""
+        randomised stages in chain order, FeCo's (``_feco_params``).  `lengths`: the entry takes the device and the host copy of
+        a padded batch's sample counts in front of B (``_lengths_args``: checked before anything is drawn or cloned)."""
         if chain is not None:
             chain = self._checked_chain(chain, feco is None)
+        if lengths is not None:
+            lengths = self._lengths_args(lengths, x.shape[0], x.shape[-1])
         x_adv, y, lower, upper, B, T, p, outs = self._pgd_args(x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign,
                                                                eot_size, eot_batch_size, trace)
         extras = []
@@ -233,7 +276,8 @@ class EngineOps:
             extras.append(None if feco is None else C.byref(self._feco_params(feco, T)))
         if feco_level is not None:
             extras.append(int(feco_level))
-        self.ctx.call(entry, N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), B, T, C.byref(p), *extras,
+        front = [] if lengths is None else [N._ptr(lengths[0]), lengths[1].ctypes.data_as(C.c_void_p)]
+        self.ctx.call(entry, N._ptr(x_adv), N._ptr(y), N._ptr(lower), N._ptr(upper), *front, B, T, C.byref(p), *extras,
                       *[N._ptr(t) for t in outs], self._stream())
         return (x_adv,) + outs
 

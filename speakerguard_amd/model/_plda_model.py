@@ -157,12 +157,17 @@ class PldaModel(EngineOps):
         return feats, (x, scale, dz)
 
     # ------------------------------------------------------------------ reference API
-    def _forward(self, x, flag, want_emb=False, dither_noise=None, enroll=None, dither_seed=None, **want):
-        """-> (decisions, scores, embedding or None, the model's fourth output or None: asked for by its keyword ``_fourth``)"""
+    def _forward(self, x, flag, want_emb=False, dither_noise=None, enroll=None, dither_seed=None, lengths=None, **want):
+        """-> (decisions, scores, embedding or None, the model's fourth output or None: asked for by its keyword ``_fourth``).
+        `lengths`: x is a padded batch of unequal lengths (``EngineOps._lengths_args``; the x-vector model only)."""
         want_fourth = want.pop(self._fourth, False)
         if want:
             raise TypeError("_forward() got an unexpected keyword argument %r" % sorted(want)[0])
         x, B, TF = self._prep(x, flag)
+        if lengths is not None:
+            if dither_noise is not None:
+                raise ValueError("an explicit dither tensor is not supported with lengths=")
+            lengths = self._lengths_args(lengths, B, TF, flag)
         n_spk = self.num_spks if enroll is None else enroll.shape[0]
         dec = torch.empty(B, device=self.device, dtype=torch.int64)
         scores = torch.empty(B, n_spk, device=self.device, dtype=torch.float32)
@@ -172,8 +177,12 @@ class PldaModel(EngineOps):
         if enroll is not None:
             self.ctx.call(self._entry + "_enroll_override", N._ptr(enroll), enroll.shape[0])
         try:
-            self.ctx.call(self._entry + "_forward", N._ptr(x), B, TF, flag, C.byref(dz), N._ptr(dec), N._ptr(scores), N._ptr(emb),
-                          N._ptr(fourth), self._stream())
+            if lengths is None:
+                self.ctx.call(self._entry + "_forward", N._ptr(x), B, TF, flag, C.byref(dz), N._ptr(dec), N._ptr(scores), N._ptr(emb),
+                              N._ptr(fourth), self._stream())
+            else:
+                self.ctx.call(self._entry + "_forward_ragged", N._ptr(x), N._ptr(lengths[0]), lengths[1].ctypes.data_as(C.c_void_p), B, TF,
+                              C.byref(dz), N._ptr(dec), N._ptr(scores), N._ptr(emb), N._ptr(fourth), self._stream())
         finally:
             if enroll is not None:
                 self.ctx.call(self._entry + "_enroll_override", None, 0)
@@ -183,21 +192,22 @@ class PldaModel(EngineOps):
     def embedding(self, x, flag=0):
         return self._forward(x, flag, want_emb=True)[2]
 
-    def forward(self, x, flag=0, return_emb=False, enroll_embs=None, dither_seed=None):
-        """`enroll_embs`: a per-call table, as in the reference (iv_plda.py:155-165); `dither_seed`: explicit generator key of
+    def forward(self, x, flag=0, return_emb=False, enroll_embs=None, dither_seed=None, lengths=None):
+        """`lengths`: x is a padded batch (B, 1, T_max) of utterances of unequal lengths, int32 sample counts (B,): row b is scored as
+        utterance b alone at its own length (the x-vector model; ``audio_io.pad_batch`` builds both).  `enroll_embs`: a per-call table, as in the reference (iv_plda.py:155-165); `dither_seed`: explicit generator key of
         this pass's dither (a caller that scores an input and then asks ``loss_grad`` for the gradient of the SAME noise
         realisation passes one key to both: defended_model 'average')."""
         enroll = self._enroll_for_call(enroll_embs)
-        _, scores, emb, _ = self._forward(x, flag, want_emb=return_emb, enroll=enroll, dither_seed=dither_seed)
+        _, scores, emb, _ = self._forward(x, flag, want_emb=return_emb, enroll=enroll, dither_seed=dither_seed, lengths=lengths)
         return (scores, emb) if return_emb else scores
 
     __call__ = forward
 
-    def score(self, x, flag=0, enroll_embs=None):
-        return self.forward(x, flag=flag, enroll_embs=enroll_embs)
+    def score(self, x, flag=0, enroll_embs=None, lengths=None):
+        return self.forward(x, flag=flag, enroll_embs=enroll_embs, lengths=lengths)
 
-    def make_decision(self, x, flag=0, enroll_embs=None):
-        """-> (decisions int64 (B,), scores (B, n_spk)); iv_plda.py:182-194."""
+    def make_decision(self, x, flag=0, enroll_embs=None, lengths=None):
+        """-> (decisions int64 (B,), scores (B, n_spk)); iv_plda.py:182-194.  `lengths`: see ``forward``."""
         enroll = self._enroll_for_call(enroll_embs)
-        dec, scores, _, _ = self._forward(x, flag, enroll=enroll)
+        dec, scores, _, _ = self._forward(x, flag, enroll=enroll, lengths=lengths)
         return dec, scores

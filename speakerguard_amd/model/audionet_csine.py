@@ -112,21 +112,25 @@ class audionet_csine(EngineOps):
     def embedding(self, x, flag=0):
         return self._forward(x, flag, want_emb=True)[2]
 
-    def forward(self, x, flag=0, return_emb=False, enroll_embs=None):
+    # (`lengths`, a padded batch of unequal lengths, is the x-vector model's: refused here by name, never ignored)
+    def forward(self, x, flag=0, return_emb=False, enroll_embs=None, lengths=None):
+        self.refuse_lengths(lengths)
         _, scores, emb = self._forward(x, flag, want_emb=return_emb)
         return (scores, emb) if return_emb else scores
 
     __call__ = forward
 
-    def score(self, x, flag=0, enroll_embs=None):
-        return self.forward(x, flag=flag)
+    def score(self, x, flag=0, enroll_embs=None, lengths=None):
+        return self.forward(x, flag=flag, lengths=lengths)
 
-    def make_decision(self, x, flag=0, enroll_embs=None):
+    def make_decision(self, x, flag=0, enroll_embs=None, lengths=None):
+        self.refuse_lengths(lengths)
         dec, scores, _ = self._forward(x, flag)
         return dec, scores
 
     # ---- engine protocol used by attack.*
-    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True):
+    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, lengths=None):
+        self.refuse_lengths(lengths)
         x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)
         spec = loss_spec.native()
         self.ctx.call("sg_an_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), *[N._ptr(t) for t in outs],

@@ -98,9 +98,20 @@ class defended_model:
             return self.base_model.embedding(self.process_sequential(x), flag=self._last_flag())
         return self._average(lambda xx, f: (self.base_model.embedding(xx, flag=f),), x)[0]
 
-    def forward(self, x, return_emb=False, enroll_embs=None):
+    def _lengths_kw(self, lengths):
+        """`lengths` (a padded batch of unequal lengths) goes to a base model without defenses as it came; behind any defense
+        it is refused: no defense here knows where an utterance ends, and it would defend -- and be attacked in -- the padding."""
+        if lengths is None:
+            return {}
+        if self.defense is not None:
+            raise ValueError("defended_model does not take lengths= with a defense in place: the defenses handle batches of one "
+                             "length only (crop, or run the utterances one at a time)")
+        return {"lengths": lengths}
+
+    def forward(self, x, return_emb=False, enroll_embs=None, lengths=None):
         if self.defense is None:
-            return self.base_model(x, flag=0, return_emb=return_emb, enroll_embs=enroll_embs)
+            return self.base_model(x, flag=0, return_emb=return_emb, enroll_embs=enroll_embs, **self._lengths_kw(lengths))
+        self._lengths_kw(lengths)
         if self.order == sequential:
             return self.base_model(self.process_sequential(x), flag=self._last_flag(), return_emb=return_emb, enroll_embs=enroll_embs)
         logits, emb = self._average(lambda xx, f: self.base_model(xx, flag=f, return_emb=True, enroll_embs=enroll_embs), x)
@@ -108,24 +119,26 @@ class defended_model:
 
     __call__ = forward
 
-    def score(self, x, enroll_embs=None):
+    def score(self, x, enroll_embs=None, lengths=None):
         if self.defense is None:
-            return self.base_model.score(x, flag=0, enroll_embs=enroll_embs)
+            return self.base_model.score(x, flag=0, enroll_embs=enroll_embs, **self._lengths_kw(lengths))
+        self._lengths_kw(lengths)
         if self.order == sequential:
             return self.base_model.score(self.process_sequential(x), flag=self._last_flag(), enroll_embs=enroll_embs)
         return self._average(lambda xx, f: (self.base_model.score(xx, flag=f, enroll_embs=enroll_embs),), x)[0]
 
-    def make_decision(self, x, enroll_embs=None):
-        scores = self.score(x, enroll_embs=enroll_embs)
+    def make_decision(self, x, enroll_embs=None, lengths=None):
+        scores = self.score(x, enroll_embs=enroll_embs, **self._lengths_kw(lengths))
         decisions = torch.argmax(scores, dim=1)
         max_scores = torch.max(scores, dim=1)[0]
         decisions = torch.where(max_scores > self.base_model.threshold, decisions, torch.full_like(decisions, -1))
         return decisions, scores
 
     # ---- engine protocol ---------------------------------------------------------------------
-    def loss_grad(self, x, y, loss_spec, want_grad=True):
+    def loss_grad(self, x, y, loss_spec, want_grad=True, lengths=None):
         if self.defense is None:
-            return self.base_model.loss_grad(x, y, loss_spec, flag=0, want_grad=want_grad)
+            return self.base_model.loss_grad(x, y, loss_spec, flag=0, want_grad=want_grad, **self._lengths_kw(lengths))
+        self._lengths_kw(lengths)
         if not want_grad:
             decisions, scores = self.make_decision(x)
             return decisions, scores, loss_spec(scores, y), None

@@ -273,9 +273,11 @@ class iv_plda(PldaModel):
         return self._forward(x, flag, want_ivector=True)[3]
 
     # ------------------------------------------------------------------ engine protocol used by attack.*
-    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):
+    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None, lengths=None):
         """make_decision + per-example loss (+ d loss / d x, the shape of x, on a ``white_box=True`` model) in one native call
-        -> (decisions, scores, loss, grad or None).  On the default model ``want_grad=True`` raises."""
+        -> (decisions, scores, loss, grad or None).  On the default model ``want_grad=True`` raises.  `lengths` (a padded batch
+        of unequal lengths) is refused: the i-vector engine takes one length per call."""
+        self.refuse_lengths(lengths)
         if want_grad and not getattr(self, "_white_box", False):
             raise NotImplementedError(_NO_GRAD % "loss_grad(want_grad=True)")
         x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)

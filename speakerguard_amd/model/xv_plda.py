@@ -36,6 +36,7 @@ class xv_plda(PldaModel):
     _feat_width = 30
     _debug_activation = "sg_xv_debug_activation"
     _entry, _fourth, _fourth_width = "sg_xv", "want_tdnn", 512  # the fourth output: fc1's output before the mean subtraction
+    takes_lengths = True  # padded batches of unequal lengths: sg_xv_forward_ragged / _loss_grad_ragged / _pgd_run_ragged
 
     def __init__(self, extractor_file, plda_file, mean_file, transform_mat_file, model_file=None,
                  threshold=None, device="cuda:0", dither=1.0, dither_seed=0):
@@ -143,14 +144,24 @@ class xv_plda(PldaModel):
         return out[0] if slabs == 1 else out
 
     # ------------------------------------------------------------------ engine protocol used by attack.*
-    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None):
+    def loss_grad(self, x, y, loss_spec, flag=0, want_grad=True, dither_noise=None, dither_seed=None, lengths=None):
         """make_decision + per-example loss + d loss / d x in one native call (replaces EOT.py:32-35).
 
         Returns (decisions, scores, loss, grad) with grad shaped like x (None if want_grad=False).
+        `lengths` (B,) int32: x (B, 1, T_max) is a padded batch of utterances of unequal lengths; row b of every output is that
+        of utterance b alone at its own length, and grad is 0 in the padding (sg_xv_loss_grad_ragged).
         """
         x, y, B, TF, outs = self._loss_grad_args(x, y, loss_spec, flag, want_grad)
+        if lengths is not None:
+            if dither_noise is not None:
+                raise ValueError("an explicit dither tensor is not supported with lengths=")
+            lens_dev, lens_host = self._lengths_args(lengths, B, TF, flag)
         dz = self._dither(dither_noise, dither_seed)
         spec = loss_spec.native()
+        if lengths is not None:
+            self.ctx.call("sg_xv_loss_grad_ragged", N._ptr(x), N._ptr(lens_dev), lens_host.ctypes.data_as(C.c_void_p), N._ptr(y), B, TF,
+                          C.byref(spec), C.byref(dz), *[N._ptr(t) for t in outs], self._stream())
+            return outs
         self.ctx.call("sg_xv_loss_grad", N._ptr(x), N._ptr(y), B, TF, flag, C.byref(spec), C.byref(dz),
                       *[N._ptr(t) for t in outs], self._stream())
         return outs
@@ -161,10 +172,14 @@ class xv_plda(PldaModel):
 
     # the device loops: which C entry each takes (``EngineOps._pgd_loop`` marshals; neither takes a FeCo block)
     def pgd_run(self, x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size=1, eot_batch_size=1,
-                trace=False):
+                trace=False, lengths=None):
         """attack/FGSM.py:38-70 attack_batch as one device-resident loop, including EOT over the front-end's random
         dither (eot_size fresh-noise passes per gradient step, gradients summed on the device; the traces record each
-        step's loss averaged and decision voted over its repeats, like the reference's verbose print)."""
+        step's loss averaged and decision voted over its repeats, like the reference's verbose print).
+        `lengths` (B,) int32: a padded batch of unequal lengths (sg_xv_pgd_run_ragged); no padding sample moves."""
+        if lengths is not None:
+            return self._pgd_loop("sg_xv_pgd_run_ragged", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
+                                  eot_batch_size, trace, lengths=lengths)
         return self._pgd_loop("sg_xv_pgd_run", x, y, lower, upper, loss_spec, step_size, max_iter, grad_sign, eot_size,
                               eot_batch_size, trace)
 

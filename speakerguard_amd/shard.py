@@ -108,19 +108,21 @@ class ShardedAttack:
         dist.all_gather(parts, pad, group=self.group)
         return torch.cat([p[: e - s] for p, (s, e) in zip(parts, bounds)], 0)
 
-    def _local_attack(self, x, y, ranges):
+    def _local_attack(self, x, y, ranges, lengths=None):
         """This rank's part: one ``attack`` call per range (normally one range; a second one only for the trailing
         one-utterance call of a batch-coupled model).  Returns (adver of the ranges concatenated, success list)."""
         a = self.attacker
         ranges = [r for r in ranges if r[1] > r[0]]
         try:
-            return self._local_attack_at(x, y, ranges)
+            return self._local_attack_at(x, y, ranges, lengths)
         finally:
             a.index_offset = 0
 
-    def _local_attack_at(self, x, y, ranges):
+    def _local_attack_at(self, x, y, ranges, lengths=None):
         a = self.attacker
         restarts = getattr(a, "num_random_init", 0)
+        if lengths is not None and restarts and restarts > 0:
+            raise ValueError("ShardedAttack does not take lengths= with random restarts (num_random_init > 0)")
         if restarts and restarts > 0:
             if hasattr(a, "_begin_attack"):
                 a._begin_attack()
@@ -157,7 +159,8 @@ class ShardedAttack:
             if i > 0 and hasattr(a, "_begin_attack"):
                 a._begin_attack = lambda: None  # the rank's ranges are ONE attack call of the unsharded run: counted once
             try:
-                adv_r, succ_r = a.attack(x[lo:hi], y[lo:hi])
+                # (lengths: sliced with the batch; the attack pads every range's result back to the width of x)
+                adv_r, succ_r = a.attack(x[lo:hi], y[lo:hi]) if lengths is None else a.attack(x[lo:hi], y[lo:hi], lengths=lengths[lo:hi])
             finally:
                 if i > 0 and "_begin_attack" in vars(a):
                     del a._begin_attack
@@ -193,18 +196,21 @@ class ShardedAttack:
             s = e
         return out
 
-    def attack(self, x, y):
-        """x (N,1,T), y (N,) identical on every rank -> (adver_x, success list of length N).
+    def attack(self, x, y, lengths=None):
+        """x (N,1,T), y (N,) identical on every rank -> (adver_x, success list of length N).  `lengths` (N,) int32: x is a
+        padded batch of unequal lengths (``FGSM.attack``), identical on every rank too.
 
         With ``gather_audio=False`` the returned audio is this rank's shard only (the 12 MB all-gather
         of a 64 x 3 s batch is skipped); success flags are always global."""
         world, rank = self._world()
         n = x.shape[0]
         if world > 1 and getattr(self.attacker, "chunk_coupling", None) == "mean":
+            if lengths is not None:
+                raise ValueError("%s does not take lengths=" % type(self.attacker).__name__)
             return self._attack_mean_coupled(x, y)
         plan = self.plan(n)
         bounds = self.bounds(n)
-        adv, succ = self._local_attack(x, y, plan[rank])
+        adv, succ = self._local_attack(x, y, plan[rank], lengths)
         if world == 1:
             return adv, list(succ)
         flags = torch.tensor([bool(s) for s in succ], dtype=torch.uint8, device=x.device)
