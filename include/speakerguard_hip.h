@@ -427,6 +427,30 @@ int sg_an_debug_activation(sg_ctx* ctx, int32_t layer, float* out_dev, int64_t c
 int sg_an_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32_t B, int32_t T_or_F,
                     int32_t flag, const sg_loss_spec* loss, int64_t* decisions_dev, float* scores_dev,
                     float* loss_dev, float* grad_dev, void* stream);
+/* Workspace of the LAST sg_an_loss_grad call that asked for a gradient and ran the per-layer launch sequence (debug /
+ * parity): copies one buffer to out_dev, laid out as that pass wrote it (its B and frame counts, not the workspace's capacity).
+ *   which                          buffer                                                            dims[0..3]
+ *   SG_AN_GRAD_DACT1 + l - 1       d loss / d pre-activation of conv(l+1), l = 1..7 (conv2 .. conv8)   1, B, Tout_l, Cout_l
+ *   SG_AN_GRAD_DPOOL1 / 4 / 6      d loss / d pooled output of conv2 / conv5 / conv7                   1, B, Tout_l / 2, Cout_l
+ *   SG_AN_GRAD_DPRE                d loss / d pre-filter output                                        1, B, F, 32
+ *   SG_AN_GRAD_PRE                 the pre-filter's forward output                                     1, B, F, 32
+ *   SG_AN_GRAD_ACT1_UNPOOLED / 4 / 6   ReLU output of conv2 / conv5 / conv7 BEFORE its MaxPool (what the pooling backward reads;
+ *                                  sg_an_debug_activation returns the pooled tensor)                   1, B, Tout_l, Cout_l
+ * dims (4 host int32, may be NULL) is filled whether or not out_dev is NULL.  Read only: launches nothing but the copy.
+ * SG_ERR_STATE unless the context's last AudioNet pass was such a call: the fused forms (the default) keep these tensors in
+ * LDS, and a forward-only call, a device loop, a front-end call or a rebuilt workspace since leave the buffers stale.
+ * SG_ERR_ARG for an unknown `which` and, with out_dev, a capacity below the buffer's size. */
+#define SG_AN_GRAD_DACT1 0
+#define SG_AN_GRAD_DPOOL1 7
+#define SG_AN_GRAD_DPOOL4 8
+#define SG_AN_GRAD_DPOOL6 9
+#define SG_AN_GRAD_DPRE 10
+#define SG_AN_GRAD_PRE 11
+#define SG_AN_GRAD_ACT1_UNPOOLED 12
+#define SG_AN_GRAD_ACT4_UNPOOLED 13
+#define SG_AN_GRAD_ACT6_UNPOOLED 14
+int sg_an_debug_gradient(sg_ctx* ctx, int32_t which, float* out_dev, int64_t capacity_floats, int32_t* dims,
+                         void* stream);
 /* attack/FGSM.py:38-70 attack_batch on AudioNet, whole loop on the device (params->dither ignored).
  * On a non-zero return x_adv_dev is UNSPECIFIED (the loop steps between two buffers when the overlap-add runs inside the
  * adjoint; an error in the middle leaves the caller's buffer on an earlier iterate): discard it with the error. */

@@ -61,3 +61,35 @@ void sg_feco_scores(const float* xc, const float* cc, const float* h, float* out
             out[(size_t)i * k + j] = acc;
         }
 }
+
+/* AudioNet's 5 x 5 pre-filter (speakerguard_amd/csrc/k_audionet.hip an_prefilter_kernel; reference model/audionet_csine.py
+ * conv1 + BatchNorm folded by the loader) as ONE fmaf chain of 25 terms per output, started from the bias, in the kernel's
+ * order: mel offset i outer, time offset j inner, weight w25[5 i + j]; a sample outside the 32 mel bands or the utterance's T
+ * frames enters as zero (the fmaf is still executed).  transpose != 0: the data gradient -- the sample at (t - j + 2, m - i + 2),
+ * started from 0 (the bias argument is ignored, as the kernel ignores it).  in / out (B, T, 32).
+ * sg_prefilter_chain_defect is the same loop with a planted defect, for tests/test_an_stages_power.py alone (defect 1: the mel
+ * edge clamped to bands 0 / 31 instead of zero-padded), so that the planted value is itself an exact fmaf chain. */
+static void prefilter_chain(const float* in, int B, int T, const float* w25, float bias, int transpose, int defect, float* out) {
+#pragma omp parallel for schedule(static)
+    for (long bt = 0; bt < (long)B * T; ++bt) {
+        const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
+        const float* x = in + (size_t)b * T * 32;
+        for (int m = 0; m < 32; ++m) {
+            float acc = transpose ? 0.f : bias;
+            for (int i = 0; i < 5; ++i)
+                for (int j = 0; j < 5; ++j) {
+                    const int mm = transpose ? m - i + 2 : m + i - 2, tt = transpose ? t - j + 2 : t + j - 2;
+                    const int mc = mm < 0 ? 0 : (mm > 31 ? 31 : mm);
+                    const int ok = (defect == 1 || mm == mc) && tt >= 0 && tt < T;
+                    acc = fmaf(w25[i * 5 + j], ok ? x[(size_t)tt * 32 + mc] : 0.f, acc);
+                }
+            out[(size_t)bt * 32 + m] = acc;
+        }
+    }
+}
+void sg_prefilter_chain(const float* in, int B, int T, const float* w25, float bias, int transpose, float* out) {
+    prefilter_chain(in, B, T, w25, bias, transpose, 0, out);
+}
+void sg_prefilter_chain_defect(const float* in, int B, int T, const float* w25, float bias, int transpose, int defect, float* out) {
+    prefilter_chain(in, B, T, w25, bias, transpose, defect, out);
+}

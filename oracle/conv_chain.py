@@ -20,6 +20,10 @@ def _load():
         _lib = C.CDLL(_SO)
         _lib.sg_conv_chain.restype = None
         _lib.sg_feco_scores.restype = None
+        _lib.sg_prefilter_chain.restype = None
+        _lib.sg_prefilter_chain.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
+        _lib.sg_prefilter_chain_defect.restype = None
+        _lib.sg_prefilter_chain_defect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]
     return _lib
 
 
@@ -50,4 +54,21 @@ def feco_scores(xc, cc, h):
     out = np.empty((F, k), np.float32)
     _load().sg_feco_scores(xc.ctypes.data_as(C.c_void_p), cc.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p),
                            out.ctypes.data_as(C.c_void_p), F, k, Dp)
+    return out
+
+
+def prefilter_chain(x, w25, bias=0.0, transpose=False, defect=0):
+    """AudioNet's 5 x 5 pre-filter (an_prefilter_kernel): x (B, T, 32), w25 (25,) [mel offset][time offset] float32 -> (B, T, 32)
+    float32, one 25-term fmaf chain per output from ``bias`` (zero pad in mel and in time); ``transpose``: the data gradient
+    (the flipped kernel, from 0).  ``defect`` (the power test only): 1 = the mel edge clamped instead of zero-padded."""
+    x = np.ascontiguousarray(x, np.float32)
+    w25 = np.ascontiguousarray(w25, np.float32).reshape(25)
+    B, T, M = x.shape
+    assert M == 32
+    out = np.empty_like(x)
+    args = (x.ctypes.data_as(C.c_void_p), B, T, w25.ctypes.data_as(C.c_void_p), float(np.float32(bias)), int(bool(transpose)))
+    if defect:
+        _load().sg_prefilter_chain_defect(*args, int(defect), out.ctypes.data_as(C.c_void_p))
+    else:
+        _load().sg_prefilter_chain(*args, out.ctypes.data_as(C.c_void_p))
     return out

@@ -36,11 +36,14 @@ EXPORTS = (
     "sg_iv_forward", "sg_iv_loss",
     "sg_iv_loss_grad", "sg_iv_extract_backward", "sg_iv_stats_backward", "sg_iv_delta_cmvn_backward",
     "sg_feco_kmeans_compress_wide",
-    "sg_xv_debug_gradient",
+    "sg_xv_debug_gradient", "sg_an_debug_gradient",
     "sg_xv_forward_ragged", "sg_xv_loss_grad_ragged", "sg_xv_pgd_run_ragged",
 )
 # `which` of sg_xv_debug_gradient (SG_GRAD_* of the header); "dact1" .. "dact5" = SG_GRAD_DACT1 + l - 1
 SG_GRAD = dict({"demb": 0, "dstats": 6, "dfeats": 7, "dfeats_raw": 8}, **{"dact%d" % l: l for l in range(1, 6)})
+# `which` of sg_an_debug_gradient (SG_AN_GRAD_*); "dact1" .. "dact7" = SG_AN_GRAD_DACT1 + l - 1 (conv2 .. conv8)
+SG_AN_GRAD = dict({"dpool1": 7, "dpool4": 8, "dpool6": 9, "dpre": 10, "pre": 11, "act1_unpooled": 12, "act4_unpooled": 13,
+                   "act6_unpooled": 14}, **{"dact%d" % l: l - 1 for l in range(1, 8)})
 
 # stage tags of sg_trace_end (include/speakerguard_hip.h); +l / -l = forward / data-gradient contraction of TDNN layer l
 STAGE_NAMES = {10: "mfcc_fwd", 11: "cmvn_fwd", 12: "pool_fwd", 13: "fc1_fwd", 14: "tail", 15: "fc1_bwd", 16: "pool_bwd",
@@ -218,6 +221,7 @@ def load():
         "sg_an_forward": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "sg_an_debug_activation": (C.c_int, [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), vp]),
         "sg_an_loss_grad": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(LossSpec), vp, vp, vp, vp, vp]),
+        "sg_an_debug_gradient": (C.c_int, [vp, i32, vp, i64, C.POINTER(i32), vp]),
         "sg_an_pgd_run": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), vp, vp, vp, vp, vp, vp, vp]),
         "sg_an_pgd_run_feco": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(PgdParams), C.POINTER(FecoParams), vp, vp, vp,
                                          vp, vp, vp, vp]),

@@ -187,6 +187,7 @@ struct AnDims {
 
 int an_check(sg_ctx* ctx, int B, int TF, int flag, AnDims* d) {
     if (!ctx) return SG_ERR_ARG;
+    ctx->an_ws.grad_B = 0;  // a pass starts: the buffers of the last gradient call are no longer its own
     if (!ctx->an.loaded) return fail(ctx, SG_ERR_STATE, "no AudioNet model loaded (call sg_an_load)");
     SG_HIP(hipSetDevice(ctx->device));
     if (B < 1) return fail(ctx, SG_ERR_ARG, "B must be >= 1");
@@ -790,8 +791,49 @@ int sg_an_loss_grad(sg_ctx* ctx, const float* x_dev, const int64_t* y_dev, int32
     }
     const AnHeadArgs head = an_head_args(ctx, y_dev, *loss, 0, nullptr, scores_dev, decisions_dev, loss_dev, nullptr, nullptr, nullptr);
     float* dfeats = !grad_dev ? nullptr : flag == 1 ? grad_dev : w.dfeats;
-    if ((rc = an_net_step(ctx, plan, feats, B, head, nullptr, dfeats, s)) || !grad_dev || flag == 1) return rc;
-    return an_frontend_backward(ctx, x_dev, d, w.dfeats, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s);
+    if ((rc = an_net_step(ctx, plan, feats, B, head, nullptr, dfeats, s)) || !grad_dev) return rc;
+    if (flag == 0 && (rc = an_frontend_backward(ctx, x_dev, d, w.dfeats, grad_dev, nullptr, nullptr, nullptr, nullptr, 0.f, 0, s))) return rc;
+    if (plan.form == AN_PER_LAYER) { w.grad_B = B; w.grad_F = d.F; }  // what sg_an_debug_gradient may read back
+    return SG_OK;
+}
+
+int sg_an_debug_gradient(sg_ctx* ctx, int32_t which, float* out_dev, int64_t capacity_floats, int32_t* dims, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    const AnWorkspace& w = ctx->an_ws;
+    if (!w.scale || w.grad_B < 1)
+        return fail(ctx, SG_ERR_STATE, "sg_an_debug_gradient: the last AudioNet pass on this context was not an sg_an_loss_grad call with a gradient "
+                                       "in the per-layer form (the fused forms keep these tensors in LDS)");
+    const int B = w.grad_B, F = w.grad_F;
+    int Tin[kAnConv], Tout[kAnConv];
+    an_layer_frames(F, Tin, Tout);
+    static const int kPooled[3] = {0, 3, 5};  // conv2, conv5, conv7: the layers with a MaxPool (kAnPool)
+    const float* src = nullptr;
+    int rows = 0, cols = 0;
+    if (which >= SG_AN_GRAD_DACT1 && which < SG_AN_GRAD_DACT1 + kAnConv) {
+        const int l = which - SG_AN_GRAD_DACT1;
+        src = w.dact[l]; rows = Tout[l]; cols = kAnCout[l];
+    }
+    else if (which >= SG_AN_GRAD_DPOOL1 && which <= SG_AN_GRAD_DPOOL6) {
+        const int l = kPooled[which - SG_AN_GRAD_DPOOL1];
+        src = w.dpool[l]; rows = Tout[l] / 2; cols = kAnCout[l];
+    }
+    else if (which == SG_AN_GRAD_DPRE) { src = w.dpre; rows = F; cols = kAnMel; }
+    else if (which == SG_AN_GRAD_PRE) { src = w.pre; rows = F; cols = kAnMel; }
+    else if (which >= SG_AN_GRAD_ACT1_UNPOOLED && which <= SG_AN_GRAD_ACT6_UNPOOLED) {
+        const int l = kPooled[which - SG_AN_GRAD_ACT1_UNPOOLED];
+        src = w.act[l]; rows = Tout[l]; cols = kAnCout[l];
+    }
+    else return fail(ctx, SG_ERR_ARG, "sg_an_debug_gradient: unknown buffer %d", which);
+    if (dims) { dims[0] = 1; dims[1] = B; dims[2] = rows; dims[3] = cols; }
+    if (out_dev) {
+        // the pass fits its workspace (B <= w.B, F <= w.F) and every buffer is one contiguous run at the pass's own strides
+        const size_t n = (size_t)B * rows * cols;
+        if (capacity_floats < 0 || (size_t)capacity_floats < n)
+            return fail(ctx, SG_ERR_ARG, "sg_an_debug_gradient: capacity of %lld floats, the buffer holds %zu", (long long)capacity_floats, n);
+        SG_HIP(hipSetDevice(ctx->device));
+        SG_HIP(hipMemcpyAsync(out_dev, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return SG_OK;
 }
 
 int sg_an_pgd_run(sg_ctx* ctx, float* x_adv_dev, const int64_t* y_dev, const float* lower_dev, const float* upper_dev,

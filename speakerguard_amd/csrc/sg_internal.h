@@ -177,6 +177,9 @@ struct AnWorkspace {
     // frames entering / leaving each conv (before pooling) of the LAST pass (an_net_step writes them): what
     // sg_an_debug_activation reports.  No decision reads them.
     int Tin[kAnConv] = {}, Tout[kAnConv] = {};
+    // B and F of the sg_an_loss_grad call whose per-layer forward and backward buffers are still in place
+    // (sg_an_debug_gradient); grad_B == 0: none -- cleared by every later pass (an_check) and with the workspace itself
+    int grad_B = 0, grad_F = 0;
     float* scale = nullptr;
     float* feats = nullptr;    // (B, F, 32) log-mel
     float* pre = nullptr;      // (B, F, 32) pre-filter output

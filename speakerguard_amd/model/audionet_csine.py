@@ -137,6 +137,20 @@ class audionet_csine(EngineOps):
                       self._stream())
         return outs
 
+    def read_gradient(self, what):
+        """A buffer of the last ``loss_grad`` call's per-layer pass (sg_an_debug_gradient; parity tests), (B, rows, C) channel-last
+        as that pass wrote it: 'dact1' .. 'dact7' (d loss / d pre-activation of conv2 .. conv8), 'dpool1' / 'dpool4' / 'dpool6',
+        'dpre', 'pre', and the un-pooled 'act1_unpooled' / 'act4_unpooled' / 'act6_unpooled'.  Refused (NativeError) unless that
+        call was the last pass of this model and ran the per-layer launch sequence (the fused forms keep these tensors on chip).
+        An integer is passed to the library as it is (the refusal of an unknown buffer is the library's)."""
+        which = N.SG_AN_GRAD[what] if isinstance(what, str) else int(what)
+        dims = (C.c_int32 * 4)()
+        self.ctx.call("sg_an_debug_gradient", which, None, 0, dims, self._stream())
+        _, B, rows, cols = (int(v) for v in dims)
+        out = torch.empty(B, rows, cols, device=self.device, dtype=torch.float32)
+        self.ctx.call("sg_an_debug_gradient", which, N._ptr(out), out.numel(), None, self._stream())
+        return out
+
     def _feco_params(self, feco, T):
         """sg_feco_params of one fused call: one key per call, from the model's noise bookkeeping (attack call, restart, call
         number); the passes inside derive theirs from it; a row is keyed by its utterance's GLOBAL index (chunk base + row)"""

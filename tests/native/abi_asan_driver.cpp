@@ -599,6 +599,35 @@ int main(int argc, char** argv) {
             EXPECT(sg_an_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, dec.data(), sc.data(), loss.data(), grad.data(), nullptr) == SG_OK);
             unsetenv("SG_AN_FUSED");
             EXPECT(hipdouble_launches() - l2 > fused / 2 + 10);  // ~28 launches per pass pair against ~8
+            // the workspace of that per-layer call (sg_an_debug_gradient): exact-size destinations, so the sanitizer sees any overrun
+            int32_t dm[4] = {-1, -1, -1, -1};
+            const long l3 = hipdouble_launches();
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, nullptr, 0, dm, nullptr) == SG_OK && dm[0] == 1 && dm[1] == B && dm[2] == Fa && dm[3] == 32);
+            std::vector<float> dpre((size_t)B * Fa * 32);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, dpre.data(), (int64_t)dpre.size(), nullptr, nullptr) == SG_OK);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_PRE, dpre.data(), (int64_t)dpre.size() + 3, nullptr, nullptr) == SG_OK);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, dpre.data(), (int64_t)dpre.size() - 1, nullptr, nullptr) == SG_ERR_ARG);  // too small: refused, not cut
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, dpre.data(), 0, nullptr, nullptr) == SG_ERR_ARG);
+            for (int which = SG_AN_GRAD_DACT1; which <= SG_AN_GRAD_ACT6_UNPOOLED; ++which) {
+                EXPECT(sg_an_debug_gradient(ctx, which, nullptr, 0, dm, nullptr) == SG_OK && dm[1] == B && dm[2] >= 1 && dm[3] >= 32);
+                std::vector<float> buf((size_t)dm[1] * dm[2] * dm[3]);
+                EXPECT(sg_an_debug_gradient(ctx, which, buf.data(), (int64_t)buf.size(), nullptr, nullptr) == SG_OK);
+            }
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DACT1 + 6, nullptr, 0, dm, nullptr) == SG_OK && dm[3] == 32);   // conv8
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPOOL1, nullptr, 0, dm, nullptr) == SG_OK && dm[2] == Fa / 2 && dm[3] == 64);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_ACT1_UNPOOLED, nullptr, 0, dm, nullptr) == SG_OK && dm[2] == Fa && dm[3] == 64);
+            EXPECT(sg_an_debug_gradient(ctx, 15, nullptr, 0, dm, nullptr) == SG_ERR_ARG && sg_an_debug_gradient(ctx, -1, nullptr, 0, dm, nullptr) == SG_ERR_ARG);
+            EXPECT(sg_an_debug_gradient(nullptr, SG_AN_GRAD_DPRE, nullptr, 0, dm, nullptr) != SG_OK);
+            EXPECT(hipdouble_launches() == l3);  // copies only
+            // a fused gradient call, a forward-only call and a front-end call since: refused
+            EXPECT(sg_an_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, dec.data(), sc.data(), loss.data(), grad.data(), nullptr) == SG_OK);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, dpre.data(), (int64_t)dpre.size(), dm, nullptr) == SG_ERR_STATE);
+            setenv("SG_AN_FUSED", "0", 1);
+            EXPECT(sg_an_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, dec.data(), sc.data(), loss.data(), grad.data(), nullptr) == SG_OK);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, nullptr, 0, dm, nullptr) == SG_OK);
+            EXPECT(sg_an_loss_grad(ctx, x.data(), y.data(), B, T, 0, &ce, dec.data(), sc.data(), loss.data(), nullptr, nullptr) == SG_OK);
+            EXPECT(sg_an_debug_gradient(ctx, SG_AN_GRAD_DPRE, nullptr, 0, dm, nullptr) == SG_ERR_STATE);
+            unsetenv("SG_AN_FUSED");
         }
         EXPECT(sg_an_logmel_backward(ctx, x.data(), B, T, fe.data(), grad.data(), 1, nullptr) == SG_OK);
         pp = sg_pgd_params{};

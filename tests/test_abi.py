@@ -114,6 +114,17 @@ def test_gradient_buffer_ids_match_the_header():
     assert "sg_xv_debug_gradient" in _native.EXPORTS and declared("sg_xv_debug_gradient")[1][-2:] == ["int32_t*", "void*"]
 
 
+def test_audionet_gradient_buffer_ids_match_the_header():
+    """``_native.SG_AN_GRAD`` (the names ``audionet_csine.read_gradient`` takes) against the SG_AN_GRAD_* of sg_an_debug_gradient"""
+    ids = {k: int(v) for k, v in re.findall(r"#define\s+SG_AN_GRAD_(\w+)\s+(\d+)", header_text())}
+    assert ids == {"DACT1": 0, "DPOOL1": 7, "DPOOL4": 8, "DPOOL6": 9, "DPRE": 10, "PRE": 11, "ACT1_UNPOOLED": 12,
+                   "ACT4_UNPOOLED": 13, "ACT6_UNPOOLED": 14}
+    want = {k.lower(): v for k, v in ids.items() if k != "DACT1"}
+    want.update({"dact%d" % l: ids["DACT1"] + l - 1 for l in range(1, 8)})  # conv2 .. conv8
+    assert _native.SG_AN_GRAD == want and sorted(want.values()) == list(range(15))
+    assert "sg_an_debug_gradient" in _native.EXPORTS and declared("sg_an_debug_gradient")[1][-2:] == ["int32_t*", "void*"]
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     monkeypatch.setattr(_native, "_lib", None)
     monkeypatch.setattr(_native, "LIB_PATH", str(tmp_path / "nope.so"))

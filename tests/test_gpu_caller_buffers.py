@@ -339,6 +339,22 @@ def case_an_loss_grad(e):
     return out
 
 
+@sweeps("sg_an_debug_gradient")
+def case_an_debug_gradient(e):
+    """the workspace readback of a per-layer gradient call (the fused forms keep these tensors on chip: SG_AN_FUSED=0)"""
+    y, had = torch.tensor([3, 200], device=e.dev), os.environ.get("SG_AN_FUSED")
+    os.environ["SG_AN_FUSED"] = "0"
+    try:
+        out = named("feat", e.an.loss_grad(e.rand(2, 101, 32, seed=2, scale=4.0), y, ce(), flag=1), ("dec", "scores", "loss", "grad"))
+        out.update({k: e.an.read_gradient(k) for k in ("dact7", "dpool4", "dpre", "pre", "act1_unpooled")})
+    finally:
+        if had is None:
+            del os.environ["SG_AN_FUSED"]
+        else:
+            os.environ["SG_AN_FUSED"] = had
+    return out
+
+
 @sweeps("sg_an_pgd_run")
 def case_an_pgd_run(e):
     out = {}
