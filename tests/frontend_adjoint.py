@@ -21,6 +21,11 @@ cotangent, a one-hot one that lights a single edge frame included.  Here:
 * ``judge(got, yard, g64)`` -- the per-utterance rule of tests/truth.py (POLICY's C, FLOOR_UTT, FLOOR_BLOCK, TAU, unchanged; the
   rule ``xv_backward.judge`` applies) over 160-sample blocks, plus: where the float64 truth is exactly 0 the judged value is
   exactly 0 (a frame with a zero cotangent contributes zeros in exact arithmetic).  Every element of every row is judged.
+* the floors -- ``FLOOR_CASES``: digital silence written over the utterances (``FLOOR_LAYOUTS``, ``apply_layout``) so that both
+  logarithms take their floor, forward and backward; ``floor_report`` (what the oracle's floors see, in float64 and float32, and
+  the silent frames), ``forward_oracle`` / ``forward_candidate`` / ``forward_fails`` (the forward under the suite's own bounds)
+  and the slips ``floored_log`` plants by name (FLOOR_SLIPS); run by tests/test_gpu_frontend_floor.py, proved on the CPU by
+  tests/test_frontend_floor_power.py, which also states the condition on these inputs under which the VJP stays a truth.
 """
 import functools
 from collections import namedtuple
@@ -96,7 +101,7 @@ def an_num_frames(T):
 
 
 # ---------------------------------------------------------------------------------------------------------------- cases
-Case = namedtuple("Case", "model B T kind variant")  # model xv | iv | an; kind dense | onehot; variant None | int16 | noise
+Case = namedtuple("Case", "model B T kind variant")  # model xv | iv | an; kind dense | onehot; variant None | int16 | noise | a layout
 XV_LENGTHS = (5040, 5041, 5119, 5199, 5200, 16123)  # both sides of a frame-count step, right reflection of 41 .. 200 samples
 # (16 | 15, 48000): the two sides of B T >= 16 x 48000; (152, 5056): four samples per thread with both edges inside a 32-frame
 # utterance and 4864 frames > 512 blocks x 8 waves (the grid-stride loop iterates); (150, 5121): as large, T % 4 != 0
@@ -108,6 +113,66 @@ XV_CASES = tuple(Case("xv", B, T, k, None) for B, T in XV_SHAPES for k in ("dens
     Case("xv", 2, 5041, "dense", "int16"), Case("xv", 2, 5041, "dense", "noise"))
 IV_CASES = tuple(Case("iv", 2, T, k, None) for T in XV_SHORT for k in ("dense", "onehot"))
 AN_CASES = tuple(Case("an", B, T, k, None) for B, T in AN_SHAPES for k in ("dense", "onehot"))
+
+# ---- digital silence: spans of exact zeros written over the utterance after it is generated, so that both log floors are
+# taken, forward and backward (tests/test_frontend_floor_power.py states the condition these inputs meet, tests/
+# test_gpu_frontend_floor.py runs them).  A layout is a list of (start, stop, value) spans of row 0; row r moves every
+# boundary that is not an end of the utterance by ROW_SHIFT r samples, so the rows sit at different frame phases.
+ROW_SHIFT = 53
+FLOOR_LAYOUTS = {  # T -> spans; None as a bound: that end of the utterance
+    "gap": lambda T: [(T // 3, T // 3 + 2000, 0.0)],
+    "lead": lambda T: [(None, 1500, 0.0)],
+    "trail": lambda T: [(T - 1500, None, 0.0)],
+    "edges": lambda T: [(None, 1500, 0.0), (T - 1700, None, 0.0)],  # the zero-padded utterance: both reflections inside silence
+    "all": lambda T: [],  # row 0 entirely zero, row 1 untouched speech (the batch's range rule still says "scale")
+    # x-vector only: a hard clip at PGD's upper clamp.  32768 x 400 / 400 is exact in float32 and float64, so DC removal leaves
+    # exact zeros: raw samples nonzero, every floor taken.  (AudioNet has no DC removal; its windowed constant leaks ~1e-16.)
+    "plateau": lambda T: [(2000, 4000, 1.0)],
+    # AudioNet only: the last nonzero sample of the PRE-EMPHASISED signal (index s - 1 when x[s:] is zero) is column 0 of
+    # frame f, s = 160 f - 399, where the periodic Hann window is exactly 0: that frame's raw content is nonzero, its windowed
+    # content exactly zero.  (Only column 0 can do this -- the window's last tap is 1.5e-5 --, so the frame is the one where
+    # speech stops; read backwards in time, where it starts.)  Rows move by one hop, not by ROW_SHIFT: the alignment is the case.
+    "window0": lambda T: [(160 * ((T - 1500 + 399) // 160) - 399, None, 0.0)],
+    "lead480": lambda T: [(None, 480, 0.0)],  # the i-vector route at T = 720: frames 0 and 1 silent, frame 2 partial
+}
+XV_FLOOR_LAYOUTS = ("gap", "lead", "trail", "edges", "all", "plateau")
+AN_FLOOR_LAYOUTS = ("gap", "lead", "trail", "edges", "all", "window0")
+# Boundaries moved off the table above, {case: {row: samples}}.  None was needed for the condition on the pre-log values
+# (test_inputs_keep_clear_of_the_floor).  One for the condition that the truth does not depend on the CPU that built the
+# oracle's float32 mel bank (test_truths_do_not_depend_on_the_cpu_that_built_the_mel_bank): row 4 of (16, 48000) ``edges`` led
+# with 1712 zeros, which leaves frame 9 eight samples of speech under the last eight taps of the povey window (<= 0.0072); its
+# gradient on the 392 silent samples is what is left of a near-total cancellation across the spectrum, and two CPUs' mel banks
+# (they differ in 34 weights by at most 2.8e-6) move the float64 VJP there by 6.6e-4 of the row's RMS -- more than the bound.
+# Eight samples later the frame is silent.
+FLOOR_MOVES = {Case("xv", 16, 48000, "dense", "edges"): {4: 8}}
+XV_FLOOR_CASES = tuple(Case("xv", 2, T, "dense", v) for T in (5200, 16123) for v in XV_FLOOR_LAYOUTS) + tuple(
+    Case("xv", 2, T, "onehot", "gap") for T in (5200, 16123)) + (Case("xv", 16, 48000, "dense", "edges"),)
+IV_FLOOR_CASES = (Case("iv", 2, 720, "dense", "lead480"),)
+AN_FLOOR_CASES = tuple(Case("an", 2, T, "dense", v) for T in (4096, 16001) for v in AN_FLOOR_LAYOUTS) + tuple(
+    Case("an", 2, T, "onehot", "gap") for T in (4096, 16001))
+FLOOR_CASES = XV_FLOOR_CASES + IV_FLOOR_CASES + AN_FLOOR_CASES
+
+
+def apply_layout(x, layout, rows=None, moves=None):
+    """x (R, 1, T) float32, overwritten in place with `layout`'s spans; row r is shifted as batch row rows[r] (default r),
+    plus moves[row] samples (FLOOR_MOVES)"""
+    R, _, T = x.shape
+    rows = range(R) if rows is None else rows
+    for r, k in enumerate(rows):
+        if layout == "all":
+            if k == 0:
+                x[r] = 0.0
+            continue
+        shift = (AN_HOP if layout == "window0" else ROW_SHIFT) * k + (moves or {}).get(k, 0)
+        for a, b, value in FLOOR_LAYOUTS[layout](T):
+            a, b = 0 if a is None else a + shift, T if b is None else b + shift
+            assert 0 <= a < b <= T, (layout, T, k, a, b)
+            x[r, 0, a:b] = value
+    return x
+
+
+def is_floor_case(c):
+    return c.variant in FLOOR_LAYOUTS
 
 
 def case_id(c):
@@ -131,6 +196,17 @@ def inputs(c):
     D = {"xv": XV_CEPS, "iv": IV_CEPS, "an": AN_MEL}[c.model]
     seed = 7000 + c.B + c.T
     noise = None
+    if is_floor_case(c):
+        if c.kind == "dense":
+            x = apply_layout(synth.make_waveforms(c.B, c.T, seed=seed), c.variant, moves=FLOOR_MOVES.get(c))
+            return dict(x=x, cot=dense(c.B, F, D, seed + 1), noise=None, shared=False, n=c.B)
+        x = apply_layout(synth.make_waveforms(1, c.T, seed=seed), c.variant)
+        silent = sorted(f for _, f in silent_frames(c.model, x))
+        assert silent and silent == list(range(silent[0], silent[-1] + 1)) and 0 < silent[0] and silent[-1] < F - 1, silent
+        # the last speech frame before the silence, its first, a middle and its last frame, the first speech frame after it
+        frames = (silent[0] - 1, silent[0], silent[len(silent) // 2], silent[-1], silent[-1] + 1)
+        cot, n = one_hot_rows(F, D, frames, AN_ONE_HOT_BINS if c.model == "an" else XV_ONE_HOT_COLS)
+        return dict(x=np.repeat(x, cot.shape[0], 0), cot=cot, noise=None, shared=True, n=n)
     if c.kind == "dense":
         x = synth.make_waveforms(c.B, c.T, seed=seed)
         cot, n, shared = dense(c.B, F, D, seed + 1), c.B, False
@@ -175,6 +251,81 @@ def truths(c):
         g.setflags(write=False)
         out.append(g)
     return tuple(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the floors
+XV_FLOOR, AN_FLOOR = float(km.EPSILON), oan.EPSILON  # kEps of k_mfcc.hip (float32 eps), 1e-16f of k_audionet.hip
+
+
+def oracle_pre_log(model, x, dtype=torch.float64):
+    """what the oracle's floors see at x (R, 1, T) float32 as the engine receives it, in `dtype` -> (frame energies (R, F) or
+    None for AudioNet, mel energies (R, F, D)).  The oracle's own lines up to its clamp: oracle.kaldi_mfcc.mfcc's framing
+    (get_strided) and per-frame arithmetic (xv_forward_frames, bit-equal to it), oracle.audionet.preprocess's torch.stft;
+    tests/test_frontend_floor_power.py checks that the logarithm of these IS the oracle's output, bit for bit."""
+    w = torch.as_tensor(np.asarray(x, np.float32)).to(dtype)
+    if model == "an":
+        wav = oan.check_input_range(w, "scale").squeeze(1)
+        wav = wav[:, 1:] - oan.PREEMPH * wav[:, :-1]
+        spec = torch.stft(wav, n_fft=oan.N_FFT, hop_length=oan.HOP, win_length=oan.WIN, window=torch.hann_window(oan.WIN, dtype=dtype),
+                          center=True, pad_mode="reflect", return_complex=True)
+        mag = spec.real.pow(2) + spec.imag.pow(2)
+        mel = torch.matmul(mag.transpose(2, 1), torch.from_numpy(oan.mel_basis()).t().to(dtype))
+        return None, mel.numpy()
+    w = xv_input_range(w, "origin")
+    pairs = [xv_forward_frames(km.get_strided(w[r, 0]), pre_log=True) for r in range(w.shape[0])]
+    return np.stack([e.numpy() for e, _ in pairs]), np.stack([m.numpy() for _, m in pairs])
+
+
+def silent_frames(model, x):
+    """{(row, frame)} whose every pre-log value is exactly 0 in the float64 oracle"""
+    energy, mel = oracle_pre_log(model, x)
+    dead = (mel == 0).all(2) if energy is None else (mel == 0).all(2) & (energy == 0)
+    return {(int(r), int(f)) for r, f in zip(*np.nonzero(dead))}
+
+
+@functools.lru_cache(maxsize=None)
+def floor_report(c):
+    """-> dict(f64=(energy, mel), f32=(energy, mel), silent={(row, frame)}, floor): ``oracle_pre_log`` of the distinct waveforms
+    of inputs(c) (one for a one-hot family) in float64 and float32, the silent frames of the float64 one, the floor's value"""
+    i = inputs(c)
+    x = i["x"][:1] if i["shared"] else i["x"]
+    return dict(f64=oracle_pre_log(c.model, x), f32=oracle_pre_log(c.model, x, torch.float32), silent=silent_frames(c.model, x),
+                floor=AN_FLOOR if c.model == "an" else XV_FLOOR)
+
+
+def forward_oracle(c, dtype=torch.float32):
+    """the oracle's features at inputs(c), (R, F, D) in `dtype` (the i-vector route: the first 24 columns), as the forward
+    tests of the suite compute them: oracle.kaldi_mfcc.mfcc_batch / oracle.audionet.preprocess behind the range rule"""
+    x = torch.as_tensor(inputs(c)["x"]).to(dtype)
+    if c.model == "an":
+        return oan.preprocess(oan.check_input_range(x, "scale").squeeze(1)).transpose(1, 2).numpy()
+    return km.mfcc_batch(xv_input_range(x, "origin")).numpy()[:, :, :IV_CEPS if c.model == "iv" else XV_CEPS]
+
+
+def forward_candidate(c, defect=None):
+    """the engine's forward modelled in float64 (restated framing, restated per-frame forward), with a floor defect planted"""
+    x = inputs(c)["x"]
+    x = x.reshape(len(x), -1)
+    out = []
+    for r in range(1 if inputs(c)["shared"] else x.shape[0]):
+        if c.model == "an":
+            out.append(an_forward_frames(an_frames(x[r], input_scale(x, "scale")), defect).numpy())
+        else:
+            xs = torch.as_tensor(x[r].astype(np.float64)) * input_scale(x, "origin")
+            out.append(xv_forward_frames(xs[torch.as_tensor(xv_frame_index(x.shape[1]))], defect).numpy())
+    out = np.stack(out)[:, :, :IV_CEPS if c.model == "iv" else None]
+    return np.repeat(out, len(x), 0) if inputs(c)["shared"] else out
+
+
+def forward_fails(got, want, model):
+    """the suite's own forward bounds, unchanged: rtol 1e-4, atol 5e-3 (test_mfcc_matches_oracle); atol 8e-4 (the log-mel test)
+    -> a description of the failure, or None"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    if not np.isfinite(got).all():
+        return "%d non-finite features" % (~np.isfinite(got)).sum()
+    rtol, atol = (0.0, 8e-4) if model == "an" else (1e-4, 5e-3)
+    bad = np.abs(got - want) > atol + rtol * np.abs(want)
+    return "%d features off, the worst by %.3e" % (bad.sum(), np.abs(got - want).max()) if bad.any() else None
 
 
 # ---------------------------------------------------------------------------------------------------------------- judgement
@@ -272,15 +423,50 @@ def xv_scatter(df, T):
     return np.bincount(xv_frame_index(T).ravel(), weights=np.asarray(df, np.float64).ravel(), minlength=T)
 
 
-def xv_forward_frames(frames, defect=None):
+FLOOR_DEFECTS = ("floor_ungated", "floor_value", "floor_none")  # each must be caught on a floor case
+# floor_clamped: what exact silence cannot tell from the gate; floor_as_is: no slip, through the same natural-log expressions
+FLOOR_SLIPS = FLOOR_DEFECTS + ("floor_clamped", "floor_as_is")
+WRONG_FLOOR = 1e-10  # what floor_value floors at, in both front ends
+
+
+class _UngatedLog(torch.autograd.Function):
+    """log(max(v, floor)) whose backward divides by v itself (the adjoint without its ``v > floor ? . / v : 0`` gate) or, with
+    `clamped`, by max(v, floor) (the gate replaced by a clamped denominator)"""
+    @staticmethod
+    def forward(ctx, v, floor, clamped):
+        ctx.save_for_backward(v)
+        ctx.floor = floor if clamped else None
+        return torch.clamp(v, min=floor).log()
+
+    @staticmethod
+    def backward(ctx, g):
+        v = ctx.saved_tensors[0]
+        return g / (v if ctx.floor is None else torch.clamp(v, min=ctx.floor)), None, None
+
+
+def floored_log(v, floor, defect=None):
+    """log(max(v, floor)) as both oracles write it (torch.clamp: the adjoint is 0 below the floor), or with a planted slip:
+    floor_ungated (the backward divides by v without the gate: 0 / 0 or c / 0 on a silent frame), floor_value (the forward
+    floors at WRONG_FLOOR), floor_none (no floor at all: log 0), floor_clamped (the backward divides by max(v, floor))"""
+    if defect in ("floor_ungated", "floor_clamped"):
+        return _UngatedLog.apply(v, floor, defect == "floor_clamped")
+    if defect == "floor_none":
+        return v.log()
+    return torch.clamp(v, min=WRONG_FLOOR if defect == "floor_value" else floor).log()
+
+
+def xv_forward_frames(frames, defect=None, pre_log=False):
     """oracle.kaldi_mfcc.mfcc after the framing, on (F, 400) strided frames (dither added): equal to it when defect is None.
     A defect alters what the BACKWARD of this forward computes, as the named slip in mfcc_bwd_kernel would:
     no_dc_mean (the DC-removal mean dropped), no_energy (the energy path into c0 dropped), no_preemph_n0 (the n == 0 term of
-    the pre-emphasis adjoint dropped), lifter_1 / lifter_29 (the lifter missing on that column)"""
+    the pre-emphasis adjoint dropped), lifter_1 / lifter_29 (the lifter missing on that column); or one of FLOOR_DEFECTS at
+    both logarithms (``floored_log``, FLOOR_SLIPS).  pre_log: -> (frame energies (F,), mel energies (F, 30)), what the two floors see"""
     c = {k: v.to(frames.dtype) for k, v in km.constants().items()}
     mean = frames.mean(dim=1, keepdim=True)
     frames = frames - (mean.detach() if defect == "no_dc_mean" else mean)
-    energy = torch.clamp(frames.pow(2).sum(1), min=km.EPSILON).log()
+    floor_defect = defect if defect in FLOOR_SLIPS else None
+    raw_energy = frames.pow(2).sum(1)
+    energy = floored_log(raw_energy, km.EPSILON, floor_defect)
     if defect == "no_energy":
         energy = energy.detach()
     first = frames[:, :1].detach() if defect == "no_preemph_n0" else frames[:, :1]
@@ -289,7 +475,10 @@ def xv_forward_frames(frames, defect=None):
     spec = torch.fft.rfft(frames, dim=1)
     power = spec.real.pow(2) + spec.imag.pow(2)
     mel = torch.nn.functional.pad(c["mel"], (0, 1))
-    mel_energies = torch.clamp((power.unsqueeze(1) * mel.unsqueeze(0)).sum(dim=2), min=km.EPSILON).log()
+    mel_energies = (power.unsqueeze(1) * mel.unsqueeze(0)).sum(dim=2)
+    if pre_log:
+        return raw_energy, mel_energies
+    mel_energies = floored_log(mel_energies, km.EPSILON, floor_defect)
     feature = mel_energies.matmul(c["dct"])
     lifter = c["lifter"].clone()
     if defect in ("lifter_1", "lifter_29"):
@@ -501,33 +690,46 @@ def an_dx(dp0, dpm1, scale=1.0, defect=None):
     return (a - 0.97 * b) * scale
 
 
-def an_forward_frames(frames):
+def an_forward_frames(frames, defect=None, pre_log=False):
     """oracle.audionet.preprocess after pre-emphasis and framing: (F, 800) -> (F, 32) log-mel (the 800-tap window centred in
-    the 1024-point transform, as torch.stft places it)"""
+    the 1024-point transform, as torch.stft places it).  defect: one of FLOOR_DEFECTS; pre_log: -> the mel energies (F, 32)"""
     w = torch.hann_window(AN_WIN, dtype=frames.dtype)
     pad = (AN_FFT - AN_WIN) // 2
     spec = torch.fft.rfft(torch.nn.functional.pad(frames * w, (pad, pad)), dim=1)
     mag = spec.real.pow(2) + spec.imag.pow(2)
     mel = torch.as_tensor(oan.mel_basis()).to(frames.dtype)
-    return 10 * torch.clamp(mag.matmul(mel.t()), oan.EPSILON).log10()
+    energies = mag.matmul(mel.t())
+    if pre_log:
+        return energies
+    if defect is None:
+        return 10 * torch.clamp(energies, oan.EPSILON).log10()
+    return (10 / np.log(10.0)) * floored_log(energies, oan.EPSILON, defect)
 
 
-def an_dframes(x, cot, scale=None):
+def an_frames(x, scale, dtype=torch.float64):
+    """one row: x (T,) -> (F, 800) frames of the pre-emphasised signal by the restated index map"""
+    xs = torch.as_tensor(np.asarray(x, np.float32)).to(dtype) * scale
+    pre = xs[1:] - oan.PREEMPH * xs[:-1]
+    return pre[torch.as_tensor(an_frame_index(xs.shape[0]))]
+
+
+def an_dframes(x, cot, scale=None, defect=None):
     """one row: x (T,), cot (F, 32) -> ((F, 800) float64 d <cot, log-mel> / d frame of the pre-emphasised signal, the scale)"""
     scale = input_scale(x, "scale") if scale is None else scale
     xs = torch.as_tensor(np.asarray(x, np.float64)) * scale
     pre = xs[1:] - oan.PREEMPH * xs[:-1]
     frames = pre[torch.as_tensor(an_frame_index(xs.shape[0]))].clone().requires_grad_(True)
-    return torch.autograd.grad(an_forward_frames(frames), frames, torch.as_tensor(np.asarray(cot, np.float64)))[0].numpy(), scale
+    return torch.autograd.grad(an_forward_frames(frames, defect), frames, torch.as_tensor(np.asarray(cot, np.float64)))[0].numpy(), scale
 
 
-def an_candidate(x, cot, form="one", S=1, halo=AN_HALO, gather_defect=None, dx_defect=None):
-    """the engine modelled in float64: x (R, 1, T), cot (R, F, 32) -> (R, T); form one | quad | ola"""
+def an_candidate(x, cot, form="one", S=1, halo=AN_HALO, gather_defect=None, dx_defect=None, frame_defect=None):
+    """the engine modelled in float64: x (R, 1, T), cot (R, F, 32) -> (R, T); form one | quad | ola; frame_defect: one of
+    FLOOR_DEFECTS in the per-frame forward"""
     x = np.asarray(x).reshape(len(x), -1)
     scale, T = input_scale(x, "scale"), x.shape[1]
     out = []
     for r in range(x.shape[0]):
-        df, _ = an_dframes(x[r], cot[r], scale)
+        df, _ = an_dframes(x[r], cot[r], scale, frame_defect)
         dp0, dpm1 = (an_form_one(df, T, gather_defect) if form == "one" else
                      an_form_quad(df, T, gather_defect) if form == "quad" else an_form_ola(df, T, S, halo))
         out.append(an_dx(dp0, dpm1, scale, dx_defect))
