@@ -36,7 +36,9 @@ $(LIB): $(OBJS)
 # (tests/native/hip_host_double.cpp: test infrastructure) so that argument validation, table builders, weight folding /
 # packing, workspace sizing and launch selection all execute under AddressSanitizer + UBSan.  No GPU sanitizer involved.
 ASAN_DIR   := build/asan
-ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-sanitize-recover=all \
+# (-fno-sanitize=function: a kernel's host-side handle is not a function, and UBSan's function-type check silently drops a
+# launch made through a kernel pointer -- the double would never see it)
+ASAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-sanitize=function -fno-sanitize-recover=all \
               -fno-omit-frame-pointer -Iinclude -Wall -Wno-unused-function
 ASAN_OBJS  := $(patsubst $(CSRC)/%.hip,$(ASAN_DIR)/%.o,$(SRCS))
 DRIVERS    := abi_asan_driver defended_asan_driver an_defended_asan_driver xv_feco_asan_driver feco_cos_asan_driver \

@@ -71,73 +71,8 @@ __device__ int g_feco_ablate;  // experiment builds only (never the shipped libr
 #define FECO_CYCLES(i) \
     if (g_feco_tr.on && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) g_feco_tr.t[4 * kFecoTraceIters + 4 + (i)] = __builtin_readcyclecounter();
 
-constexpr int kFecoMaxD = 64;
-constexpr int kFecoThreads = 1024;
-constexpr int kFecoMaxChunks = 8;     // centroid-tile chunks a frame tile is cut into (JC)
-constexpr int kFecoMergeCap = 2048;   // JC * F <= this: capacity rule of the chunk-maxima arrays
-__host__ __device__ constexpr int al4(int n) { return (n + 3) & ~3; }
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// Which units of the assignment a wave computes (host-built): u[wave][slot] = frame tile | first centroid tile << 8 | one
-// past the last << 16 | chunk index << 24, kFecoNoUnit = none; table == 0: more than 32 units, dealt round robin in the kernel.
-constexpr unsigned kFecoNoUnit = 0xFFFFFFFFu;
-struct FecoSched {
-    int table;
-    unsigned u[kFecoThreads / 64][2];
-};
-
-// Two CUs per instance (round 5, VERDICT r4 item 1: "off the single CU").  An instance's k-means is bound by the MFMA +
-// VALU issue of the four SIMDs of the one CU its block gets, and a batch of 64 x 2 instances leaves half of the chip idle.
-// With `on` the grid's z dimension is the HALF: two blocks run the same instance redundantly -- same set-up, same lists,
-// same update, bit for bit -- and split only the assignment's units (sched / sched1; bit u of `owner` says whose unit
-// u = frame tile * JC + chunk is).  After its units a block stores its chunk maxima into its exchange buffer (two of them,
-// alternating by iteration) as self-describing 8-byte words -- score | index << 32 | tag << 43, tag = launch and iteration --
-// with write-through (sc1) stores, and polls the partner's words (sc1 loads) until they carry the tag it expects: one
-// store -> load visibility delay per iteration, no flag, no fence (the first version published a flag after draining the
-// stores: 3.2 us per iteration, as much as the split saved).  A word is accepted only with the exact tag, so stale or
-// overwritten data cannot be taken for the partner's; the buffers are zeroed when the launch counter wraps.
-// No block ever waits unboundedly, and no result depends on the partner showing up: if any word is not there after
-// kFecoPairWait the block computes the partner's units itself from then on (and says so in `flags`, which saves the
-// partner its own time-out).  The partner not showing up is what happens when something else occupies the GPU: same bits,
-// the single-CU speed (+ one time-out).
-struct FecoPair {
-    int on;
-    unsigned owner;
-    FecoSched sched1;
-    unsigned long long* xchg;  // [instance][half][buffer 0 / 1][kFecoMergeCap]
-    unsigned* flags;           // [instance][half]: launch id of the launch in which the block went on alone
-    unsigned tag0;             // this launch's tag base: (launch counter mod 2^15) << 6; a word's tag = tag0 + iteration + 1
-    unsigned launch;           // launch id
-    int drop;                  // test hook (sg_debug_lose_handoffs): half 1 publishes nothing
-};
-constexpr int kFecoPairMaxIter = 62;                // tag = 15 bits of launch counter, 6 of iteration
 constexpr unsigned long long kFecoPairWait = 2000;  // 20 us of the 100 MHz clock
-
-// Dynamic LDS of feco_kmeans_kernel in 4-byte words (every array 16-byte aligned); host and device use the same function.
-struct FecoLds {
-    int cq, hq, mu, part, ids, cnt, start, members, cw, spart, wtot, pd, pj, xq, total;
-};
-__host__ __device__ inline FecoLds feco_layout(int F, int k, int dpad, int JC, int fast_lists, int x_in_lds) {
-    const int kp = (k + 31) & ~31;
-    FecoLds L;
-    int o = 0;
-    L.cq = o; o += kp * dpad;              // centred centroids, [kp][dpad], 16-byte slots XOR-permuted per row
-    L.hq = o; o += kp;                     // -|c|^2 / 2
-    L.mu = o; o += dpad;
-    L.part = o; o += 16 * dpad;            // partial sums of the centring
-    L.ids = o; o += al4(F);
-    L.cnt = o; o += al4(k);
-    L.start = o; o += al4(k + 1);
-    L.members = o; o += al4(F);            // frames grouped by cluster, ascending inside a group
-    L.cw = o; o += fast_lists ? al4(((F + 63) >> 6) * k) : 0;   // members of cluster j among frames 64 c .. 64 c + 63
-    L.spart = o; o += fast_lists ? al4(k) : 0;                  // frames of the lower clusters of j's wave of clusters
-    L.wtot = o; o += fast_lists ? 16 : 0;                       // frames per wave of clusters
-    L.pd = o; o += JC > 1 ? al4(JC * F) : 0;                    // chunk maxima [chunk][frame]
-    L.pj = o; o += JC > 1 ? al4(JC * F) : 0;
-    L.xq = o; o += x_in_lds ? F * dpad : 0;                     // centred frames, same permuted rows
-    L.total = o;
-    return L;
-}
 
 // float offset of 16-byte slot `slot` of row `row` in a [rows][DPAD] image: the 16 lanes one ds_read_b128 cycle serves
 // (MI355X_MICROARCH.md, LDS: rows {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of a 32-row tile) hit 16 different slots
@@ -230,8 +165,6 @@ __global__ void feco_compress_bwd_reps_kernel(const float* __restrict__ dout, co
     dfeats[((size_t)b * F + i) * D + d] = acc;
 }
 
-constexpr size_t kFecoLdsMax = 150 * 1024;  // (feco_kmeans_impl)
-
 }  // namespace
 
 int sg::feco_kmeans_check(sg_ctx* ctx, int B, int F, int D, int k, int max_iter, int reps) {
@@ -244,11 +177,14 @@ int sg::feco_kmeans_check(sg_ctx* ctx, int B, int F, int D, int k, int max_iter,
     return SG_OK;
 }
 
+// the most instances a context's device can pair, and the exchange words they need
+static size_t feco_pair_instances(const sg_ctx* ctx) { return (size_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) / 2; }
+static size_t feco_xchg_words(const sg_ctx* ctx) { return feco_pair_instances(ctx) * 2 * 2 * kFecoMergeCap; }
+
 bool sg::feco_pair_buffers(sg_ctx* ctx) {
     if (ctx->feco_xchg) return true;
     if (ctx->feco_two_cu == 0) return false;
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const size_t inst_max = (size_t)cus / 2, words = inst_max * 2 * 2 * kFecoMergeCap;  // room for the most instances that can be paired
+    const size_t inst_max = feco_pair_instances(ctx), words = feco_xchg_words(ctx);
     void *px = nullptr, *pf = nullptr;
     if (hipMalloc(&px, words * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&pf, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
         hipMemset(pf, 0, inst_max * 2 * sizeof(unsigned)) == hipSuccess &&
@@ -266,148 +202,115 @@ bool sg::feco_pair_buffers(sg_ctx* ctx) {
     return false;
 }
 
-// metric: SG_FECO_L2 / SG_FECO_COS (checked by the caller) -- which instantiation runs; everything else is shared
-static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
-                            int metric, int seeded, int row_wise, uint64_t seed, int64_t index_base, int reps, int32_t* assign_dev,
-                            float* out_dev, int32_t* counts_dev, void* stream) {
-    if (!ctx) return SG_ERR_ARG;
-    if (!feats_dev || !assign_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
-    if (int rc = feco_kmeans_check(ctx, B, F, D, k, max_iter, reps)) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipSetDevice failed");
-    // LDS holds the centred centroids (rows padded to 32 / 64 floats), ids, member lists and -- when they fit -- the chunk
-    // counts of the fast member lists and the centred frames (else the frames are re-read from HBM / L2 in every step).
-    // 150 KB cover ~19 s at D <= 32, ratio 0.5 (F = 1930, k = 965); beyond that the call is refused.
-    constexpr size_t kLdsMax = kFecoLdsMax;
-    const int dpad = D <= 32 ? 32 : 64;
-    const int ntc = (k + 31) / 32;
-    // a frame tile's centroid tiles are cut into JC chunks (300 x 150: 10 frame tiles x 2 chunks of 3 / 2 tiles)
-    const int ntf = (F + 31) / 32;
-    int JC = (20 + ntf - 1) / ntf;  // >= 20 units for the 16 waves (5 per SIMD), each as many tiles as possible
-    JC = JC > ntc ? ntc : JC;
-    JC = JC > kFecoMaxChunks ? kFecoMaxChunks : JC;
-    while (JC > 1 && JC * F > kFecoMergeCap) --JC;
+// The pair state of one launch of a paired plan: the exchange buffers, this launch's id and tag base, the wipe when the tags
+// start over, the fault-injection budget
+static int feco_pair_begin(sg_ctx* ctx, hipStream_t s, FecoPair& pr) {
+    const unsigned launch = ++ctx->feco_epoch;  // (0 is what a fresh flag word holds: never a launch id)
+    if (launch == 0) ctx->feco_epoch = 1;
+    // tags repeat every 2^15 launches: the words of the last cycle are wiped before they could be taken for new ones
+    if ((ctx->feco_epoch & 0x7FFFu) == 1u && hipMemsetAsync(ctx->feco_xchg, 0, feco_xchg_words(ctx) * sizeof(unsigned long long), s) != hipSuccess)
+        return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipMemsetAsync failed");
+    pr.on = 1;
+    pr.xchg = ctx->feco_xchg;
+    pr.flags = ctx->feco_flags;
+    pr.launch = ctx->feco_epoch;
+    pr.tag0 = (ctx->feco_epoch & 0x7FFFu) << 6;
+    if (ctx->lose_feco > 0) {  // test hook (sg_debug_lose_handoffs): this launch's second halves publish nothing
+        pr.drop = 1;
+        --ctx->lose_feco;
+    }
+    return SG_OK;
+}
+
+static FecoKnobs feco_knobs(const sg_ctx* ctx) {
+    FecoKnobs knobs;
+    knobs.two_cu = ctx->feco_two_cu;
 #ifdef SG_EXP_FECO_JC
     if (const char* ev = sg_tune_env("SG_FECO_ABLATE")) { const int a = atoi(ev); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_feco_ablate), &a, sizeof(a)); }
-    if (const char* ev = sg_tune_env("SG_FECO_JC")) { JC = atoi(ev); JC = JC < 1 ? 1 : (JC > ntc ? ntc : JC); while (JC > 1 && JC * F > kFecoMergeCap) --JC; }
+    if (const char* ev = sg_tune_env("SG_FECO_JC")) knobs.jc = atoi(ev) < 1 ? 1 : atoi(ev);
 #endif
-    // two CUs per instance (FecoPair): same units as one block would get (cutting them finer -- 30 units of 1-2 tiles for
-    // the 32 waves -- measured 94.3 against 92.5 us per call: the SIMDs are throughput-bound, the merge grows)
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const bool pair_ok = ctx->feco_two_cu != 0 && dpad == 32 && 2 * (long)B * reps <= cus;
-    const int kp_host = (k + 31) & ~31;
-    auto bytes = [&](int jc, int fast, int xin) { return (size_t)feco_layout(F, k, dpad, jc, fast, xin).total * sizeof(float); };
-    if (bytes(JC, 0, 0) > kLdsMax) JC = 1;  // (one chunk fits: feco_kmeans_check)
-    // the assignment's units (frame tile, chunk jc of its centroid tiles [ntc jc / JC, ntc (jc + 1) / JC)) dealt to the waves:
-    // largest first, each to the least loaded SIMD (waves w, w + 4, w + 8, w + 12) and there to the least loaded wave with a
-    // free slot -- 300 x 150: 20 units of 2 / 3 tiles -> 12 / 13 / 12 / 13 tiles per SIMD
-    FecoSched sched{};
+    return knobs;
+}
+
+// tuning aid (SG_FECO_TRACE=1): arms the device switch on the first launch, reads back and prints the phases of every later one
+static void feco_trace_report(int max_iter, hipStream_t s) {
+    static const bool tr_on = sg_tune_env("SG_FECO_TRACE") != nullptr;
+    if (!tr_on) return;
+    static bool armed[kMaxDevices] = {};  // the switch is a device symbol: one per device
+    const int dslot = sg_device_slot();
+    if (!armed[dslot]) {
+        const int one = 1;
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_feco_tr), &one, sizeof(one), offsetof(FecoTraceDev, on));
+        armed[dslot] = true;
+        return;
+    }
+    unsigned long long h[4 * kFecoTraceIters + 4 + 24];
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_feco_tr), sizeof(h), offsetof(FecoTraceDev, t)) != hipSuccess)
+        return;
+    fprintf(stderr, "feco k-means phases (us), block (0, 0): set-up %.2f;", (h[0] - h[4 * kFecoTraceIters + 2]) * 0.01);
+    for (int it = 0; it < max_iter && it < kFecoTraceIters && h[4 * it + 1] > h[4 * it]; ++it)
+        fprintf(stderr, " it%d assign %.2f lists %.2f update %.2f;", it, (h[4 * it + 1] - h[4 * it]) * 0.01,
+                h[4 * it + 2] > h[4 * it + 1] ? (h[4 * it + 2] - h[4 * it + 1]) * 0.01 : 0.0,
+                h[4 * it + 3] > h[4 * it + 2] ? (h[4 * it + 3] - h[4 * it + 2]) * 0.01 : 0.0);
+    const unsigned long long* dt = h + 4 * kFecoTraceIters + 4;
+    fprintf(stderr, " [set-up: centring %.2f staging %.2f seeding %.2f init %.2f; it0: units %.2f merge %.2f | rank+count %.2f sizes+scan %.2f "
+            "slots %.2f zero %.2f; shader clock %.0f MHz]", (dt[0] - h[4 * kFecoTraceIters + 2]) * 0.01, (dt[1] - dt[0]) * 0.01,
+            (dt[2] - dt[1]) * 0.01, (h[0] - dt[2]) * 0.01, (dt[3] - h[0]) * 0.01, (h[1] - dt[3]) * 0.01, (dt[4] - h[1]) * 0.01,
+            (dt[5] - dt[4]) * 0.01, (dt[6] - dt[5]) * 0.01, (h[2] - dt[6]) * 0.01,
+            (double)(dt[21] - dt[20]) / ((h[4 * kFecoTraceIters] - dt[0]) * 0.01));
+    fprintf(stderr, " out %.2f; loop + out total %.2f\n", (h[4 * kFecoTraceIters + 1] - h[4 * kFecoTraceIters]) * 0.01, (h[4 * kFecoTraceIters + 1] - h[0]) * 0.01);
+}
+
+// the four instantiations share one signature: [metric][dpad == 64]
+using FecoKernel = void (*)(const float*, int, int, int, int, int, int, uint64_t, int64_t, int, int, int, FecoSched, FecoPair, int*, float*, int*);
+static const FecoKernel kFecoKernels[2][2] = {{feco_kmeans_kernel<32>, feco_kmeans_kernel<64>},
+                                              {feco_kmeans_cos_kernel<32>, feco_kmeans_cos_kernel<64>}};
+static_assert(SG_FECO_L2 == 0 && SG_FECO_COS == 1, "kFecoKernels is indexed by the metric");
+
+// What an entry point asks for beyond the shape.  `entry` is the name its refusals carry; out and counts (the means and sizes
+// of the clusters) are required of the compress entries
+struct FecoCall {
+    const char* entry;
+    int metric, seeded, row_wise;
+    uint64_t seed;
+    int64_t index_base;
+    int reps;
+    int32_t* assign;
+    float* out;
+    int32_t* counts;
+    bool compress;
+};
+
+static int feco_kmeans_impl(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k, int32_t max_iter,
+                            const FecoCall& c, void* stream) {
+    if (!ctx) return SG_ERR_ARG;
+    if (c.metric != SG_FECO_L2 && c.metric != SG_FECO_COS) return fail(ctx, SG_ERR_ARG, "%s: metric must be SG_FECO_L2 or SG_FECO_COS", c.entry);
+    if (c.row_wise != 0 && c.row_wise != 1) return fail(ctx, SG_ERR_ARG, "%s: row_wise must be 0 or 1", c.entry);
+    // the L2 metric of sg_feco_kmeans_compress_metric is the entries that exist, refusals and bits included
+    const char* who = !c.compress || c.metric == SG_FECO_COS ? c.entry : c.row_wise ? "sg_feco_kmeans_compress_rows" : "sg_feco_kmeans_compress";
+    if (c.compress && (!c.out || !c.counts)) return fail(ctx, SG_ERR_ARG, "%s: out and counts are required", who);
+    if (c.compress && !c.row_wise && c.reps > 1 && !c.seeded)
+        return fail(ctx, SG_ERR_ARG, "%s: repeats of the evenly started clustering coincide (reps must be 1)", who);
+    if (!feats_dev || !c.assign) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans: need 0 < k <= F, 0 < D <= %d, max_iter > 0", kFecoMaxD);
+    if (int rc = feco_kmeans_check(ctx, B, F, D, k, max_iter, c.reps)) return rc;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipSetDevice failed");
+    const hipStream_t s = (hipStream_t)stream;
+    const FecoKnobs knobs = feco_knobs(ctx);
+    FecoPlan plan = feco_plan(F, D, k, max_iter, (long)B * c.reps, ctx->num_cus, true, knobs);
+    if (plan.pair && !feco_pair_buffers(ctx)) plan = feco_plan(F, D, k, max_iter, (long)B * c.reps, ctx->num_cus, false, knobs);
     FecoPair pr{};
-    const int nunits = ntf * JC;
-    constexpr int kWaves = kFecoThreads / 64;
-    // two CUs per instance (FecoPair): when every instance can have two resident blocks, the units fit the tables and a bit
-    // mask, and the flag values have room for the iterations
-    if (pair_ok && JC > 1 && nunits <= 32 && max_iter <= kFecoPairMaxIter && kp_host <= 2048) {
-        const size_t inst_max = (size_t)cus / 2, words = inst_max * 2 * 2 * kFecoMergeCap;
-        if (feco_pair_buffers(ctx)) {
-            const unsigned launch = ++ctx->feco_epoch;  // (0 is what a fresh flag word holds: never a launch id)
-            if (launch == 0) ctx->feco_epoch = 1;
-            // tags repeat every 2^15 launches: the words of the last cycle are wiped before they could be taken for new ones
-            if ((ctx->feco_epoch & 0x7FFFu) == 1u &&
-                hipMemsetAsync(ctx->feco_xchg, 0, words * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
-                return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: hipMemsetAsync failed");
-            pr.on = 1;
-            pr.xchg = ctx->feco_xchg;
-            pr.flags = ctx->feco_flags;
-            pr.launch = ctx->feco_epoch;
-            pr.tag0 = (ctx->feco_epoch & 0x7FFFu) << 6;
-            if (ctx->lose_feco > 0) {  // test hook (sg_debug_lose_handoffs): this launch's second halves publish nothing
-                pr.drop = 1;
-                --ctx->lose_feco;
-            }
-        }
-    }
-    const int halves = pr.on ? 2 : 1;
-    if (nunits <= 2 * kWaves) {
-        sched.table = 1;
-        pr.sched1.table = 1;
-        // bins: the SIMDs of the block (of both blocks): a unit goes to the least loaded SIMD and there to the least loaded
-        // wave with a free slot
-        int simd_load[8] = {}, wave_load[2 * kWaves] = {}, wave_n[2 * kWaves] = {};
-        for (int w = 0; w < kWaves; ++w) sched.u[w][0] = sched.u[w][1] = pr.sched1.u[w][0] = pr.sched1.u[w][1] = kFecoNoUnit;
-        auto bin = [&](int w) { return (w / kWaves) * 4 + (w & 3); };
-        for (int size = ntc; size >= 1; --size)
-            for (int u = 0; u < nunits; ++u) {
-                const int ft = u / JC, jc = u - ft * JC, lo = ntc * jc / JC, hi = ntc * (jc + 1) / JC;
-                if (hi - lo != size) continue;
-                int best_w = -1;
-                for (int w = 0; w < halves * kWaves; ++w) {
-                    if (wave_n[w] >= 2) continue;
-                    if (best_w < 0 || simd_load[bin(w)] < simd_load[bin(best_w)] ||
-                        (simd_load[bin(w)] == simd_load[bin(best_w)] && wave_load[w] < wave_load[best_w]))
-                        best_w = w;
-                }
-                const unsigned word = (unsigned)ft | (unsigned)lo << 8 | (unsigned)hi << 16 | (unsigned)jc << 24;
-                if (best_w < kWaves) sched.u[best_w][wave_n[best_w]] = word;
-                else {
-                    pr.sched1.u[best_w - kWaves][wave_n[best_w]] = word;
-                    pr.owner |= 1u << u;
-                }
-                ++wave_n[best_w];
-                wave_load[best_w] += size;
-                simd_load[bin(best_w)] += size;
-            }
-    }
-    const int x_in_lds = bytes(JC, 0, 1) <= kLdsMax;
-    const int fast_lists = F <= kFecoThreads && bytes(JC, 1, x_in_lds) <= kLdsMax;
-    const size_t lds = bytes(JC, fast_lists, x_in_lds);
-    const bool cosine = metric == SG_FECO_COS;
-    const void* fn = cosine ? (dpad == 32 ? reinterpret_cast<const void*>(feco_kmeans_cos_kernel<32>)
-                                          : reinterpret_cast<const void*>(feco_kmeans_cos_kernel<64>))
-                            : (dpad == 32 ? reinterpret_cast<const void*>(feco_kmeans_kernel<32>)
-                                          : reinterpret_cast<const void*>(feco_kmeans_kernel<64>));
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+    pr.owner = plan.owner;
+    pr.sched1 = plan.sched1;
+    if (plan.pair)
+        if (int rc = feco_pair_begin(ctx, s, pr)) return rc;
+    const FecoKernel fn = kFecoKernels[c.metric][plan.dpad == 64];
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFecoLdsMax);
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
-    if (cosine && dpad == 32)
-        hipLaunchKernelGGL(feco_kmeans_cos_kernel<32>, dim3(B, reps, pr.on ? 2 : 1), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev,
-                           F, D, k, max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev,
-                           counts_dev);
-    else if (cosine)
-        hipLaunchKernelGGL(feco_kmeans_cos_kernel<64>, dim3(B, reps), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F, D, k,
-                           max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
-    else if (dpad == 32)
-        hipLaunchKernelGGL(feco_kmeans_kernel<32>, dim3(B, reps, pr.on ? 2 : 1), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F,
-                           D, k, max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
-    else
-        hipLaunchKernelGGL(feco_kmeans_kernel<64>, dim3(B, reps), dim3(kFecoThreads), lds, (hipStream_t)stream, feats_dev, F, D, k,
-                           max_iter, seeded, row_wise, seed, index_base, x_in_lds, fast_lists, JC, sched, pr, assign_dev, out_dev, counts_dev);
+    hipLaunchKernelGGL(fn, dim3(B, c.reps, plan.pair ? 2 : 1), dim3(kFecoThreads), plan.lds, s, feats_dev, F, D, k, max_iter, c.seeded, c.row_wise,
+                       c.seed, c.index_base, plan.x_in_lds, plan.fast_lists, plan.JC, plan.sched0, pr, c.assign, c.out, c.counts);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans: %s", hipGetErrorString(e));
-    static const bool tr_on = sg_tune_env("SG_FECO_TRACE") != nullptr;
-    if (tr_on) {
-        static bool armed[kMaxDevices] = {};  // the switch is a device symbol: one per device
-        const int dslot = sg_device_slot();
-        if (!armed[dslot]) {
-            const int one = 1;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_feco_tr), &one, sizeof(one), offsetof(FecoTraceDev, on));
-            armed[dslot] = true;
-        } else if (hipStreamSynchronize((hipStream_t)stream) == hipSuccess) {
-            unsigned long long h[4 * kFecoTraceIters + 4 + 24];
-            if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_feco_tr), sizeof(h), offsetof(FecoTraceDev, t)) == hipSuccess) {
-                fprintf(stderr, "feco k-means phases (us), block (0, 0): set-up %.2f;", (h[0] - h[4 * kFecoTraceIters + 2]) * 0.01);
-                for (int it = 0; it < max_iter && it < kFecoTraceIters && h[4 * it + 1] > h[4 * it]; ++it)
-                    fprintf(stderr, " it%d assign %.2f lists %.2f update %.2f;", it, (h[4 * it + 1] - h[4 * it]) * 0.01,
-                            h[4 * it + 2] > h[4 * it + 1] ? (h[4 * it + 2] - h[4 * it + 1]) * 0.01 : 0.0,
-                            h[4 * it + 3] > h[4 * it + 2] ? (h[4 * it + 3] - h[4 * it + 2]) * 0.01 : 0.0);
-                const unsigned long long* dt = h + 4 * kFecoTraceIters + 4;
-                fprintf(stderr, " [set-up: centring %.2f staging %.2f seeding %.2f init %.2f; it0: units %.2f merge %.2f | rank+count %.2f sizes+scan %.2f "
-                        "slots %.2f zero %.2f; shader clock %.0f MHz]", (dt[0] - h[4 * kFecoTraceIters + 2]) * 0.01, (dt[1] - dt[0]) * 0.01,
-                        (dt[2] - dt[1]) * 0.01, (h[0] - dt[2]) * 0.01, (dt[3] - h[0]) * 0.01, (h[1] - dt[3]) * 0.01, (dt[4] - h[1]) * 0.01,
-                        (dt[5] - dt[4]) * 0.01, (dt[6] - dt[5]) * 0.01, (h[2] - dt[6]) * 0.01,
-                        (double)(dt[21] - dt[20]) / ((h[4 * kFecoTraceIters] - dt[0]) * 0.01));
-                fprintf(stderr, " out %.2f; loop + out total %.2f\n", (h[4 * kFecoTraceIters + 1] - h[4 * kFecoTraceIters]) * 0.01, (h[4 * kFecoTraceIters + 1] - h[0]) * 0.01);
-            }
-        }
-    }
+    feco_trace_report(max_iter, s);
     return SG_OK;
 }
 
@@ -419,50 +322,36 @@ extern "C" int sg_feco_set_two_cu(sg_ctx* ctx, int32_t mode) {
 
 extern "C" int sg_feco_kmeans(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                               int32_t max_iter, int32_t* assign_dev, void* stream) {
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, SG_FECO_L2, 0, 0, 0, 0, 1, assign_dev, nullptr, nullptr, stream);
+    const FecoCall c{"sg_feco_kmeans", SG_FECO_L2, 0, 0, 0, 0, 1, assign_dev, nullptr, nullptr, false};
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, c, stream);
 }
 
 extern "C" int sg_feco_kmeans_seeded(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                      int32_t max_iter, uint64_t seed, int64_t index_base, int32_t* assign_dev, void* stream) {
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, SG_FECO_L2, 1, 0, seed, index_base, 1, assign_dev, nullptr, nullptr, stream);
+    const FecoCall c{"sg_feco_kmeans_seeded", SG_FECO_L2, 1, 0, seed, index_base, 1, assign_dev, nullptr, nullptr, false};
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, c, stream);
 }
 
 extern "C" int sg_feco_kmeans_compress(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                        int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base, int32_t reps,
                                        int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream) {
-    if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: out and counts are required");
-    if (reps > 1 && !random_init)
-        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress: repeats of the evenly started clustering coincide (reps must be 1)");
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, SG_FECO_L2, random_init != 0, 0, seed, index_base, reps, assign_dev, out_dev,
-                            counts_dev, stream);
+    const FecoCall c{"sg_feco_kmeans_compress", SG_FECO_L2, random_init != 0, 0, seed, index_base, reps, assign_dev, out_dev, counts_dev, true};
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, c, stream);
 }
 
 extern "C" int sg_feco_kmeans_compress_rows(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                             int32_t max_iter, int32_t random_init, uint64_t seed, int64_t index_base, int32_t reps,
                                             int32_t* assign_dev, float* out_dev, int32_t* counts_dev, void* stream) {
-    if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_rows: out and counts are required");
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, SG_FECO_L2, random_init != 0, 1, seed, index_base, reps, assign_dev, out_dev,
-                            counts_dev, stream);
+    const FecoCall c{"sg_feco_kmeans_compress_rows", SG_FECO_L2, random_init != 0, 1, seed, index_base, reps, assign_dev, out_dev, counts_dev, true};
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, c, stream);
 }
 
 extern "C" int sg_feco_kmeans_compress_metric(sg_ctx* ctx, const float* feats_dev, int32_t B, int32_t F, int32_t D, int32_t k,
                                               int32_t max_iter, int32_t metric, int32_t random_init, uint64_t seed, int64_t index_base,
                                               int32_t reps, int32_t row_wise, int32_t* assign_dev, float* out_dev, int32_t* counts_dev,
                                               void* stream) {
-    if (!ctx) return SG_ERR_ARG;
-    if (metric != SG_FECO_L2 && metric != SG_FECO_COS)
-        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_metric: metric must be SG_FECO_L2 or SG_FECO_COS");
-    if (row_wise != 0 && row_wise != 1) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_metric: row_wise must be 0 or 1");
-    if (metric == SG_FECO_L2)  // the entries that exist, refusals and bits included
-        return row_wise ? sg_feco_kmeans_compress_rows(ctx, feats_dev, B, F, D, k, max_iter, random_init, seed, index_base, reps, assign_dev,
-                                                       out_dev, counts_dev, stream)
-                        : sg_feco_kmeans_compress(ctx, feats_dev, B, F, D, k, max_iter, random_init, seed, index_base, reps, assign_dev,
-                                                  out_dev, counts_dev, stream);
-    if (!out_dev || !counts_dev) return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_metric: out and counts are required");
-    if (!row_wise && reps > 1 && !random_init)
-        return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_metric: repeats of the evenly started clustering coincide (reps must be 1)");
-    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, SG_FECO_COS, random_init != 0, row_wise, seed, index_base, reps,
-                            assign_dev, out_dev, counts_dev, stream);
+    const FecoCall c{"sg_feco_kmeans_compress_metric", metric, random_init != 0, row_wise, seed, index_base, reps, assign_dev, out_dev, counts_dev, true};
+    return feco_kmeans_impl(ctx, feats_dev, B, F, D, k, max_iter, c, stream);
 }
 
 extern "C" int sg_feco_compress(sg_ctx* ctx, const float* feats_dev, const int32_t* assign_dev, int32_t B, int32_t F,

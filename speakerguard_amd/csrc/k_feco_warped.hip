@@ -69,6 +69,19 @@ __host__ __device__ inline WarpLds warp_layout(int F, int k, int D, int means_in
     return L;
 }
 
+// What sg_feco_warped launches for a shape (pure) -- the instantiation <wide, xl, ml> and its dynamic LDS: the means live in LDS
+// when they fit, the frames when both fit
+struct FecoWarpedPlan {
+    int wide, xl, ml;
+    size_t lds;
+};
+inline FecoWarpedPlan feco_warped_plan(int F, int k, int D) {
+    const auto bytes = [&](int ml, int xl) { return (size_t)warp_layout(F, k, D, ml, xl).total * sizeof(float); };
+    const int ml = bytes(1, 0) <= kWarpLdsMax;
+    const int xl = ml && bytes(1, 1) <= kWarpLdsMax;
+    return {D > 32, xl, ml, bytes(ml, xl)};
+}
+
 __device__ __forceinline__ float rfl(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
@@ -337,13 +350,15 @@ __global__ __launch_bounds__(64) void feco_warped_kernel(const float* __restrict
 }
 
 template <bool WIDE, bool XL, bool ML>
-void launch_warped(int B, size_t lds, hipStream_t s, const float* feats, int F, int D, int k, int mode, double delta,
-                   uint64_t key, int64_t index_base, int rep_rows, int cap, int32_t* bnd, int32_t* ids, int32_t* counts,
-                   float* out, int32_t* sweeps) {
+hipError_t launch_warped(int B, size_t lds, hipStream_t s, const float* feats, int F, int D, int k, int mode, double delta,
+                         uint64_t key, int64_t index_base, int rep_rows, int cap, int32_t* bnd, int32_t* ids, int32_t* counts,
+                         float* out, int32_t* sweeps) {
     auto fn = feco_warped_kernel<WIDE, XL, ML>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fn, dim3(B), dim3(64), lds, s, feats, F, D, k, mode, delta, (unsigned long long)key,
                        (long long)index_base, rep_rows, cap, bnd, ids, counts, out, sweeps);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -362,18 +377,15 @@ extern "C" int sg_feco_warped(sg_ctx* ctx, const float* feats_dev, int32_t B, in
         return fail(ctx, SG_ERR_ARG, "sg_feco_warped: need init_mode 0 (ts) / 1 (random) / 2 (given), rep_rows >= 0, "
                          "0 <= delta <= 1");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_warped: hipSetDevice failed");
-    auto bytes = [&](int ml, int xl) { return (size_t)warp_layout(F, k, D, ml, xl).total * sizeof(float); };
-    const int ml = bytes(1, 0) <= kWarpLdsMax;
-    const int xl = ml && bytes(1, 1) <= kWarpLdsMax;
-    const size_t lds = bytes(ml, xl);
+    const FecoWarpedPlan plan = feco_warped_plan(F, k, D);
     const int cap = 4 * F;
     const hipStream_t s = (hipStream_t)stream;
-    const int sel = (D > 32 ? 4 : 0) | (xl ? 2 : 0) | ml;
-    switch (sel) {
+    hipError_t e = hipSuccess;
+    switch ((plan.wide ? 4 : 0) | (plan.xl ? 2 : 0) | plan.ml) {
 #define SG_WARP_CASE(W, X, M)                                                                                              \
     case (W ? 4 : 0) | (X ? 2 : 0) | M:                                                                                     \
-        launch_warped<W, X, M>(B, lds, s, feats_dev, F, D, k, init_mode, delta, key, index_base, rep_rows, cap,            \
-                               boundaries_dev, init_ids_dev, init_counts_dev, out_dev, sweeps_dev);                        \
+        e = launch_warped<W, X, M>(B, plan.lds, s, feats_dev, F, D, k, init_mode, delta, key, index_base, rep_rows, cap,   \
+                                   boundaries_dev, init_ids_dev, init_counts_dev, out_dev, sweeps_dev);                    \
         break;
         SG_WARP_CASE(false, false, false)
         SG_WARP_CASE(false, false, true)
@@ -382,10 +394,9 @@ extern "C" int sg_feco_warped(sg_ctx* ctx, const float* feats_dev, int32_t B, in
         SG_WARP_CASE(true, false, true)
         SG_WARP_CASE(true, true, true)
 #undef SG_WARP_CASE
-        default:
+        default:  // (frames in LDS without the means: feco_warped_plan never plans it)
             return fail(ctx, SG_ERR_ARG, "sg_feco_warped: no layout for F %d, D %d, k %d", F, D, k);
     }
-    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_warped: %s", hipGetErrorString(e));
     // the per-row status decides the return code: wait for it
     std::vector<int32_t> st((size_t)B);

@@ -75,6 +75,16 @@ __host__ __device__ inline FecoWideLds feco_wide_layout(int F, int k, int ng) {
     return L;
 }
 
+// What sg_feco_kmeans_compress_wide launches for a shape (pure): the dimension groups -- the instantiation -- and its dynamic LDS
+struct FecoWidePlan {
+    int ng;
+    size_t lds;
+};
+inline FecoWidePlan feco_wide_plan(int F, int k, int D) {
+    const int ng = (D + 7) / 8;
+    return {ng, (size_t)feco_wide_layout(F, k, ng).total * sizeof(float)};
+}
+
 // lanes 0 .. 63 hold 64 consecutive dimensions: the butterfly steps 1 .. 32 (row16_sum_dpp = steps 1, 2, 4, 8)
 __device__ __forceinline__ float tree64(float v) {
     v = row16_sum_dpp(v);
@@ -348,18 +358,17 @@ extern "C" int sg_feco_kmeans_compress_wide(sg_ctx* ctx, const float* feats_dev,
         max_iter <= 0)
         return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_wide: need feats, assign, out and counts, B > 0, 0 < k <= F, %d <= D <= %d, "
                          "max_iter > 0", kWideMinD, kWideMaxD);
-    const int ng = (D + 7) / 8;
-    const size_t lds = (size_t)feco_wide_layout(F, k, ng).total * sizeof(float);
-    if (lds > kWideLdsMax)
+    const FecoWidePlan plan = feco_wide_plan(F, k, D);
+    if (plan.lds > kWideLdsMax)
         return fail(ctx, SG_ERR_ARG, "sg_feco_kmeans_compress_wide: %d clusters x %d dims + %d frames need %zu bytes of LDS (limit %zu): "
-                         "utterance too long for one block", k, D, F, lds, kWideLdsMax);
+                         "utterance too long for one block", k, D, F, plan.lds, kWideLdsMax);
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SG_ERR_HIP, "sg_feco_kmeans_compress_wide: hipSetDevice failed");
     hipError_t e = hipErrorInvalidValue;
     const int seeded = random_init != 0;
     hipStream_t s = (hipStream_t)stream;
 #define SG_WIDE_CASE(n) \
-    case n: e = launch_wide<n>(feats_dev, B, F, D, k, max_iter, seeded, seed, index_base, assign_dev, out_dev, counts_dev, lds, s); break;
-    switch (ng) {
+    case n: e = launch_wide<n>(feats_dev, B, F, D, k, max_iter, seeded, seed, index_base, assign_dev, out_dev, counts_dev, plan.lds, s); break;
+    switch (plan.ng) {
         SG_WIDE_CASE(9) SG_WIDE_CASE(10) SG_WIDE_CASE(11) SG_WIDE_CASE(12) SG_WIDE_CASE(13) SG_WIDE_CASE(14) SG_WIDE_CASE(15) SG_WIDE_CASE(16)
     }
 #undef SG_WIDE_CASE

@@ -940,6 +940,151 @@ hipError_t launch_fakebob_step(float* x, float* grad, const float* prev_grad, co
                                const float* upper, int n, int T, float momentum, float one_m_momentum, int grad_sign,
                                hipStream_t s);
 
+// ---- FeCo k-means (k_feco.hip): what the kernel and its launcher share, and the launcher's plan
+constexpr int kFecoMaxD = 64;
+constexpr int kFecoThreads = 1024;
+constexpr int kFecoMaxChunks = 8;     // centroid-tile chunks a frame tile is cut into (JC)
+constexpr int kFecoMergeCap = 2048;   // JC * F <= this: capacity rule of the chunk-maxima arrays
+__host__ __device__ constexpr int al4(int n) { return (n + 3) & ~3; }
+
+// Which units of the assignment a wave computes (host-built): u[wave][slot] = frame tile | first centroid tile << 8 | one
+// past the last << 16 | chunk index << 24, kFecoNoUnit = none; table == 0: more than 32 units, dealt round robin in the kernel.
+constexpr unsigned kFecoNoUnit = 0xFFFFFFFFu;
+struct FecoSched {
+    int table;
+    unsigned u[kFecoThreads / 64][2];
+};
+
+// Two CUs per instance (round 5, VERDICT r4 item 1: "off the single CU").  An instance's k-means is bound by the MFMA +
+// VALU issue of the four SIMDs of the one CU its block gets, and a batch of 64 x 2 instances leaves half of the chip idle.
+// With `on` the grid's z dimension is the HALF: two blocks run the same instance redundantly -- same set-up, same lists,
+// same update, bit for bit -- and split only the assignment's units (sched / sched1; bit u of `owner` says whose unit
+// u = frame tile * JC + chunk is).  After its units a block stores its chunk maxima into its exchange buffer (two of them,
+// alternating by iteration) as self-describing 8-byte words -- score | index << 32 | tag << 43, tag = launch and iteration --
+// with write-through (sc1) stores, and polls the partner's words (sc1 loads) until they carry the tag it expects: one
+// store -> load visibility delay per iteration, no flag, no fence (the first version published a flag after draining the
+// stores: 3.2 us per iteration, as much as the split saved).  A word is accepted only with the exact tag, so stale or
+// overwritten data cannot be taken for the partner's; the buffers are zeroed when the launch counter wraps.
+// No block ever waits unboundedly, and no result depends on the partner showing up: if any word is not there after
+// kFecoPairWait the block computes the partner's units itself from then on (and says so in `flags`, which saves the
+// partner its own time-out).  The partner not showing up is what happens when something else occupies the GPU: same bits,
+// the single-CU speed (+ one time-out).
+struct FecoPair {
+    int on;
+    unsigned owner;
+    FecoSched sched1;
+    unsigned long long* xchg;  // [instance][half][buffer 0 / 1][kFecoMergeCap]
+    unsigned* flags;           // [instance][half]: launch id of the launch in which the block went on alone
+    unsigned tag0;             // this launch's tag base: (launch counter mod 2^15) << 6; a word's tag = tag0 + iteration + 1
+    unsigned launch;           // launch id
+    int drop;                  // test hook (sg_debug_lose_handoffs): half 1 publishes nothing
+};
+constexpr int kFecoPairMaxIter = 62;        // tag = 15 bits of launch counter, 6 of iteration
+constexpr size_t kFecoLdsMax = 150 * 1024;  // 150 KB cover ~19 s at D <= 32, ratio 0.5 (F = 1930, k = 965); beyond that the call is refused
+
+// Dynamic LDS of feco_kmeans_kernel in 4-byte words (every array 16-byte aligned); host and device use the same function.
+struct FecoLds {
+    int cq, hq, mu, part, ids, cnt, start, members, cw, spart, wtot, pd, pj, xq, total;
+};
+__host__ __device__ inline FecoLds feco_layout(int F, int k, int dpad, int JC, int fast_lists, int x_in_lds) {
+    const int kp = (k + 31) & ~31;
+    FecoLds L;
+    int o = 0;
+    L.cq = o; o += kp * dpad;              // centred centroids, [kp][dpad], 16-byte slots XOR-permuted per row
+    L.hq = o; o += kp;                     // -|c|^2 / 2
+    L.mu = o; o += dpad;
+    L.part = o; o += 16 * dpad;            // partial sums of the centring
+    L.ids = o; o += al4(F);
+    L.cnt = o; o += al4(k);
+    L.start = o; o += al4(k + 1);
+    L.members = o; o += al4(F);            // frames grouped by cluster, ascending inside a group
+    L.cw = o; o += fast_lists ? al4(((F + 63) >> 6) * k) : 0;   // members of cluster j among frames 64 c .. 64 c + 63
+    L.spart = o; o += fast_lists ? al4(k) : 0;                  // frames of the lower clusters of j's wave of clusters
+    L.wtot = o; o += fast_lists ? 16 : 0;                       // frames per wave of clusters
+    L.pd = o; o += JC > 1 ? al4(JC * F) : 0;                    // chunk maxima [chunk][frame]
+    L.pj = o; o += JC > 1 ? al4(JC * F) : 0;
+    L.xq = o; o += x_in_lds ? F * dpad : 0;                     // centred frames, same permuted rows
+    L.total = o;
+    return L;
+}
+
+// What feco_kmeans_impl launches for a shape: a pure function of its arguments (no HIP call, no context, no statics), so the
+// CPU build can walk it (tests/test_feco_plan_table.py, and the invariants in tests/native/feco_cos_asan_driver.cpp).  For
+// shapes feco_kmeans_check admits.  One thing is left to the launcher, because only the runtime knows it: a plan with `pair`
+// whose exchange buffers feco_pair_buffers cannot provide is planned again with allow_pair = false.
+struct FecoKnobs {
+    int two_cu = -1;  // sg_feco_set_two_cu: -1 where it fits, 0 never
+    int jc = 0;       // SG_FECO_JC (experiment builds only): this many chunks where the shape allows, 0 = the plan's own
+};
+struct FecoPlan {
+    int dpad, JC, x_in_lds, fast_lists;
+    size_t lds;
+    bool pair;                 // two blocks per instance
+    FecoSched sched0, sched1;  // units in sched1 and bits in owner only when pair
+    unsigned owner;
+};
+inline FecoPlan feco_plan(int F, int D, int k, int max_iter, long instances, int num_cus, bool allow_pair, const FecoKnobs& knobs) {
+    FecoPlan p{};
+    // LDS holds the centred centroids (rows padded to 32 / 64 floats), ids, member lists and -- when they fit -- the chunk
+    // counts of the fast member lists and the centred frames (else the frames are re-read from HBM / L2 in every step)
+    p.dpad = D <= 32 ? 32 : 64;
+    const auto bytes = [&](int jc, int fast, int xin) { return (size_t)feco_layout(F, k, p.dpad, jc, fast, xin).total * sizeof(float); };
+    // a frame tile's centroid tiles are cut into JC chunks (300 x 150: 10 frame tiles x 2 chunks of 3 / 2 tiles)
+    const int ntc = (k + 31) / 32, ntf = (F + 31) / 32;
+    int JC = (20 + ntf - 1) / ntf;  // >= 20 units for the 16 waves (5 per SIMD), each as many tiles as possible
+    JC = JC > ntc ? ntc : JC;
+    JC = JC > kFecoMaxChunks ? kFecoMaxChunks : JC;
+    while (JC > 1 && JC * F > kFecoMergeCap) --JC;
+    if (knobs.jc) {
+        JC = knobs.jc < 1 ? 1 : (knobs.jc > ntc ? ntc : knobs.jc);
+        while (JC > 1 && JC * F > kFecoMergeCap) --JC;
+    }
+    if (bytes(JC, 0, 0) > kFecoLdsMax) JC = 1;  // (one chunk fits: feco_kmeans_check)
+    p.JC = JC;
+    // two CUs per instance (FecoPair): when every instance can have two resident blocks, the units fit the tables and a bit
+    // mask, and the flag values have room for the iterations.  Same units as one block would get (cutting them finer -- 30
+    // units of 1-2 tiles for the 32 waves -- measured 94.3 against 92.5 us per call: the SIMDs are throughput-bound, the
+    // merge grows)
+    const int cus = num_cus > 0 ? num_cus : 256, nunits = ntf * JC;
+    p.pair = allow_pair && knobs.two_cu != 0 && p.dpad == 32 && 2 * instances <= cus && JC > 1 && nunits <= 32 &&
+             max_iter <= kFecoPairMaxIter && ((k + 31) & ~31) <= 2048;
+    // the assignment's units (frame tile, chunk jc of its centroid tiles [ntc jc / JC, ntc (jc + 1) / JC)) dealt to the waves:
+    // largest first, each to the least loaded SIMD (waves w, w + 4, w + 8, w + 12; of both blocks when paired) and there to the
+    // least loaded wave with a free slot -- 300 x 150: 20 units of 2 / 3 tiles -> 12 / 13 / 12 / 13 tiles per SIMD
+    constexpr int kWaves = kFecoThreads / 64;
+    if (nunits <= 2 * kWaves) {
+        p.sched0.table = p.sched1.table = 1;
+        int simd_load[8] = {}, wave_load[2 * kWaves] = {}, wave_n[2 * kWaves] = {};
+        for (int w = 0; w < kWaves; ++w) p.sched0.u[w][0] = p.sched0.u[w][1] = p.sched1.u[w][0] = p.sched1.u[w][1] = kFecoNoUnit;
+        const auto bin = [&](int w) { return (w / kWaves) * 4 + (w & 3); };
+        for (int size = ntc; size >= 1; --size)
+            for (int u = 0; u < nunits; ++u) {
+                const int ft = u / JC, jc = u - ft * JC, lo = ntc * jc / JC, hi = ntc * (jc + 1) / JC;
+                if (hi - lo != size) continue;
+                int best_w = -1;
+                for (int w = 0; w < (p.pair ? 2 : 1) * kWaves; ++w) {
+                    if (wave_n[w] >= 2) continue;
+                    if (best_w < 0 || simd_load[bin(w)] < simd_load[bin(best_w)] ||
+                        (simd_load[bin(w)] == simd_load[bin(best_w)] && wave_load[w] < wave_load[best_w]))
+                        best_w = w;
+                }
+                const unsigned word = (unsigned)ft | (unsigned)lo << 8 | (unsigned)hi << 16 | (unsigned)jc << 24;
+                if (best_w < kWaves) p.sched0.u[best_w][wave_n[best_w]] = word;
+                else {
+                    p.sched1.u[best_w - kWaves][wave_n[best_w]] = word;
+                    p.owner |= 1u << u;
+                }
+                ++wave_n[best_w];
+                wave_load[best_w] += size;
+                simd_load[bin(best_w)] += size;
+            }
+    }
+    p.x_in_lds = bytes(JC, 0, 1) <= kFecoLdsMax;
+    p.fast_lists = F <= kFecoThreads && bytes(JC, 1, p.x_in_lds) <= kFecoLdsMax;
+    p.lds = bytes(JC, p.fast_lists, p.x_in_lds);
+    return p;
+}
+
 // FeCo (k_feco.hip).  What sg_feco_kmeans_compress(_rows) refuses about a (B, reps) grid of F x D clusterings into k groups,
 // said without a launch: SG_OK or SG_ERR_ARG with the error text set
 int feco_kmeans_check(sg_ctx* ctx, int B, int F, int D, int k, int max_iter, int reps);

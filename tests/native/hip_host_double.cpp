@@ -7,6 +7,7 @@
 // calloc (so AddressSanitizer sees every upload / download the host half performs with its true extent), events are
 // counters, and a kernel launch is counted, shown to the launch hook (if one is set) and otherwise ignored -- no
 // kernel arithmetic runs here, GPU results are the business of `pytest -m gpu`.  Runs in the GPU-less build container.
+// hipMemsetAsync calls are counted too (hipdouble_memset_asyncs: the wipe of the FeCo exchange buffers is one).
 // The device the double plays can be resized from the environment, read at every query: HIPDOUBLE_CUS (compute units,
 // default 256), HIPDOUBLE_OCCUPANCY (the answer to hipOccupancyMaxActiveBlocksPerMultiprocessor, default 2) and
 // HIPDOUBLE_REFUSE_LDS=1 (hipFuncSetAttribute refuses a request for 160 KB or more: a device whose blocks cannot have the whole
@@ -19,7 +20,7 @@
 #include <map>
 #include <string>
 
-static long g_launches = 0, g_allocs = 0, g_frees = 0, g_bytes = 0;
+static long g_launches = 0, g_allocs = 0, g_frees = 0, g_bytes = 0, g_memset_asyncs = 0;
 static dim3 g_grid, g_block;
 static size_t g_shmem = 0;
 static hipStream_t g_stream = nullptr;
@@ -40,6 +41,7 @@ extern "C" {
 
 long hipdouble_launches() { return g_launches; }
 long hipdouble_live_allocs() { return g_allocs - g_frees; }
+long hipdouble_memset_asyncs() { return g_memset_asyncs; }
 void hipdouble_set_launch_hook(hipdouble_launch_hook hook) { g_hook = hook; }
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
@@ -70,7 +72,7 @@ hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); ++g_memset_asyncs; return hipSuccess; }
 // device globals: the host-only objects keep a host shadow of every __device__ variable; copy to / from that
 hipError_t hipMemcpyToSymbol(const void* sym, const void* src, size_t n, size_t off, hipMemcpyKind) {
     std::memmove(const_cast<char*>(static_cast<const char*>(sym)) + off, src, n);

@@ -49,6 +49,9 @@ def test_kmeans_ids_bit_exact(hip_model):
     from oracle import feco
     from speakerguard_amd import synth
     rs = np.random.RandomState(4)
+    # every branch of the launcher's plan (feco_plan; tests/test_feco_plan_table.py prints what each shape takes): paired blocks
+    # (3x300x30), one block with a unit table (2x77x13), no table + frames not in LDS + slow lists (2x1500x30), frames in LDS with
+    # slow lists (2x700x32), 64-column operands (1x90x64)
     mfcc = hip_model.compute_feat(torch.from_numpy(synth.make_waveforms(3, 48000, seed=70)).to(DEV), flag=1).cpu()
     cases = [("mfcc 3x300x30", mfcc, 0.5), ("random 2x77x13", torch.from_numpy(rs.randn(2, 77, 13).astype(np.float32)), 0.3),
              ("logmel-like 2x300x32", torch.from_numpy((rs.randn(2, 300, 32) * 10 - 40).astype(np.float32)), 0.5),

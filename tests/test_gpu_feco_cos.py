@@ -50,10 +50,14 @@ _POOL = {}
 
 def _features(B, F, D, seed=70):
     """oracle-style features (mean |x| 6 .. 10, like the CPU test's): D 30 the oracle's MFCC, 32 its log-mel, wider ones the
-    MFCC with log-mel columns behind it; the first F frames of 3 s utterances"""
+    MFCC with log-mel columns behind it; the first F frames of 3 s utterances (more frames than those have: row b is the utterances
+    b, b + 1, b + 2, b, ... one after the other -- from frame 900 on it repeats its own frames, exact ties)"""
     from oracle import audionet as oan
     from oracle import kaldi_mfcc
     from speakerguard_amd import synth
+    if F > 300:
+        f = _features(3, 300, D, seed)
+        return torch.cat([f.roll(-i, 0) for i in range((F + 299) // 300)], dim=1)[:B, :F].contiguous()
     if seed not in _POOL:
         x = torch.from_numpy(synth.make_waveforms(3, 48000, seed=seed))
         mfcc = kaldi_mfcc.mfcc_batch(x * 32768.0).float()
@@ -90,7 +94,8 @@ SHAPES = [(50, 25, 30),     # one centroid tile, D padded to 32
           (300, 150, 32),   # the schedule the kernel's comments are written for
           (70, 14, 40),     # DPAD 64, never paired
           (33, 33, 30),     # k = F
-          (40, 1, 30)]      # k = 1
+          (40, 1, 30),      # k = 1
+          (1025, 65, 32)]   # 33 frame tiles: no unit table (dealt in the kernel), the slow member lists, frames not in LDS
 
 
 @pytest.mark.parametrize("F,k,D", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
